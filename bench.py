@@ -56,7 +56,12 @@ def parse(argv=None):
     ap.add_argument("--cpu-batch", type=int, default=32, help="batch of the bounded CPU-oracle sample (default: the workload's own)")
     ap.add_argument("--cpu-steps", type=int, default=2, help="timed oracle steps of the CPU sample (~13 s of CPU work at batch 32)")
     ap.add_argument("--cpu-threads", type=int, default=16, help="host threads for the CPU-oracle sample")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (its scalars, the updated G / D / G_ema) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def make_trainer(args, rank, local_rank, world):
@@ -183,6 +188,27 @@ def soak(tr, steps):
     return {"steps": steps, "ms_per_step_wall": round(1e3 * dt / steps, 4), "seconds": round(dt, 2),
             "step_ms_device": {"p10": q(0.10), "p50": q(0.50), "p90": q(0.90), "p99": q(0.99), "min": round(per[0], 4),
                                "max": round(per[-1], 4)}}
+
+
+DUMP_SAMPLE = 1 << 18   # elements kept of a larger tensor: G's 67M-element projection alone would be 268 MB
+
+
+def dump_outputs(tr, scal, path):
+    """What the timed path hands its caller after its last step: the step's scalars (float64) and the networks it updated in
+    place - the G, D and G_ema state dicts (float32) - as <path>/<name>.npy.  A tensor of more than DUMP_SAMPLE elements is
+    stored as a sample of its flattened elements: the same seeded, sorted indices in every run, so that two builds run with
+    the same arguments (hence the same seeded inputs) can be compared file for file.  About 10 MB at the default workload."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in scal.items():
+        np.save(os.path.join(path, "scalar." + k.replace("/", ".") + ".npy"), np.array(v, np.float64))
+    for net in ("G", "D", "G_ema"):
+        for k, v in getattr(tr, net).state_dict().items():
+            v = v.detach()
+            if v.numel() > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(0).choice(v.numel(), DUMP_SAMPLE, replace=False))
+                v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+            np.save(os.path.join(path, f"{net}.{k}.npy"), v.float().cpu().numpy())
 
 
 def held_clock():
@@ -641,6 +667,8 @@ def main():
         t = torch.tensor([dt], device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, scal, args.dump_outputs)
     ms = 1e3 * dt / args.steps
     steps_s = args.steps / dt
     imgs = steps_s * args.batch * world

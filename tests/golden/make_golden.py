@@ -15,6 +15,7 @@ usage:  python tests/golden/make_golden.py            (writes tests/golden/*.npz
         python tests/golden/make_golden.py metrics    (only metrics.npz)
         python tests/golden/make_golden.py full       (only full_dusty2.npz: the 64x1024 / 512-channel pin, digests)
         python tests/golden/make_golden.py covmmd     (only covmmd.npz: COV / MMD / 1-NNA from the reference's functions)
+        python tests/golden/make_golden.py chamfer    (only chamfer.npz: the reference's CPU nearest-neighbour search)
 """
 import importlib.util
 import math
@@ -544,6 +545,43 @@ def make_covmmd_golden():
     print("wrote", path, f"{os.path.getsize(path) / 1024:.0f} KiB", {k: round(v, 4) for k, v in res.items()})
 
 
+def make_chamfer_golden():
+    """The reference's OWN CPU nearest-neighbour search - `nnsearch` of utils/metrics/distance/cd/chamfer_distance.cpp:39-66,
+    compiled from its source by oracle/Makefile.ref into oracle/_ref/libref_cd.so - on seeded clouds: ragged sizes,
+    duplicate points (ties), one-point clouds.  Per case: `dist` / `idx` [Na, Nb, n] = nnsearch(A[i], B[j]) for every pair,
+    and where Na == Nb `dist_rev` / `idx_rev` [Na, m] = nnsearch(B[i], A[i]).  tests/test_oracle_golden.py pins
+    oracle/metrics_oracle.py's Chamfer restatement to these outputs (and to the library itself wherever it is built)."""
+    import ctypes
+    so = os.path.join(os.path.dirname(os.path.dirname(HERE)), "oracle", "_ref", "libref_cd.so")
+    lib = ctypes.CDLL(so)
+    vp = ctypes.c_void_p
+
+    def nnsearch(x1, x2):  # x1 [n,3], x2 [m,3] -> dist [n], idx [n]
+        x1, x2 = np.ascontiguousarray(x1, np.float32), np.ascontiguousarray(x2, np.float32)
+        dist, idx = np.zeros(x1.shape[0], np.float32), np.zeros(x1.shape[0], np.int32)
+        lib.ref_cd_nnsearch(1, x1.shape[0], x2.shape[0], x1.ctypes.data_as(vp), x2.ctypes.data_as(vp),
+                            dist.ctypes.data_as(vp), idx.ctypes.data_as(vp))
+        return dist, idx
+
+    rng = np.random.default_rng(3)
+    cases = ((3, 17, 4, 9), (2, 1, 2, 5), (5, 64, 5, 64), (1, 200, 3, 33))
+    d = {"meta/cases": np.array(len(cases))}
+    for c, (Na, n, Nb, m) in enumerate(cases):
+        A = rng.standard_normal((Na, n, 3)).astype(np.float32)
+        B = rng.standard_normal((Nb, m, 3)).astype(np.float32)
+        B[:, -1] = B[:, 0]  # duplicate points: ties
+        d[f"{c}/A"], d[f"{c}/B"] = A, B
+        pairs = [[nnsearch(A[i], B[j]) for j in range(Nb)] for i in range(Na)]
+        d[f"{c}/dist"] = np.stack([np.stack([p[0] for p in row]) for row in pairs])
+        d[f"{c}/idx"] = np.stack([np.stack([p[1] for p in row]) for row in pairs])
+        if Na == Nb:
+            rev = [nnsearch(B[i], A[i]) for i in range(Na)]
+            d[f"{c}/dist_rev"], d[f"{c}/idx_rev"] = np.stack([r[0] for r in rev]), np.stack([r[1] for r in rev])
+    path = os.path.join(HERE, "chamfer.npz")
+    np.savez_compressed(path, **d)
+    print("wrote", path, f"{os.path.getsize(path) / 1024:.0f} KiB")
+
+
 def make_full_golden(name="full_dusty2", arch="dusty2", seed=20261, B=2, shape=(64, 1024), in_ch=512, ch_base=64,
                      ch_max=512, autocast=False):
     """One step of the REFERENCE's modules at the benchmark's full width (BASELINE configs 2-4: 64x1024, 512 latent,
@@ -688,6 +726,9 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["covmmd"]:
         make_covmmd_golden()
         sys.exit(0)
+    if sys.argv[1:] == ["chamfer"]:
+        make_chamfer_golden()
+        sys.exit(0)
     if sys.argv[1:] == ["full"]:
         torch.set_num_threads(8)
         make_full_golden()
@@ -719,4 +760,5 @@ if __name__ == "__main__":
     make_lidar_golden()
     make_metrics_golden()
     make_covmmd_golden()
+    make_chamfer_golden()
     make_full_golden()

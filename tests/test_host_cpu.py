@@ -448,3 +448,38 @@ def test_two_word_fixed_point_split_is_exact():
     big = np.abs(v) >= 2.0 ** -36
     tot = Fraction(sum(int(x) for x in hi[big]), 2 ** 20) + Fraction(sum(int(x) for x in lo[big]), 2 ** 60)
     assert tot == sum((Fraction(float(x)) for x in v[big]), Fraction(0))
+
+
+def test_bench_dump_outputs_are_float_arrays_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the step's scalars as float64, every G / D / G_ema state-dict tensor as float32 - whole up to
+    DUMP_SAMPLE elements, above it the same seeded sample of its flattened elements in every run"""
+    import types
+    import bench
+    from dusty_gan_amd.models import define_G, define_D
+    from dusty_gan_amd.utils.config import load_config
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    cfg = load_config(["model=dusty2_dcgan_eqlr", "dataset=synthetic", "dataset.shape=[32,64]", "model.gen.in_ch=16",
+                       "model.gen.ch_base=8", "model.gen.ch_max=32", "model.dis.ch_base=8", "model.dis.ch_max=32"])
+    cfg.model.gen.shape = cfg.dataset.shape
+    cfg.model.dis.shape = cfg.dataset.shape
+    torch.manual_seed(0)
+    tr = types.SimpleNamespace(G=define_G(cfg), D=define_D(cfg), G_ema=define_G(cfg))
+    scal = {"loss/D/adversarial": 0.25, "loss/G/adversarial": 1.5}
+    bench.dump_outputs(tr, scal, str(tmp_path / "a"))
+    bench.dump_outputs(tr, scal, str(tmp_path / "b"))
+    assert float(np.load(tmp_path / "a" / "scalar.loss.G.adversarial.npy")) == 1.5
+    sampled = 0
+    for net in ("G", "D", "G_ema"):
+        for k, v in getattr(tr, net).state_dict().items():
+            a = np.load(tmp_path / "a" / f"{net}.{k}.npy")
+            assert a.dtype == np.float32
+            assert np.array_equal(a, np.load(tmp_path / "b" / f"{net}.{k}.npy"))
+            flat = v.detach().reshape(-1).numpy()
+            if v.numel() <= 1000:
+                assert np.array_equal(a, v.detach().numpy())
+            else:
+                sampled += 1
+                assert a.shape == (1000,) and np.isin(a, flat).all()
+    assert sampled > 0
+    files = list((tmp_path / "a").iterdir())
+    assert len(files) == len(scal) + sum(len(getattr(tr, n).state_dict()) for n in ("G", "D", "G_ema"))

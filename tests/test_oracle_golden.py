@@ -335,15 +335,16 @@ def test_swd_oracle_matches_reference():
 def test_chamfer_oracle_pinned_by_the_reference_nnsearch():
     """oracle/metrics_oracle.py `chamfer_dir` against the reference's OWN nearest-neighbour search: `nnsearch` of
     utils/metrics/distance/cd/chamfer_distance.cpp:39-66, compiled from the reference's source file by
-    oracle/Makefile.ref into oracle/_ref/libref_cd.so (built by __graft_entry__.build() where /root/reference exists;
-    the .so travels to the GPU box).  Ragged sizes, duplicate points (first index wins on ties), one-point clouds."""
+    oracle/Makefile.ref into oracle/_ref/libref_cd.so.  Its outputs on these clouds are stored in tests/golden/chamfer.npz
+    (make_golden.py chamfer); wherever the library has been built (__graft_entry__.build() with the reference's sources
+    at hand) the fixture is also checked against it, bit for bit.  Ragged sizes, duplicate points (first index wins on
+    ties), one-point clouds."""
     import ctypes
     import os
     from oracle import metrics_oracle as MO
+    g = load("chamfer")
     so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libref_cd.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref/libref_cd.so not built (make -f oracle/Makefile.ref needs /root/reference)")
-    lib = ctypes.CDLL(so)
+    lib = ctypes.CDLL(so) if os.path.exists(so) else None
     vp = ctypes.c_void_p
 
     def ref_nnsearch(x1, x2):  # x1 [b,n,3], x2 [b,m,3] -> dist [b,n], idx [b,n]
@@ -352,22 +353,31 @@ def test_chamfer_oracle_pinned_by_the_reference_nnsearch():
         dist, idx = np.zeros((b, n), np.float32), np.zeros((b, n), np.int32)
         lib.ref_cd_nnsearch(b, n, m, x1.ctypes.data_as(vp), x2.ctypes.data_as(vp), dist.ctypes.data_as(vp), idx.ctypes.data_as(vp))
         return dist, idx
-    rng = np.random.default_rng(3)
-    for Na, n, Nb, m in ((3, 17, 4, 9), (2, 1, 2, 5), (5, 64, 5, 64), (1, 200, 3, 33)):
-        A = rng.standard_normal((Na, n, 3)).astype(np.float32)
-        B = rng.standard_normal((Nb, m, 3)).astype(np.float32)
-        B[:, -1] = B[:, 0]  # duplicate points: ties
+    for c in range(int(g["meta/cases"])):
+        A, B = g[f"{c}/A"], g[f"{c}/B"]
+        Na, Nb = A.shape[0], B.shape[0]
+        dist, idx = g[f"{c}/dist"], g[f"{c}/idx"]   # [Na, Nb, n]: nnsearch(A[i], B[j])
+        assert (B[:, -1] == B[:, 0]).all()          # duplicate points: ties
+        if lib is not None:
+            for i in range(Na):
+                for j in range(Nb):
+                    d, k = ref_nnsearch(A[i][None], B[j][None])
+                    assert np.array_equal(d[0], dist[i, j]) and np.array_equal(k[0], idx[i, j]), (c, i, j)
         L = MO.chamfer_dir(A, B).numpy()
         for i in range(Na):
             for j in range(Nb):
-                d, _ = ref_nnsearch(A[i][None], B[j][None])
+                d = dist[i, j]
                 assert abs(L[i, j] - d.mean()) <= 1e-6 * max(1.0, abs(d.mean())), (i, j)
         # compute_cd of cov_mmd_1nna.py:20-22 = dl.mean + dr.mean
         if Na == Nb:
+            dist_rev = g[f"{c}/dist_rev"]           # [Na, m]: nnsearch(B[i], A[i])
+            if lib is not None:
+                for i in range(Na):
+                    d, k = ref_nnsearch(B[i][None], A[i][None])
+                    assert np.array_equal(d[0], dist_rev[i]) and np.array_equal(k[0], g[f"{c}/idx_rev"][i]), (c, i)
             M = MO.pairwise_cd(A, B).numpy()
             for i in range(Na):
-                dl, _ = ref_nnsearch(A[i][None], B[i][None])
-                dr, _ = ref_nnsearch(B[i][None], A[i][None])
+                dl, dr = dist[i, i], dist_rev[i]
                 assert abs(M[i, i] - (dl.mean() + dr.mean())) <= 1e-6 * max(1.0, abs(M[i, i]))
 
 
