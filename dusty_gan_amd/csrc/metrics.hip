@@ -97,6 +97,9 @@ constexpr int CH_WPTS = 64 * CH_PT;      // points of A per wave
 constexpr int CH_MC = 512;               // points of B per LDS chunk (8 KB), two buffers
 constexpr int CH_LD = CH_MC / CH_THREADS;  // chunk points loaded per thread
 
+// PAIRED: cloud A_i against B_i only (L[i]); the workgroup then owns one cloud (wpc >= 4) and streams just B_i - the same
+// per-wave arithmetic and sums as the diagonal of the all-pairs launch.
+template <bool PAIRED>
 __global__ __launch_bounds__(CH_THREADS) void chamfer_dir_kernel(const float* __restrict__ A, int Na, int n, int wpc,
                                                                  const float* __restrict__ Bc, int Nb, int m, int TB,
                                                                  float* __restrict__ L) {
@@ -121,7 +124,7 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_dir_kernel(const float* __
       pz[h][e] = a[pp * 3 + 2];
     }
   }
-  const int j0 = blockIdx.x * TB, j1 = min(Nb, j0 + TB);
+  const int j0 = PAIRED ? i : blockIdx.x * TB, j1 = PAIRED ? i + 1 : min(Nb, j0 + TB);
   const int nchunk = (m + CH_MC - 1) / CH_MC;
   const int total = (j1 - j0) * nchunk;  // (cloud, chunk) steps of this workgroup
   float r[CH_LD][3];
@@ -172,7 +175,7 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_dir_kernel(const float* __
       }
       s = dg_wave_sum(s);
       if (lane == 0 && live && slice * CH_WPTS < n) {
-        float* dst = &L[(long)i * Nb + j0 + step / nchunk];
+        float* dst = PAIRED ? &L[i] : &L[(long)i * Nb + j0 + step / nchunk];
         if (wpc == 1) *dst = s / (float)n;
         else atomicAdd(dst, s / (float)n);
       }
@@ -412,7 +415,20 @@ int dg_chamfer_dir(const float* A, int Na, int n, const float* Bc, int Nb, int m
   while (TB > 1 && (long)((Nb + TB - 1) / TB) * gy * gz < 2048) TB >>= 1;
   const dim3 grid((Nb + TB - 1) / TB, gy, gz);
   if (grid.y > 65535 || grid.z > 65535) return DG_EUNSUPPORTED;
-  chamfer_dir_kernel<<<grid, CH_THREADS, 0, s>>>(A, Na, n, wpc, Bc, Nb, m, TB, L);
+  chamfer_dir_kernel<false><<<grid, CH_THREADS, 0, s>>>(A, Na, n, wpc, Bc, Nb, m, TB, L);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
+
+int dg_chamfer_paired(const float* A, int n, const float* Bc, int m, int B, float* L, void* s_) {
+  if (!A || !Bc || !L || B <= 0 || n <= 0 || m <= 0) return DG_EINVAL;
+  hipStream_t s = (hipStream_t)s_;
+  // whole workgroups per cloud (a workgroup streams ONE cloud B_i); slices past n hold no points and store nothing
+  const int wpc = (n + 4 * CH_WPTS - 1) / (4 * CH_WPTS) * 4;
+  if (B > 65535 || wpc / 4 > 65535) return DG_EUNSUPPORTED;
+  const int zrc = dg_zero_f32(L, B, s);
+  if (zrc) return zrc;
+  chamfer_dir_kernel<true><<<dim3(1, B, wpc / 4), CH_THREADS, 0, s>>>(A, B, n, wpc, Bc, B, m, 1, L);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }

@@ -456,32 +456,7 @@ __global__ __launch_bounds__(256) void transpose_shadow_kernel(const float* __re
   }
 }
 
-// ----------------------------------------------------------------------------------------------------------
-// Philox4x32-10 (Salmon et al., SC'11; the counter-based generator torch's device RNG also uses).  One call of
-// philox(counter=(i,0,0,0) + offset, key=seed) yields 4 x 32 random bits for element group i.
-__host__ __device__ inline void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0,
-                                             uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-  const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-  const uint32_t n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-  const uint32_t n3 = (uint32_t)p0;
-  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
-
-__host__ __device__ inline void philox4x32_10(uint64_t seed, uint64_t ctr_lo, uint64_t ctr_hi, uint32_t out[4]) {
-  uint32_t c0 = (uint32_t)ctr_lo, c1 = (uint32_t)(ctr_lo >> 32), c2 = (uint32_t)ctr_hi, c3 = (uint32_t)(ctr_hi >> 32);
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c0, c1, c2, c3, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
+// (philox4x32_10: common.h)
 // raw bits: out[4*i + j] = philox(seed, counter = (offset + i, stream))[j]
 __global__ void philox_bits_kernel(uint64_t seed, uint64_t stream, uint64_t offset, long n4, uint32_t* __restrict__ out) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

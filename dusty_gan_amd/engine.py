@@ -943,9 +943,10 @@ class GEngine:
         self.HW = HW
         self.ws_B = B
 
-    def forward(self, st: ParamStore, z, noise=None, training=True, z_ready=False):
+    def forward(self, st: ParamStore, z, noise=None, training=True, z_ready=False, want_sums=True):
         """z [B,nz] fp32; noise: dict(pixel [B,1,H,W], image [B,1,1,1]) logistic noise (dusty archs).
         z_ready: self.zT already holds z in the compute dtype (written by the launch that drew z: dg_step_prologue).
+        want_sums=False: no per-sample depth sums into the step's accumulator arena (GAN inversion: no DiffAugment reads them).
         Returns the reference's output dict (views of engine workspaces)."""
         c, o, lib = self.cfg, self.ops, L.lib()
         B = z.shape[0]
@@ -993,7 +994,7 @@ class GEngine:
             self.noise_image = noise["image"].contiguous().float() if (arch == 2 and training) else None
             if arch == 2 and training and self.noise_image is None:
                 raise ValueError("dusty2 in training mode needs image-level noise")
-        sums = L.AccArena.take(B, self.depth.device) if self.HW % 256 == 0 else None
+        sums = L.AccArena.take(B, self.depth.device) if (self.HW % 256 == 0 and want_sums) else None
         hp_args = (L.ptr(self.gout), L.ptr(self.noise_pixel) if arch else None,
                    L.ptr(self.noise_image) if arch == 2 and training else None, arch, int(training), c.tau, c.drop_const, B,
                    self.HW, L.ptr(self.mask), L.ptr(self.depth))
@@ -1111,21 +1112,24 @@ class GEngine:
             self.proj_wgrad(st, self.dp[0], self.zT, B, accumulate_proj)
 
     # ------------------------------------------------------------------ path-length regulariser (trainers/dcgan_amp.py:268-306)
-    def _backward_chain(self, st, ddepth, draw, draw_pm, dp, acts, chain, second_of, thead=None):
+    def _backward_chain(self, st, ddepth, draw, draw_pm, dp, acts, chain, second_of, thead=None, head_ready=False):
         """One walk down the generator from the head to Proj's pre-activation.
         acts is None  : data only (first-order chain of d(sum x y)/dz).
+        head_ready    : (data only) `draw` / `draw_pm` already hold the head gradient (GAN inversion: dg_inv_loss_grad
+                        writes it), no dg_head_post_bwd; ddepth is not read.
         acts given    : the forward-over-reverse walk.  `draw`/`dp` receive the TANGENT gradient chain (upstream =
                         Hessian of the head post-processing applied to `thead`); weight gradients accumulate
                         a (x) tangent-chain + tangent-activations (x) first-order chain, bias gradients the sums of
                         the tangent chain.  acts = tangent activations, chain = (draw1, draw_pm1, dp1) of the
                         first-order walk."""
         c, o, lib = self.cfg, self.ops, L.lib()
-        B = ddepth.shape[0]
+        B = self.ws_B if head_ready else ddepth.shape[0]
         sp = L.stream_ptr()
         chs = [c.ch[3], c.ch[2], c.ch[1], c.ch[0]]
         arch = ARCH_ID[c.arch]
         s_depth, s_conf = self.head_scales
         full = acts is not None
+        assert not (full and head_ready)
         g = st.grad
         common = (L.ptr(self.gout), L.ptr(self.noise_pixel) if arch else None,
                   L.ptr(self.noise_image) if arch == 2 else None, L.ptr(self.mask) if arch else None, L.ptr(ddepth))
@@ -1133,7 +1137,7 @@ class GEngine:
             L.check(lib.dg_head_post_bwd2(*common, L.ptr(thead), arch, c.tau, c.drop_const, B, self.HW, s_depth, s_conf,
                                           L.ptr(draw), st.fptr("head_b", g), L.ptr(draw_pm), self.cp, sp),
                     "dg_head_post_bwd2")
-        else:
+        elif not head_ready:
             L.check(lib.dg_head_post_bwd(*common, arch, c.tau, c.drop_const, B, self.HW, s_depth, s_conf,
                                          None if draw_pm is not None else L.ptr(draw),   # (pixel-major copy only)
                                          None, L.ptr(draw_pm), self.cp, None, sp), "dg_head_post_bwd")
@@ -1174,13 +1178,25 @@ class GEngine:
         dz^T [nz][B] = s * sum_n' W[n'][:] (x) dp0[:, n'] - a reduction over Proj's 131 072 output rows, i.e. the
         weight-gradient GEMM shape (wmode 2: rows = "pixels") with W as the layer input and dp0^T, zero-padded to 64
         columns, as the gradient; split-K on the MFMA kernel instead of a one-off VALU kernel."""
+        return self.grad_z_T(st)[:, :self.ws_B].t().contiguous()
+
+    def grad_z_buffers(self):
+        """allocate (once per batch size) grad_z's operand dp0^T, zero-padded to Bp columns, and its result; returns Bp"""
+        c = self.cfg
+        Np = c.h0 * c.w0 * c.ch[3]
+        Bp = (self.ws_B + 63) // 64 * 64
+        if getattr(self, "_dzT", None) is None or self._dzT.shape != (Np, Bp) or self._dzT.dtype != self.dtype:
+            self._dzT = torch.zeros(Np, Bp, dtype=self.dtype, device=self.dp[0].device)
+            self._dzw = torch.empty(c.nz, Bp, dtype=torch.float32, device=self.dp[0].device)
+        return Bp
+
+    def grad_z_T(self, st: ParamStore):
+        """grad_z's result in place: the engine's fixed buffer dz^T [nz][Bp] (Bp = B rounded up to 64; column b = sample b),
+        the operand of a replayed step's optimizer (GAN inversion)."""
         c = self.cfg
         B = self.ws_B
         Np = c.h0 * c.w0 * c.ch[3]
-        Bp = (B + 63) // 64 * 64
-        if getattr(self, "_dzT", None) is None or self._dzT.shape != (Np, Bp):
-            self._dzT = torch.zeros(Np, Bp, dtype=self.dtype, device=self.dp[0].device)
-            self._dzw = torch.empty(c.nz, Bp, dtype=torch.float32, device=self.dp[0].device)
+        Bp = self.grad_z_buffers()
         dp0 = x2_unpack(self.dp[0]) if is_x2(self.dp[0]) else self.dp[0]
         self._dzT[:, :B].copy_(dp0.view(B, Np).t())
         L.zero_(self._dzw)
@@ -1189,7 +1205,7 @@ class GEngine:
         R = 512 if Np % (512 * 64) == 0 else 1
         self.ops.wgrad(2, 1, R, 1, Np // R, c.nz, Bp, shadow, ((Np // R) * c.nz, c.nz, 1), self._dzT,
                        ((Np // R) * Bp, Bp, 1), L.ptr(self._dzw), 1.0 / math.sqrt(Np), accumulate=1)
-        return self._dzw[:, :B].t().contiguous()
+        return self._dzw
 
     def tangent_forward(self, st: ParamStore, v):
         """Forward-mode derivative of the head pre-activations along the latent direction v [B,nz]: the generator with
@@ -1228,6 +1244,29 @@ class GEngine:
         the operand list of the fused optimizer / the all-gather)."""
         self._backward_chain(st, y, self.draw2, self.draw_pm2, self.dp2, acts=self.ta,
                              chain=(self.draw, self.draw_pm, self.dp), second_of=proj_terms, thead=self.tout)
+
+
+    # ------------------------------------------------------------------ GAN inversion (evaluate_reconstruction.py:93-118)
+    def inversion_step(self, st: ParamStore, S):
+        """One step of the latent optimiser on the frozen generator `st` (S: dusty_gan_amd.inversion.InvState, every buffer
+        allocated before the loop): forward in eval mode on self.zT (latent + this step's perturbation, written by the previous
+        step's optimizer launch) -> dg_inv_loss_grad (per-sample masked loss and the head gradient, in place of
+        dg_head_post_bwd) -> the data-only backward-data chain -> grad_z into its fixed buffer -> dg_sphere_adam (Adam,
+        renormalisation, the next step's perturbed latent into self.zT).  No parameter, gradient or counter of the model is
+        touched: the step's only state is S's.  Returns the forward's output dict (views of engine workspaces)."""
+        c, lib = self.cfg, L.lib()
+        B, sp = S.B, L.stream_ptr()
+        out = self.forward(st, S.latent, S.gumbel, training=False, z_ready=True, want_sums=False)
+        pm = self.draw_pm is not None   # bf16: the chain reads the pixel-major copy only
+        L.check(lib.dg_inv_loss_grad(L.ptr(self.gout), c.nheads * self.HW, 1, L.ptr(S.ref), L.ptr(S.mask), L.ptr(S.msum),
+                                     S.l2, B, self.HW, self.head_scales[0], None if pm else L.ptr(self.draw), c.nheads,
+                                     L.ptr(self.draw_pm), self.cp, L.ptr(S.parts), L.ptr(S.tickets), S.nchunk,
+                                     L.ptr(S.loss), sp), "dg_inv_loss_grad")
+        self._backward_chain(st, None, self.draw, self.draw_pm, self.dp, acts=None, chain=None, second_of=None,
+                             head_ready=True)
+        dzT = self.grad_z_T(st)
+        S.optimizer_launch(dzT, self.zT, L.dtype_code(self.dtype))
+        return out
 
 
 class AugGrad:

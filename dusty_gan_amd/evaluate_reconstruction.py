@@ -1,0 +1,92 @@
+"""Reconstruction evaluation by GAN inversion -- reference: evaluate_reconstruction.py (same flags, same CSV).
+
+    python -m dusty_gan_amd.evaluate_reconstruction --model-path <ckpt.pth> --config-path <config.yaml>
+        [--save-dir-path .] [--tol 0] [--batch-size 512] [--distance l1|l2] [--num-step 1000]
+
+Every test scan is reconstructed by optimising the latent of the EMA generator (dusty_gan_amd.inversion.invert), then
+scored per scan: Chamfer distance of the point clouds, depth accuracy / error, and the drop ratios."""
+import argparse
+import csv
+import datetime
+import os
+import os.path as osp
+
+COLUMNS = ["cd", "accuracy_1", "accuracy_2", "accuracy_3", "rmse", "rmse_log", "abs_rel", "sq_rel", "tol", "drop_gen",
+           "drop_ref"]
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--model-path", type=str, required=True)
+    parser.add_argument("--config-path", type=str, required=True)
+    parser.add_argument("--save-dir-path", type=str, default=".")
+    parser.add_argument("--tol", type=float, default=0)
+    parser.add_argument("--batch-size", type=int, default=512)
+    parser.add_argument("--distance", default="l1", choices=["l1", "l2"])
+    parser.add_argument("--num-step", type=int, default=1000)
+    return parser.parse_args(argv)
+
+
+def flatten(t):
+    """utils.flatten (utils/__init__.py:213-214): [B,C,H,W] -> [B,HW,C]"""
+    return t.flatten(2).permute(0, 2, 1).contiguous()
+
+
+def evaluate_batch(G, lidar, arch, item, args):
+    """one batch of the reference's loop body (:80-152) -> {column: list}"""
+    from .inversion import invert
+    from .utils.lidar import postprocess
+    from .utils.metrics.depth import depth_metrics
+    from .utils.metrics.distance import compute_cd
+    xyz, depth, mask = item["xyz"], item["depth"], item["mask"].float()
+    inv = lidar.invert_depth(depth)
+    inv_ref = mask * inv + (1 - mask) * 0.0   # preprocess_reals (:63-69)
+    res = invert(G, inv_ref, mask, num_step=args.num_step, distance=args.distance)
+    out = postprocess(res["out"], lidar, tol=args.tol)
+    cd = compute_cd(flatten(xyz.float()), flatten(out["points"]))
+    if "dusty" in arch:
+        keep, keep_is_depth = out["mask"], False
+    else:
+        keep, keep_is_depth = out["depth"], True
+    m = depth_metrics(inv_ref, res["inv_gen"], mask, lidar.min_depth, lidar.max_depth, keep=keep,
+                      keep_is_depth=keep_is_depth, tol=args.tol)
+    B = inv_ref.shape[0]
+    cols = {"cd": cd.tolist(), "tol": [args.tol] * B}
+    for k in COLUMNS:
+        if k not in cols:
+            cols[k] = m[k].tolist()
+    return cols
+
+
+def write_csv(path, results):
+    """pandas.DataFrame(results).to_csv(path)'s layout: an unnamed index column, then the columns in order"""
+    n = len(results[COLUMNS[0]])
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow([""] + COLUMNS)
+        for i in range(n):
+            w.writerow([i] + [repr(float(results[k][i])) for k in COLUMNS])
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from . import utils
+    from .datasets import ScanLoader, define_dataset
+    cfg, G, lidar, device = utils.setup(args.model_path, args.config_path, ema=True, fix_noise=True)
+    utils.set_requires_grad(G, False)
+    dataset = define_dataset(cfg.dataset, phase="test")
+    loader = ScanLoader(dataset, args.batch_size, device, shuffle=False, drop_last=False, want_xyz=True,
+                        num_workers=min(4, int(getattr(cfg, "num_workers", 4) or 1)))
+    results = {k: [] for k in COLUMNS}
+    for item in loader:
+        for k, v in evaluate_batch(G, lidar, str(cfg.model.gen.arch), item, args).items():
+            results[k] += v
+    os.makedirs(args.save_dir_path, exist_ok=True)
+    save_path = osp.join(args.save_dir_path, f"{datetime.datetime.now().isoformat()}.csv")
+    write_csv(save_path, results)
+    print(f"Saved: {save_path}")
+    return save_path
+
+
+if __name__ == "__main__":
+    main()

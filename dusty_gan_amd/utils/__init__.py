@@ -1,5 +1,5 @@
 """Host-side helpers mirrored from the reference's utils/__init__.py (only the four on the hot path,
-SURVEY.md §2) plus the engine's Philox stream."""
+SURVEY.md §2, and masked_loss of the reconstruction evaluation) plus the engine's Philox stream."""
 
 
 def set_requires_grad(net, requires_grad: bool = True):
@@ -61,3 +61,27 @@ def setup(model_path, config_path, ema=True, fix_noise=True, cuda=True):
         lidar.use_nominal_angles()
     lidar.to(device)
     return cfg, G, lidar, device
+
+
+def masked_loss(img_ref, img_gen, mask, distance="l1"):
+    """reference: utils/__init__.py:237-246 -> per-sample [B] sum(|ref - gen| or (ref - gen)^2) mask / sum(mask) for
+    [B,1,H,W] images, on the kernel GAN inversion uses (csrc/inversion.hip dg_inv_loss_grad, forward only)"""
+    import torch
+
+    from .. import _lib as L
+    if distance not in ("l1", "l2"):
+        raise NotImplementedError
+    if not img_gen.is_cuda:
+        raise RuntimeError("masked_loss runs on the GPU only (no CPU fallback)")
+    ref, gen, m = (t.contiguous().float() for t in (img_ref, img_gen, mask))
+    assert ref.shape == gen.shape == m.shape and ref.ndim == 4 and ref.shape[1] == 1
+    B, HW = ref.shape[0], ref.shape[2] * ref.shape[3]
+    msum = m.sum(dim=(1, 2, 3)).contiguous()
+    nchunk = max(1, min(16, HW // 1024))
+    parts = torch.zeros(B * nchunk, dtype=torch.float32, device=gen.device)
+    tickets = torch.zeros(B, dtype=torch.int32, device=gen.device)
+    loss = torch.empty(B, dtype=torch.float32, device=gen.device)
+    L.check(L.lib().dg_inv_loss_grad(L.ptr(gen), HW, 0, L.ptr(ref), L.ptr(m), L.ptr(msum), int(distance == "l2"), B, HW,
+                                     1.0, None, 1, None, 1, L.ptr(parts), L.ptr(tickets), nchunk, L.ptr(loss),
+                                     L.stream_ptr()), "dg_inv_loss_grad")
+    return loss

@@ -101,6 +101,19 @@ class LiDAR:
                                        pol.numel(), L.ptr(out), L.stream_ptr()), "dg_fetch_reals")
         return out, mask
 
+    def invert_depth(self, norm_depth):
+        """utils/lidar.py:31-36: normalised depth -> normalised inverse depth (the reference's own torch expression; the
+        reconstruction evaluation prepares its targets with it once per batch)"""
+        depth = norm_depth * (self.max_depth - self.min_depth) + self.min_depth
+        return (1 / depth - 1 / self.max_depth) / (1 / self.min_depth - 1 / self.max_depth)
+
+    def revert_depth(self, x, norm=True):
+        """utils/lidar.py:38-47: normalised inverse depth -> depth (metres), or normalised depth with norm=True (the
+        reference's own torch expression; the metrics kernel, dg_depth_metrics, fuses it)"""
+        disp = x * (1 / self.min_depth - 1 / self.max_depth) + 1 / self.max_depth
+        depth = 1 / disp
+        return (depth - self.min_depth) / (self.max_depth - self.min_depth) if norm else depth
+
     def inv_to_xyz(self, inv_depth, tol=1e-8, from_tanh=False, return_depth=False):
         """utils/lidar.py:58-65.  inv_depth [B,1,H,W] in [0,1] (or the generator's [-1,1] output with from_tanh=True,
         which applies utils/__init__.py:168 first) -> points [B,3,H,W] in unit space (metres / max_depth)."""

@@ -30,6 +30,21 @@ def chamfer_distance_matrix(pcs_1, pcs_2):
     return chamfer_dir(pcs_1, pcs_2) + chamfer_dir(pcs_2, pcs_1).t()
 
 
+def chamfer_paired(pcs_1, pcs_2):
+    """L[i] = mean_{p in pcs_1[i]} min_{q in pcs_2[i]} |p - q|^2 -> [B] (the diagonal of chamfer_dir, one launch)"""
+    a, b = _prep(pcs_1), _prep(pcs_2)
+    assert a.size(0) == b.size(0)
+    out = torch.empty(a.size(0), dtype=torch.float32, device=a.device)
+    L.check(L.lib().dg_chamfer_paired(L.ptr(a), a.size(1), L.ptr(b), b.size(1), a.size(0), L.ptr(out), L.stream_ptr()),
+            "dg_chamfer_paired")
+    return out
+
+
+def compute_cd(pcs_1, pcs_2):
+    """compute_cd (utils/metrics/cov_mmd_1nna.py:19-21) of paired sets: cloud i against cloud i -> [B]"""
+    return chamfer_paired(pcs_1, pcs_2) + chamfer_paired(pcs_2, pcs_1)
+
+
 def earth_mover_distance(xyz1, xyz2):
     """cost[b] of the approximate matching between xyz1[b] and xyz2[b] (reference: utils/metrics/distance/emd/,
     EarthMoverDistanceFunction.forward): approxmatch + matchcost in one kernel (csrc/metrics.hip emd_kernel)"""

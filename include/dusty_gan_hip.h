@@ -434,6 +434,12 @@ int dg_normals(const float* points, int B, int H, int W, int d, float* out, void
  * accumulate.  dg_jsd: _jensen_shannon_divergence :96-107 of two counter vectors -> out[0]. */
 int dg_fps(const float* xyz, int B, int n, int m, float* temp, int* idx, float* out, void* stream);
 int dg_chamfer_dir(const float* A, int Na, int n, const float* Bc, int Nb, int m, float* L, void* stream);
+/* dg_chamfer_paired: the same directed means for B PAIRS of clouds, L[i] = mean_{p in A_i} min_{q in B_i} |p - q|^2 for
+ * A [B,n,3], B [B,m,3] -> L [B] (the diagonal of dg_chamfer_dir's matrix: the same per-wave sums; above 1024 points the
+ * 512-point slices of a cloud are added with float atomics in arrival order, as in dg_chamfer_dir, so the result is not
+ * bit-reproducible run to run there); compute_cd of
+ * utils/metrics/cov_mmd_1nna.py:19-21 on paired sets = L_AB + L_BA (evaluate_reconstruction.py:126). */
+int dg_chamfer_paired(const float* A, int n, const float* Bc, int m, int B, float* L, void* stream);
 /* dg_emd: approximate earth mover's distance  utils/metrics/distance/emd/earth_mover_distance.cu (approxmatch :28-190
  * + matchcost :218-262 fused; the [m,n] match matrix is never stored).  paired = 1: out[i] = emd(A_i, B_i) (Na == Nb,
  * the extension's semantics); paired = 0: out [Na,Nb] for all pairs.  The value is the raw cost (compute_emd of
@@ -609,6 +615,43 @@ int dg_adam_fused(float* p, float* grad, float* v, float* ema, void* shadow, int
 int dg_adam_proj_fused(float* p, float* v, float* ema, void* shadow, int shadow_dtype, const void* dp0, const void* zT,
                        int op_dtype, int nb, long Np, int K, float wscale, float gscale, float lr, float beta2,
                        float eps, const unsigned long long* step_dev, float ema_decay, void* stream);
+
+/* ---- GAN inversion  evaluate_reconstruction.py:32-164 with utils/__init__.py:224-246 ------------------------------------
+ * dg_inv_loss_grad: masked_loss (utils/__init__.py:237-246) of the reference inverse depth `ref` [B,HW] against the generated
+ * one - gen [B,*] with sample stride gen_sb: tanh_to_sigmoid of it (from_tanh = 1: the head output's tanh'd depth channel,
+ * gout [B,nheads,HW]) or the image itself - under `mask` [B,HW]: loss[b] = sum(|ref - gen| or (ref - gen)^2) mask / msum[b]
+ * (distance 0 = l1, 1 = l2; msum[b] = sum of the sample's mask, 0 gives NaN as in the reference).  With draw / draw_pm the
+ * same launch writes d loss_b / d (head depth pre-activation) * s_depth (the head's EqualLR scale) where dg_head_post_bwd
+ * writes its head gradient - draw [B,nheads,HW] planar fp32 and / or draw_pm [B,HW,cp] pixel-major bf16 - confidence
+ * channels zero; l1 takes sign(gen - ref) with sign(0) = 0.  Per-sample sums in a fixed order: nchunk > 1 workgroups per
+ * sample store their partials in parts [B*nchunk] and draw tickets [B] (zero on entry, left zero); the last one adds the
+ * partials in chunk order.
+ * dg_sphere_adam: one step of SphericalOptimizer (utils/__init__.py:224-234: torch.optim.Adam, then every latent row / sqrt(
+ * mean(row^2) + 1e-9)) on latent [B,nz] fp32 with moments m, v [B,nz] and gradient grad(b, j) = grad[b g_sb + j g_sk], at
+ * step index k = *step_dev (device memory: a replayed hipGraph advances it), Adam step count k + 1.  sched [num_step + 1][3]
+ * holds per step k (fp32, formed as torch's Adam forms them): the step size lr lambda(k) / (1 - beta1^(k+1)) with the LambdaLR schedule of
+ * evaluate_reconstruction.py:72-77 (lambda(0) = 0), sqrt(1 - beta2^(k+1)), and the perturbation strength 0.05 noise_sigma
+ * max(0, 1 - k/num_step/noise_ratio)^2 (:100-104); index k > num_step reads row num_step.  The same launch writes the
+ * generator input of step k + 1, latent + strength(k + 1) randn (perturb = 0: the latent alone), into zT [B,nz] of
+ * z_dtype (DG_F32 / DG_BF16) - randn from Philox (seed, counter (k' ceil(nz/4) + j/4, stream_id | b << 32)), Box-Muller on
+ * word pairs as dg_philox_fill kind 1 - or noise_in [B,nz] when given (the perturbation itself, injected).  The last
+ * row's workgroup increments *step_dev (ticket [1]: zero on entry, left zero).
+ * prime = 1: no optimiser step, only zT for step *step_dev (the first forward).  nz <= 1024.
+ * dg_depth_metrics: compute_depth_error + compute_depth_accuracy (utils/metrics/depth.py) of revert_depth(inv, norm=False)
+ * (utils/lidar.py:38-47) of inv_ref / inv_gen [B,HW] under mask [B,HW], and the drop ratios of the evaluation CSV
+ * (evaluate_reconstruction.py:138-152): out [B,9] = abs_rel, sq_rel, rmse, rmse_log, accuracy_1..3, drop_gen, drop_ref.
+ * drop_gen = sum(1 - keep) / HW over keep [B,kc,HW] (the dusty masks), or with keep_is_depth over |keep| > tol of the
+ * depth image keep [B,1,HW].  max_depth <= 0: inv_ref / inv_gen are depths already (no revert_depth).  One workgroup per
+ * sample; a zero mask sum gives NaN as in the reference. */
+int dg_inv_loss_grad(const float* gen, long gen_sb, int from_tanh, const float* ref, const float* mask, const float* msum,
+                     int distance, int B, long HW, float s_depth, float* draw, int nheads, void* draw_pm, int cp,
+                     float* parts, unsigned* tickets, int nchunk, float* loss, void* stream);
+int dg_sphere_adam(const float* grad, long g_sb, long g_sk, float* latent, float* m, float* v, unsigned long long* step_dev,
+                   unsigned* ticket, const float* noise_in, void* zT, int z_dtype, int B, int nz, const float* sched,
+                   int num_step, float beta1, float beta2, float eps, int perturb, uint64_t seed, uint64_t stream_id, int prime,
+                   void* stream);
+int dg_depth_metrics(const float* inv_ref, const float* inv_gen, const float* mask, const float* keep, int kc,
+                     int keep_is_depth, float tol, int B, long HW, float min_depth, float max_depth, float* out, void* stream);
 
 const char* dg_version(void);
 
