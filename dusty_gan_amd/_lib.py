@@ -19,7 +19,13 @@ DG_F32, DG_BF16 = 0, 1
 DG_BF16X2 = 2   # split-bf16 pairs (hi | lo per 64 channels), 4 bytes per element: include/dusty_gan_hip.h
 MODE_S2, MODE_UP, MODE_GEMM = 0, 1, 2
 EPI_LINEAR, EPI_LRELU, EPI_MASK = 0, 1, 2
-DG_FORCE_FP32X3 = 0x100   # flag bit of the `force` arguments (include/dusty_gan_hip.h)
+# include/dusty_gan_hip.h: the request codes of `force` (| DG_FORCE_FP32X3), then what ran (DgConvPlan.family, DgWgradPlan.variant)
+DG_FORCE_AUTO, DG_FORCE_DIRECT, DG_FORCE_MFMA, DG_FORCE_THIN, DG_FORCE_LOCKSTEP, DG_FORCE_PINGPONG = 0, 1, 2, 3, 4, 5
+DG_FORCE_WG_REGSTAGED, DG_FORCE_WG_DMA_PAIRS, DG_FORCE_WG_DMA_NOPAIRS, DG_FORCE_PINGPONG_SINGLE, DG_FORCE_PROJ_STREAM = 6, 7, 8, 9, 10
+DG_FORCE_FP32X3 = 0x100
+DG_CONV_FAMILY_DIRECT, DG_CONV_FAMILY_MFMA, DG_CONV_FAMILY_THIN, DG_CONV_FAMILY_LOCKSTEP, DG_CONV_FAMILY_PINGPONG = 1, 2, 3, 4, 5
+DG_CONV_FAMILY_PROJ_STREAM = 6
+DG_WGRAD_VARIANT_DIRECT, DG_WGRAD_VARIANT_MFMA, DG_WGRAD_VARIANT_THIN, DG_WGRAD_VARIANT_DMA, DG_WGRAD_VARIANT_THIN_MFMA = 1, 2, 3, 5, 7
 POLICY_BITS = {"brightness": 1, "saturation": 2, "contrast": 4, "translation": 8, "cutout": 16}
 
 _ERR = {1: "DG_EINVAL (bad argument)", 2: "DG_EUNSUPPORTED (shape not supported by the requested kernel)",
@@ -128,14 +134,12 @@ PROTOTYPES = {
     "dg_conv_ex": [C.POINTER(DgConv), _I, _I, _P],
     "dg_conv_plan": [C.POINTER(DgConv), _I, _I, C.POINTER(DgConvPlan)],
     "dg_conv_mfma_supported": [C.POINTER(DgConv)],
-    "dg_conv_kernel_choice": [C.POINTER(DgConv)],
     "dg_wgrad": [C.POINTER(DgWgrad), _I, _I, _P],
     "dg_wgrad_plan": [C.POINTER(DgWgrad), _I, _I, C.POINTER(DgWgradPlan)],
     "dg_wgrad_group": [C.POINTER(DgWgrad), _I, _I, _I, _P],
     "dg_wgrad_group_plan": [C.POINTER(DgWgrad), _I, _I, _I, C.POINTER(DgWgradPlan)],
     "dg_wgrad_reduce": [C.POINTER(DgWgradReduce), _I, _P],
     "dg_wgrad_mfma_supported": [C.POINTER(DgWgrad)],
-    "dg_wgrad_kernel_choice": [C.POINTER(DgWgrad)],
     "dg_wgrad_kernel_variant": [C.POINTER(DgWgrad), _I],
     "dg_wgrad_has_sample_map": [C.POINTER(DgWgrad), _I],
     "dg_blur_fwd": [_P, _P, _I, _I, _I, _I, _I, _P],

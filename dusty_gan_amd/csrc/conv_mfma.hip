@@ -359,7 +359,7 @@ static int launch_cfg(const ConvP* p, hipStream_t stream, DgConvPlan* plan) {
   const long nwg = tiles_m * tiles_n;
   if (nwg <= 0 || nwg > 0x7fffffffL) return DG_EINVAL;
   if (plan) {
-    plan->family = 2; plan->bm = BM; plan->bn = BN; plan->tiles = (int)nwg; plan->workgroups = (int)nwg;
+    plan->family = DG_CONV_FAMILY_MFMA; plan->bm = BM; plan->bn = BN; plan->tiles = (int)nwg; plan->workgroups = (int)nwg;
     plan->tiles_per_wg = 1;
     return DG_OK;
   }
@@ -369,9 +369,20 @@ static int launch_cfg(const ConvP* p, hipStream_t stream, DgConvPlan* plan) {
   return DG_OK;
 }
 
-// Shapes this kernel takes; everything else goes to the thin / direct kernels (dg_conv in api.hip decides).
+// the largest tiles the layer's width and channel count divide into
+template <typename T, bool X3 = false>
+static int launch_tiles(const ConvP* p, hipStream_t stream, DgConvPlan* plan) {
+  const bool m128 = p->mode == MODE_GEMM ? false : (p->Wc % 128 == 0);
+  const bool n128 = p->N % 128 == 0;
+  if (m128 && n128) return launch_cfg<T, 128, 128, X3>(p, stream, plan);
+  if (m128) return launch_cfg<T, 128, 64, X3>(p, stream, plan);
+  if (n128) return launch_cfg<T, 64, 128, X3>(p, stream, plan);
+  return launch_cfg<T, 64, 64, X3>(p, stream, plan);
+}
+
 int dg_conv_mfma_pp_launch(const ConvP* p, hipStream_t stream, int min_tiles, int wg_cap, DgConvPlan* plan, int dual);
 
+// Shapes this kernel takes; everything else goes to the thin / direct kernels (select_conv in api.hip decides).
 extern "C" int dg_conv_mfma_supported(const ConvP* p) {
   if (p->in_dtype == DG_BF16X2 || p->out_dtype == DG_BF16X2 || p->w_dtype == DG_BF16X2) {
     // split-bf16 pairs: the ping-pong kernel or nothing (its launcher describes the launch without making it)
@@ -393,14 +404,22 @@ extern "C" int dg_conv_mfma_supported(const ConvP* p) {
 int dg_conv_mfma_persist_launch_bf16(const ConvP* p, hipStream_t stream, int auto_rule, int wg_cap, DgConvPlan* plan);
 int dg_conv_mfma_persist_launch_f32(const ConvP* p, hipStream_t stream, int auto_rule, int wg_cap, DgConvPlan* plan);
 
-int dg_conv_mfma_pp_launch(const ConvP* p, hipStream_t stream, int min_tiles, int wg_cap, DgConvPlan* plan, int dual);
-
-// plan != NULL: fill it with what would be launched and launch nothing.
-// Auto rule: bf16 layers with >= 256 tiles of 256 pixels -> ping-pong persistent kernel (conv_mfma_pp.hip, family 5);
-// layers the lock-step persistent kernel tiles with every CU busy -> that one (conv_mfma_persist_impl.h, family 4: fp32,
-// 128 x 128 tiles); everything else -> one tile per workgroup (below, family 2).
-int dg_conv_mfma_launch(const ConvP* p, hipStream_t stream, int wg_cap, DgConvPlan* plan, int fp32x3) {
+// The MFMA family of dg_conv; plan != NULL: fill it with what would be launched and launch nothing.
+// force DG_FORCE_LOCKSTEP / _PINGPONG / _PINGPONG_SINGLE: that persistent large-tile kernel wherever its geometry allows, else
+// DG_EUNSUPPORTED (parity tests of either family on small problems).  DG_FORCE_AUTO / _MFMA, the auto rule: bf16 layers with
+// >= 256 tiles of 256 pixels -> ping-pong persistent kernel (conv_mfma_pp.hip, DG_CONV_FAMILY_PINGPONG); layers the lock-step
+// persistent kernel tiles with every CU busy -> that one (conv_mfma_persist_impl.h, DG_CONV_FAMILY_LOCKSTEP: fp32,
+// 128 x 128 tiles); everything else -> one tile per workgroup (above, DG_CONV_FAMILY_MFMA).
+int dg_conv_mfma_launch(const ConvP* p, hipStream_t stream, int force, int fp32x3, int wg_cap, DgConvPlan* plan) {
   if (!dg_conv_mfma_supported(p)) return DG_EUNSUPPORTED;
+  if (force == DG_FORCE_PINGPONG || force == DG_FORCE_PINGPONG_SINGLE)
+    return (p->in_dtype == DG_BF16 || p->in_dtype == DG_BF16X2)
+               ? dg_conv_mfma_pp_launch(p, stream, 1, wg_cap, plan, force == DG_FORCE_PINGPONG) : DG_EUNSUPPORTED;
+  if (force == DG_FORCE_LOCKSTEP) {
+    if (p->in_dtype == DG_BF16X2) return DG_EUNSUPPORTED;
+    return p->in_dtype == DG_BF16 ? dg_conv_mfma_persist_launch_bf16(p, stream, 0, wg_cap, plan)
+                                  : dg_conv_mfma_persist_launch_f32(p, stream, 0, wg_cap, plan);
+  }
   if (p->in_dtype == DG_BF16X2) return dg_conv_mfma_pp_launch(p, stream, 1, wg_cap, plan, 1);
   if (p->in_dtype == DG_BF16) {
     const int rc = dg_conv_mfma_pp_launch(p, stream, 256, wg_cap, plan, 1);
@@ -412,34 +431,6 @@ int dg_conv_mfma_launch(const ConvP* p, hipStream_t stream, int wg_cap, DgConvPl
                                           : dg_conv_mfma_persist_launch_f32(p, stream, 1, wg_cap, plan);
     if (rc != DG_EUNSUPPORTED) return rc;
   }
-  const bool m128 = p->mode == MODE_GEMM ? false : (p->Wc % 128 == 0);
-  const bool n128 = p->N % 128 == 0;
-  if (x3) {
-    if (m128 && n128) return launch_cfg<float, 128, 128, true>(p, stream, plan);
-    if (m128) return launch_cfg<float, 128, 64, true>(p, stream, plan);
-    if (n128) return launch_cfg<float, 64, 128, true>(p, stream, plan);
-    return launch_cfg<float, 64, 64, true>(p, stream, plan);
-  }
-  if (p->in_dtype == DG_BF16) {
-    if (m128 && n128) return launch_cfg<bf16, 128, 128>(p, stream, plan);
-    if (m128) return launch_cfg<bf16, 128, 64>(p, stream, plan);
-    if (n128) return launch_cfg<bf16, 64, 128>(p, stream, plan);
-    return launch_cfg<bf16, 64, 64>(p, stream, plan);
-  }
-  if (m128 && n128) return launch_cfg<float, 128, 128>(p, stream, plan);
-  if (m128) return launch_cfg<float, 128, 64>(p, stream, plan);
-  if (n128) return launch_cfg<float, 64, 128>(p, stream, plan);
-  return launch_cfg<float, 64, 64>(p, stream, plan);
-}
-
-// a persistent large-tile kernel wherever its geometry allows, else DG_EUNSUPPORTED (parity tests of either family on
-// small problems): dg_conv force == 4 -> the lock-step kernel, force == 5 -> the ping-pong kernel
-int dg_conv_mfma_big_launch(const ConvP* p, hipStream_t stream, int family, int wg_cap, DgConvPlan* plan) {
-  if (!dg_conv_mfma_supported(p)) return DG_EUNSUPPORTED;
-  if (family == 5 || family == 9)   // 9: the ping-pong kernel without its both-parities tile (A/B, parity tests)
-    return (p->in_dtype == DG_BF16 || p->in_dtype == DG_BF16X2) ? dg_conv_mfma_pp_launch(p, stream, 1, wg_cap, plan, family == 5)
-                                                               : DG_EUNSUPPORTED;
-  if (p->in_dtype == DG_BF16X2) return DG_EUNSUPPORTED;
-  return p->in_dtype == DG_BF16 ? dg_conv_mfma_persist_launch_bf16(p, stream, 0, wg_cap, plan)
-                                : dg_conv_mfma_persist_launch_f32(p, stream, 0, wg_cap, plan);
+  if (x3) return launch_tiles<float, true>(p, stream, plan);
+  return p->in_dtype == DG_BF16 ? launch_tiles<bf16>(p, stream, plan) : launch_tiles<float>(p, stream, plan);
 }

@@ -505,7 +505,7 @@ int launch(const ConvP* p, const Geo& g0, hipStream_t stream, int wg_cap, DgConv
   const int cap = (wg_cap > 0 && wg_cap < resident) ? wg_cap : resident;
   const int G = g.ntiles < cap ? g.ntiles : cap;
   if (plan) {
-    plan->family = 4; plan->bm = BM; plan->bn = BN; plan->tiles = g.ntiles; plan->workgroups = G;
+    plan->family = DG_CONV_FAMILY_LOCKSTEP; plan->bm = BM; plan->bn = BN; plan->tiles = g.ntiles; plan->workgroups = G;
     plan->tiles_per_wg = (g.ntiles + G - 1) / G;
     plan->dbias_rows = (sizeof(T) == 4 && p->bias_mod == p->N) ? G : 0;   // fp32: one partial row per workgroup (DgConv.dbias_part)
     return DG_OK;

@@ -764,7 +764,7 @@ int launch(const ConvP* p, const Geo& g0, hipStream_t stream, int wg_cap, DgConv
   const int cap = (wg_cap > 0 && wg_cap < resident) ? wg_cap : resident;
   const int G = g.ntiles < cap ? g.ntiles : cap;
   if (plan) {
-    plan->family = 5; plan->bm = DUAL ? 512 : 256; plan->bn = DUAL ? BN / 2 : BN; plan->tiles = g.ntiles; plan->workgroups = G;
+    plan->family = DG_CONV_FAMILY_PINGPONG; plan->bm = DUAL ? 512 : 256; plan->bn = DUAL ? BN / 2 : BN; plan->tiles = g.ntiles; plan->workgroups = G;
     plan->tiles_per_wg = (g.ntiles + G - 1) / G;
     plan->mask_bits = MASK ? (bits ? 2 : 0) : 1;
     // (per-wave bias-gradient rows need DBW * N floats of the kernel's LDS rows: 2048)

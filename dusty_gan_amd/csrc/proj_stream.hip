@@ -157,7 +157,7 @@ int dg_proj_stream_launch(const ConvP* p, hipStream_t stream, DgConvPlan* plan) 
   int G = cus;                                   // 128 KB of LDS: one workgroup per CU
   if ((long)G * PS_WAVES > tiles) G = (tiles + PS_WAVES - 1) / PS_WAVES;
   if (plan) {
-    plan->family = 6; plan->bm = 16 * ((p->B + 15) / 16); plan->bn = PS_ROWS; plan->tiles = tiles; plan->workgroups = G;
+    plan->family = DG_CONV_FAMILY_PROJ_STREAM; plan->bm = 16 * ((p->B + 15) / 16); plan->bn = PS_ROWS; plan->tiles = tiles; plan->workgroups = G;
     plan->tiles_per_wg = (tiles + G - 1) / G;
     return DG_OK;
   }

@@ -572,7 +572,7 @@ int dg_wgrad_mfma_dma_group_launch(const WgradP* items, int n, int pairs, int ro
     const DmaGeo ge = bm == 128 ? (bn == 128 ? dma_geo<128, 128>(p, 1, pairs, true, target) : dma_geo<128, 64>(p, 1, pairs, true, target))
                                 : (bn == 128 ? dma_geo<64, 128>(p, 1, pairs, true, target) : dma_geo<64, 64>(p, 1, pairs, true, target));
     if (plans) {
-      plans[i].variant = 5;
+      plans[i].variant = DG_WGRAD_VARIANT_DMA;
       plans[i].splits = (int)ge.split;
       plans[i].ws_floats = ge.split * 16L * p->Ci * p->Co;
       plans[i].tap_pairs = ge.use_pairs ? 1 : 0;

@@ -585,8 +585,9 @@ class Ops:
         self.x3 = bool(x3) and dtype == torch.float32
         self.dt = L.dtype_code(dtype)
         self.es = 2 if dtype == torch.bfloat16 else 4
-        # dg_conv / dg_wgrad `force` (0 auto; the parity tests set 1 direct, 2 MFMA, 3 thin, 4 / 5 persistent kernels)
-        self.force = 0
+        # dg_conv / dg_wgrad `force`: a request code L.DG_FORCE_* (AUTO; the parity tests pin DIRECT, MFMA, THIN, the persistent
+        # LOCKSTEP / PINGPONG[_SINGLE] convs, PROJ_STREAM, the WG_* weight-gradient kernels)
+        self.force = L.DG_FORCE_AUTO
         self.wg_cap = Ops.default_wg_cap  # dg_conv_ex: cap on the persistent conv's workgroup count (0 = one residency wave)
         self.use_ws = True  # split-K partials through WGRAD_WS + dg_wgrad_reduce (False: fp32 atomics onto dW)
         self._group = None  # the open `grouped()` block's launches
@@ -602,7 +603,7 @@ class Ops:
 
     @property
     def _f(self):
-        """the `force` argument of the C ABI: kernel-family code | flag bits"""
+        """the `force` argument of the C ABI: request code | flag bits"""
         return self.force | (L.DG_FORCE_FP32X3 if self.x3 else 0)
 
     def conv(self, mode, adj, ring, B, Hc, Wc, K, N, x, x_strides, out, out_strides, w_ptr, scale, epi,
@@ -694,20 +695,20 @@ class Ops:
                 x2_pack(out, x2_out, out_off, B * N)
             return sum_parts
         # bench.py's instrumented pass: HIP events on the launch stream around this one kernel
-        choice = self.lib.dg_conv_kernel_choice(C.byref(p)) if self.force == 0 else self.force
+        pl = L.DgConvPlan()
+        L.check(self.lib.dg_conv_plan(C.byref(p), self._f, self.wg_cap, C.byref(pl)), "dg_conv_plan")
+        name = {L.DG_CONV_FAMILY_THIN: "conv_thin_kernel", L.DG_CONV_FAMILY_DIRECT: "conv_direct_kernel"}.get(pl.family,
+                                                                                                             "conv_mfma_kernel")
         wes = 2 if p.w_dtype == L.DG_BF16 else 4
         mb = 0
         if p.mask_out or p.mask_in:
-            pl = L.DgConvPlan()
-            L.check(self.lib.dg_conv_plan(C.byref(p), self._f, self.wg_cap, C.byref(pl)), "dg_conv_plan")
             mb = pl.mask_bits if p.mask_in else 1  # (mask_out behind a kernel without it: the packing launch writes the same bytes)
         flops, nbytes = conv_algorithmic(mode, B, Hc, Wc, K, N, ies, oes, wes, epi == L.EPI_MASK, mb)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         L.check(self.lib.dg_conv_ex(C.byref(p), self._f, self.wg_cap, L.stream_ptr()), "dg_conv_ex")
         e1.record()
-        PROFILE.append(({2: "conv_mfma_kernel", 3: "conv_thin_kernel"}.get(choice, "conv_direct_kernel"), flops, nbytes, e0, e1,
-                        f"mode{mode}adj{adj} B{B} {Hc}x{Wc} K{K} N{N}"))
+        PROFILE.append((name, flops, nbytes, e0, e1, f"mode{mode}adj{adj} B{B} {Hc}x{Wc} K{K} N{N}"))
         self._db_rows_done(p, db_rows, dbias, N, defer_db)
         if x2_out is not None:
             x2_pack(out, x2_out, out_off, B * N)
@@ -733,7 +734,7 @@ class Ops:
         p = self._wgrad_params(wmode, ring, B, Hc, Wc, Ci, Co, a, a_strides, g, g_strides, dw_ptr, scale, rowscale, a_dt,
                                g_dt, a_off, g_off, g_mod)
         pl = self.wgrad_plan(p, accumulate) if self.use_ws else None
-        if (self._group is not None and defer and pl is not None and pl.ws_floats > 0 and pl.variant == 5
+        if (self._group is not None and defer and pl is not None and pl.ws_floats > 0 and pl.variant == L.DG_WGRAD_VARIANT_DMA
                 and len(self._group) < self.GROUP_MAX and pl.ws_floats <= WgradWorkspace.FLOATS):
             # inside `with ops.grouped():` - the launch joins the group's ONE launch (dg_wgrad_group) at the end of the block:
             # its geometry (K split, workspace) is decided there, for the group as a whole
@@ -748,15 +749,16 @@ class Ops:
         if PROFILE is None:
             L.check(self.lib.dg_wgrad(C.byref(p), accumulate, self._f, L.stream_ptr()), "dg_wgrad")
         else:
-            choice = self.lib.dg_wgrad_kernel_choice(C.byref(p)) if self.force in (0, 7, 8) else self.force
+            v = self.lib.dg_wgrad_kernel_variant(C.byref(p), self._f)
+            name = {L.DG_WGRAD_VARIANT_THIN: "wgrad_thin_kernel", L.DG_WGRAD_VARIANT_THIN_MFMA: "wgrad_thin_kernel",
+                    L.DG_WGRAD_VARIANT_DIRECT: "wgrad_direct_kernel"}.get(v, "wgrad_mfma_kernel")
             flops, nbytes = wgrad_algorithmic(wmode, B, Hc, Wc, Ci, Co, 2 if p.a_dtype == L.DG_BF16 else 4,
                                               2 if p.g_dtype == L.DG_BF16 else 4)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             L.check(self.lib.dg_wgrad(C.byref(p), accumulate, self._f, L.stream_ptr()), "dg_wgrad")
             e1.record()
-            PROFILE.append(({2: "wgrad_mfma_kernel", 3: "wgrad_thin_kernel"}.get(choice, "wgrad_direct_kernel"), flops, nbytes,
-                            e0, e1, f"wmode{wmode} B{B} {Hc}x{Wc} Ci{Ci} Co{Co}"))
+            PROFILE.append((name, flops, nbytes, e0, e1, f"wmode{wmode} B{B} {Hc}x{Wc} Ci{Ci} Co{Co}"))
         if p.ws:
             WGRAD_WS.add(p.ws, dw_ptr, (1 if wmode == 2 else 16) * Ci * Co, pl.splits, int(accumulate))
             if not defer:
@@ -821,7 +823,7 @@ class Ops:
         descs = [f"wmode{d[0]} B{d[1]} {d[2]}x{d[3]} Ci{d[4]} Co{d[5]}" for _, d, _, _, _ in items]
         if TRACE is not None:
             for i, it in enumerate(items):
-                TRACE.append(("wgrad", 5, descs[i], plans[i].splits, plans[i].tap_pairs, True, it[0].g_mod))
+                TRACE.append(("wgrad", L.DG_WGRAD_VARIANT_DMA, descs[i], plans[i].splits, plans[i].tap_pairs, True, it[0].g_mod))
             if grouped:
                 TRACE.append(("wgrad_group", n, descs))
 

@@ -144,14 +144,22 @@ typedef struct DgWgrad {
  *   Proj.forward            models/gans/dcgan_eqlr.py:6-16
  *   their autograd backward-data passes (loss.backward() at trainers/dcgan_amp.py:235,309 and
  *   torch.autograd.grad(create_graph=True) at :218-223), and the R1 tangent pass (double backward, :229-235).
- * force: 0 = pick (MFMA implicit GEMM when the shape allows, else the thin LDS/VALU kernel for <=4-channel sides,
- * else the general direct kernel), 1 = direct, 2 = MFMA or error, 3 = thin or error, 4 / 5 = a persistent large-tile
- * MFMA kernel or error (4 the lock-step one, 5 the bf16 ping-pong one; what 0 / 2 pick for layers that fill the chip
- * with such tiles - the forced forms let parity tests run either family on small problems).
- */
+ * `force` (dg_conv* and dg_wgrad*) is a request code: a forced kernel that does not take the shape answers DG_EUNSUPPORTED
+ * (parity tests run each family on small problems); any other code runs the direct kernel (dg_wgrad_group refuses it). */
 int dg_conv(const DgConv* p, int force, void* stream);
+#define DG_FORCE_AUTO 0             /* both: pick (Proj stream -> MFMA family -> thin for <=4-channel sides -> direct)  */
+#define DG_FORCE_DIRECT 1           /* both: the general direct kernel                                               */
+#define DG_FORCE_MFMA 2             /* conv: the MFMA family's auto rule; wgrad: LDS-DMA where it fits, else REGSTAGED */
+#define DG_FORCE_THIN 3             /* both: the thin LDS/VALU or matrix-core kernels of <=4-channel sides           */
+#define DG_FORCE_LOCKSTEP 4         /* conv: the lock-step persistent large-tile MFMA kernel                         */
+#define DG_FORCE_PINGPONG 5         /* conv: the ping-pong persistent MFMA kernel (bf16 / DG_BF16X2)                  */
+#define DG_FORCE_WG_REGSTAGED 6     /* wgrad: the register-staged MFMA kernel                                        */
+#define DG_FORCE_WG_DMA_PAIRS 7     /* wgrad: the LDS-DMA kernel with W-tap pairs                                    */
+#define DG_FORCE_WG_DMA_NOPAIRS 8   /* wgrad: the LDS-DMA kernel without W-tap pairs                                 */
+#define DG_FORCE_PINGPONG_SINGLE 9  /* conv: the ping-pong kernel without its both-parities tile (64-channel MODE_UP) */
+#define DG_FORCE_PROJ_STREAM 10     /* conv: the weight-streaming Proj forward                                       */
 /* "fp32x3" (precision contract: fp32 storage with fp32 or split-bf16 x 3 MFMA): a flag bit in the
- * `force` argument of dg_conv / dg_conv_ex / dg_conv_plan / dg_wgrad / dg_wgrad_plan, OR-ed onto the kernel-family code, for
+ * `force` argument of dg_conv / dg_conv_ex / dg_conv_plan / dg_wgrad / dg_wgrad_plan, OR-ed onto the request code, for
  * DG_F32 operands on the matrix-core kernels.  Clear (default): exact fp32 products (v_mfma_f32_32x32x2_f32, 1/16 of the bf16
  * rate); set: every operand is split into bf16 hi + lo in registers and a product is a_hi b_hi + a_lo b_hi + a_hi b_lo on
  * the bf16 matrix instructions with fp32 accumulation (relative error ~2^-16 per product; the mode autocast-free fp32
@@ -159,18 +167,22 @@ int dg_conv(const DgConv* p, int force, void* stream);
  * different precision in one process do not share a setting. */
 #define DG_FORCE_FP32X3 0x100
 /* What a dg_conv call launches (introspection for the parity tests and the benchmark: which kernel family / tile ran,
- * and how many tiles each persistent workgroup walks).  family: 1 direct, 2 one-tile-per-workgroup MFMA, 3 thin,
- * 4 persistent large-tile MFMA (lock step: fp32, small layers), 5 persistent ping-pong MFMA (bf16 fat layers),
- * 6 weight-streaming Proj forward (bf16 DG_MODE_GEMM with K = 512, B <= 32; dg_conv force 10 asks for it).  dg_conv_ex = dg_conv with a cap on the persistent kernel's workgroup count
- * (wg_cap <= 0: one residency wave of the device); dg_conv_plan fills `plan` for the same arguments and launches
- * nothing. */
+ * and how many tiles each persistent workgroup walks): DgConvPlan.family is one of */
+#define DG_CONV_FAMILY_DIRECT 1       /* the direct kernel                                                   */
+#define DG_CONV_FAMILY_MFMA 2         /* one-tile-per-workgroup MFMA                                         */
+#define DG_CONV_FAMILY_THIN 3         /* thin (DgConvPlan.thin_mfma: which one)                              */
+#define DG_CONV_FAMILY_LOCKSTEP 4     /* persistent large-tile MFMA, lock step (fp32, small layers)          */
+#define DG_CONV_FAMILY_PINGPONG 5     /* persistent ping-pong MFMA (bf16 fat layers)                         */
+#define DG_CONV_FAMILY_PROJ_STREAM 6  /* weight-streaming Proj forward (bf16 DG_MODE_GEMM, K = 512, B <= 32)  */
+/* dg_conv_ex = dg_conv with a cap on the persistent kernel's workgroup count (wg_cap <= 0: one residency wave of the
+ * device); dg_conv_plan fills `plan` for the same arguments and launches nothing. */
 typedef struct DgConvPlan {
-  int family;
+  int family;        /* DG_CONV_FAMILY_* */
   int bm, bn;        /* output tile (pixels x channels), 0 for the non-MFMA kernels */
   int tiles;         /* tiles of the launch */
   int workgroups;    /* grid size */
   int tiles_per_wg;  /* most tiles any workgroup walks */
-  int thin_mfma;     /* family 3: 1 = thin_s2_mfma, 2 = thin_up_mfma (matrix cores), 0 = the VALU kernels */
+  int thin_mfma;     /* DG_CONV_FAMILY_THIN: 1 = thin_s2_mfma, 2 = thin_up_mfma (matrix cores), 0 = the VALU kernels */
   int mask_bits;     /* 1: the kernel writes DgConv.mask_out itself (else a packing launch follows it), 2: it reads mask_in */
   int dbias_rows;    /* > 0: the kernel takes DgConv.dbias_part and writes this many partial rows of N floats; 0: it does not */
   int sum_parts;     /* > 0: the kernel takes DgConv.tanh_sum_parts and stores this many partial sums per sample; 0: it does not */
@@ -178,16 +190,20 @@ typedef struct DgConvPlan {
 int dg_conv_ex(const DgConv* p, int force, int wg_cap, void* stream);
 int dg_conv_plan(const DgConv* p, int force, int wg_cap, DgConvPlan* plan);
 int dg_conv_mfma_supported(const DgConv* p);
-int dg_conv_kernel_choice(const DgConv* p);   /* what force == 0 launches: 2 MFMA, 3 thin, 1 direct */
 
 /* dg_wgrad replaces the weight-gradient half of the same autograd calls.  accumulate: 1 = atomically add onto dw
  * (dw zeroed by the caller at step start: optim.zero_grad, trainers/dcgan_amp.py:177,246), 0 = overwrite. */
 int dg_wgrad(const DgWgrad* p, int accumulate, int force, void* stream);
 /* What dg_wgrad launches for these arguments, and the split-K workspace it can use: `splits` partial tiles of
- * 16 Ci Co floats (ws_floats = splits * 16 Ci Co; 0 when the kernel that runs has no workspace form).  force 7 / 8:
- * the LDS-DMA kernel with / without W-tap pairs (A/B measurements; 0 / 2 choose by the K range per workgroup). */
+ * 16 Ci Co floats (ws_floats = splits * 16 Ci Co; 0 when the kernel that runs has no workspace form).  The plan describes
+ * the kernel: dg_wgrad alone refuses a `ws` or `g_mod` that kernel does not take.  DgWgradPlan.variant is one of */
+#define DG_WGRAD_VARIANT_DIRECT 1     /* the direct kernel                                             */
+#define DG_WGRAD_VARIANT_MFMA 2       /* register-staged MFMA (the fp32 modes' fat layers, Proj)        */
+#define DG_WGRAD_VARIANT_THIN 3       /* thin (VALU)                                                    */
+#define DG_WGRAD_VARIANT_DMA 5        /* MFMA on the LDS-DMA ring (bf16 / DG_BF16X2 Down and Up layers) */
+#define DG_WGRAD_VARIANT_THIN_MFMA 7  /* thin on the matrix cores (bf16 Down1 / Head)                   */
 typedef struct DgWgradPlan {
-  int variant;      /* as dg_wgrad_kernel_variant */
+  int variant;      /* DG_WGRAD_VARIANT_*, 0 when `force` has no kernel for the shape */
   int splits;
   long ws_floats;
   int tap_pairs;    /* 1: one workgroup computes the W taps (kx, kx + 2) from one staged image */
@@ -195,7 +211,7 @@ typedef struct DgWgradPlan {
 int dg_wgrad_plan(const DgWgrad* p, int accumulate, int force, DgWgradPlan* plan);
 /* Up to 4 weight-gradient GEMMs as ONE launch (the layers of one network: independent of each other, all reading finished
  * activations and gradient chains - loss.backward() at trainers/dcgan_amp.py:235,309 produces them in one sweep too): every
- * item must run on the MFMA LDS-DMA kernel (dg_wgrad_plan: variant 5) and bring its split-K workspace `ws`, sized by
+ * item must run on the MFMA LDS-DMA kernel (dg_wgrad_plan: DG_WGRAD_VARIANT_DMA) and bring its split-K workspace `ws`, sized by
  * dg_wgrad_group_plan for the same (items, force, rounds).  One grid instead of n residency rounds: the ring fill and the
  * partial-tile stores of one layer's workgroups run under the matrix work of its neighbours'.  rounds > 0: the group as a
  * whole aims at rounds x 512 workgroups, shared among the items by their FLOPs - fewer, longer K ranges per item than a launch
@@ -214,9 +230,7 @@ typedef struct DgWgradReduce {
 } DgWgradReduce;
 int dg_wgrad_reduce(const DgWgradReduce* items, int n, void* stream);
 int dg_wgrad_mfma_supported(const DgWgrad* p);
-int dg_wgrad_kernel_choice(const DgWgrad* p);
-/* which kernel `force` launches: 5 MFMA on the LDS-DMA ring (bf16 Down/Up layers), 2 register-staged MFMA (also
- * force == 6), 7 thin on the matrix cores (bf16 Down1 / Head), 3 thin (VALU), 1 direct, 0 unsupported */
+/* which kernel `force` launches: DgWgradPlan.variant of dg_wgrad_plan (0: a refusal) */
 int dg_wgrad_kernel_variant(const DgWgrad* p, int force);
 /* 1 when the kernel `force` launches honours DgWgrad.g_mod (the LDS-DMA kernel; Down1's thin matrix-core kernel) */
 int dg_wgrad_has_sample_map(const DgWgrad* p, int force);

@@ -14,7 +14,7 @@ dtype = torch.bfloat16 if (len(sys.argv) < 2 or sys.argv[1] == "bf16") else torc
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 32
 dev = "cuda"
 o = Ops(dtype)
-o.force = 2
+o.force = L.DG_FORCE_MFMA
 torch.manual_seed(0)
 
 # (name, mode, adj, Hc, Wc, K, N, batch multiplier)
@@ -95,7 +95,8 @@ if len(sys.argv) > 3 and sys.argv[3] == "convonly":
 # gradient chain; G layers: B samples) in four forms - fp32 atomics onto dW, split-K workspace + reduce with the launcher's
 # tap-pair choice, with pairs forced, with single taps forced
 from dusty_gan_amd import engine as E
-FORMS = [("atomics", 2, False), ("ws auto", 2, True), ("ws pairs", 7, True), ("ws single", 8, True)]
+FORMS = [("atomics", L.DG_FORCE_MFMA, False), ("ws auto", L.DG_FORCE_MFMA, True), ("ws pairs", L.DG_FORCE_WG_DMA_PAIRS, True),
+         ("ws single", L.DG_FORCE_WG_DMA_NOPAIRS, True)]
 tot = {f[0]: 0.0 for f in FORMS}
 tot_fl = 0.0
 for name, wmode, Hc, Wc, Ci, Co, bm in WGRAD:

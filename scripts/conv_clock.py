@@ -20,7 +20,7 @@ from dusty_gan_amd.engine import Ops  # noqa: E402
 seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 2.0
 dev = "cuda"
 o = Ops(torch.bfloat16)
-o.force = 2
+o.force = L.DG_FORCE_MFMA
 torch.manual_seed(0)
 # the step's launches of the family, one of each geometry class (name, mode, adj, Hc, Wc, K, N, samples)
 LAYERS = [("down3 fwd 2B", L.MODE_S2, 0, 8, 128, 128, 256, 64), ("up1 fwd B", L.MODE_UP, 0, 4, 64, 512, 256, 32),

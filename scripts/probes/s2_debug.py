@@ -15,7 +15,7 @@ b = torch.randn(Co, generator=g)
 wq = w.bfloat16().float()
 y = O.down(x, wq, b, True)
 s = 1.0 / math.sqrt(Ci * 16)
-o = Ops(torch.bfloat16); o.force = 3
+o = Ops(torch.bfloat16); o.force = L.DG_FORCE_THIN
 xd = nhwc(x).to("cuda", torch.bfloat16)
 coci = w.permute(2, 3, 0, 1).contiguous().to("cuda", torch.bfloat16)
 out = torch.empty(B * Hc * Wc * Co, device="cuda", dtype=torch.bfloat16)

@@ -11,6 +11,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from dusty_gan_amd._lib import (DG_CONV_FAMILY_DIRECT, DG_CONV_FAMILY_LOCKSTEP, DG_CONV_FAMILY_MFMA, DG_FORCE_DIRECT,
+                                DG_FORCE_LOCKSTEP, DG_FORCE_MFMA, DG_FORCE_PINGPONG, DG_FORCE_PINGPONG_SINGLE,
+                                DG_FORCE_WG_DMA_NOPAIRS, DG_FORCE_WG_DMA_PAIRS, DG_FORCE_WG_REGSTAGED, DG_WGRAD_VARIANT_DIRECT,
+                                DG_WGRAD_VARIANT_MFMA)
 from oracle import dusty_oracle as O
 from tests.golden_util import load, rel_l2, sub
 
@@ -88,7 +92,7 @@ def run_conv(L, mode, adj, ring, x, wpacked_nk, N, scale, epi, dtype, force, bia
         assert torch.equal(out.view(torch.int16), out2.view(torch.int16)), "mask_in and aux give different outputs"
         if db is not None:
             from dusty_gan_amd import engine as E
-            if E.DETERMINISTIC and force in (5, 9):
+            if E.DETERMINISTIC and force in (L.DG_FORCE_PINGPONG, L.DG_FORCE_PINGPONG_SINGLE):
                 # round 5: the ping-pong conv's bias-gradient sums leave as per-workgroup rows (DgConv.dbias_part), summed in a
                 # fixed order - two launches of the same data agree bit for bit
                 assert torch.equal(db, db2), rel_l2(db.cpu(), db2.cpu())
@@ -133,29 +137,29 @@ def pack_up(w):  # ConvTranspose2d weight (Ci,Co,4,4) -> fwd [16][co][ci], bwd [
     return fwd, bwd
 
 
-CASES = [  # (Ci, Co, H, W, B, ring, dtype, force)   force 1 = direct, 2 = MFMA, 4 / 5 = lock-step / ping-pong persistent kernel
-    (6, 4, 8, 16, 2, True, torch.float32, 1),
-    (6, 4, 8, 16, 2, False, torch.float32, 1),
-    (5, 3, 4, 6, 3, True, torch.float32, 1),
-    (64, 64, 8, 64, 2, True, torch.float32, 2),
-    (64, 128, 4, 128, 2, True, torch.float32, 2),
-    (128, 64, 8, 64, 1, True, torch.bfloat16, 2),
-    (128, 128, 4, 128, 2, True, torch.bfloat16, 2),
+CASES = [  # (Ci, Co, H, W, B, ring, dtype, force)
+    (6, 4, 8, 16, 2, True, torch.float32, DG_FORCE_DIRECT),
+    (6, 4, 8, 16, 2, False, torch.float32, DG_FORCE_DIRECT),
+    (5, 3, 4, 6, 3, True, torch.float32, DG_FORCE_DIRECT),
+    (64, 64, 8, 64, 2, True, torch.float32, DG_FORCE_MFMA),
+    (64, 128, 4, 128, 2, True, torch.float32, DG_FORCE_MFMA),
+    (128, 64, 8, 64, 1, True, torch.bfloat16, DG_FORCE_MFMA),
+    (128, 128, 4, 128, 2, True, torch.bfloat16, DG_FORCE_MFMA),
     # large tiles: 256-row M tiles built from 4 / 2 / 1 samples' row segments, 256- and 128-channel N tiles
-    (128, 256, 2, 64, 4, True, torch.float32, 4),
-    (256, 128, 4, 128, 2, True, torch.bfloat16, 4),
-    (128, 128, 2, 512, 1, True, torch.bfloat16, 4),
-    (128, 256, 4, 64, 8, True, torch.bfloat16, 4),
-    (64, 128, 2, 256, 1, True, torch.bfloat16, 4),   # backward-data: 256 x 64 tiles (8 waves of 32 x 64)
+    (128, 256, 2, 64, 4, True, torch.float32, DG_FORCE_LOCKSTEP),
+    (256, 128, 4, 128, 2, True, torch.bfloat16, DG_FORCE_LOCKSTEP),
+    (128, 128, 2, 512, 1, True, torch.bfloat16, DG_FORCE_LOCKSTEP),
+    (128, 256, 4, 64, 8, True, torch.bfloat16, DG_FORCE_LOCKSTEP),
+    (64, 128, 2, 256, 1, True, torch.bfloat16, DG_FORCE_LOCKSTEP),   # backward-data: 256 x 64 tiles (8 waves of 32 x 64)
     # the ping-pong kernel (bf16; what the benchmark's fat layers run) on the same geometries
-    (256, 128, 4, 128, 2, True, torch.bfloat16, 5),
-    (128, 128, 2, 512, 1, True, torch.bfloat16, 5),
-    (128, 256, 4, 64, 8, True, torch.bfloat16, 5),
-    (64, 128, 2, 256, 1, True, torch.bfloat16, 5),   # Down backward-data: 64 channels, both-parities tile (512 px x 64)
-    (64, 128, 4, 64, 8, True, torch.bfloat16, 5),    # ... 4 sample segments of 64 + 2 columns
-    (64, 128, 2, 512, 1, True, torch.bfloat16, 5),   # ... two column tiles per row
-    (64, 128, 2, 256, 1, True, torch.bfloat16, 9),   # force 9: the single-parity 256 x 64 tile those layers ran on before
-    (512, 128, 2, 128, 2, True, torch.bfloat16, 5),  # 512 channels in the backward-data pass: four N tiles, bias-gradient rows
+    (256, 128, 4, 128, 2, True, torch.bfloat16, DG_FORCE_PINGPONG),
+    (128, 128, 2, 512, 1, True, torch.bfloat16, DG_FORCE_PINGPONG),
+    (128, 256, 4, 64, 8, True, torch.bfloat16, DG_FORCE_PINGPONG),
+    (64, 128, 2, 256, 1, True, torch.bfloat16, DG_FORCE_PINGPONG),   # Down backward-data: 64 channels, both-parities tile (512 px x 64)
+    (64, 128, 4, 64, 8, True, torch.bfloat16, DG_FORCE_PINGPONG),    # ... 4 sample segments of 64 + 2 columns
+    (64, 128, 2, 512, 1, True, torch.bfloat16, DG_FORCE_PINGPONG),   # ... two column tiles per row
+    (64, 128, 2, 256, 1, True, torch.bfloat16, DG_FORCE_PINGPONG_SINGLE),   # the single-parity 256 x 64 tile those layers ran on before
+    (512, 128, 2, 128, 2, True, torch.bfloat16, DG_FORCE_PINGPONG),  # 512 channels in the backward-data pass: four N tiles, bias-gradient rows
                                                      # of 512 floats per wave (round 5: they once overlapped the store strips)
 ]
 
@@ -197,7 +201,7 @@ def test_down_fwd_bwd_wgrad(L, Ci, Co, H, W, B, ring, dtype, force):
     # weight gradient
     from dusty_gan_amd.engine import Ops
     o = Ops(dtype)
-    o.force = 2 if force in (4, 5, 9) else force
+    o.force = L.DG_FORCE_MFMA if force in (L.DG_FORCE_LOCKSTEP, L.DG_FORCE_PINGPONG, L.DG_FORCE_PINGPONG_SINGLE) else force
     xd, ed = nhwc(x).to(DEV, dtype), nhwc(e).to(DEV, dtype)
     dw = torch.zeros(16, Ci, Co, device=DEV)
     o.wgrad(0, ring, B, H, W, Ci, Co, xd, (4 * H * W * Ci, Ci, 1), ed, (H * W * Co, Co, 1), dw.data_ptr(), s)
@@ -245,7 +249,7 @@ def test_up_fwd_bwd_wgrad(L, Ci, Co, H, W, B, ring, dtype, force):
     assert rel_l2(db, ref_dx.sum(dim=[0, 2, 3])) < (tol if dtype == torch.float32 else 5e-2)
     from dusty_gan_amd.engine import Ops
     o = Ops(dtype)
-    o.force = 2 if force in (4, 5, 9) else force
+    o.force = L.DG_FORCE_MFMA if force in (L.DG_FORCE_LOCKSTEP, L.DG_FORCE_PINGPONG, L.DG_FORCE_PINGPONG_SINGLE) else force
     xd, ed = nhwc(x).to(DEV, dtype), nhwc(e).to(DEV, dtype)
     dw = torch.zeros(16, Ci, Co, device=DEV)
     o.wgrad(1, ring, B, H, W, Ci, Co, xd, (H * W * Ci, Ci, 1), ed, (4 * H * W * Co, Co, 1), dw.data_ptr(), s)
@@ -256,8 +260,8 @@ def test_up_fwd_bwd_wgrad(L, Ci, Co, H, W, B, ring, dtype, force):
 @pytest.mark.parametrize("B,N,epi", [(32, 4096, "lrelu"), (17, 2048, "lrelu"), (8, 1024, "linear"), (32, 131072, "lrelu"),
                                      (8, 131072, "lrelu"), (16, 131072, "linear"), (4, 524288, "lrelu")])
 def test_proj_forward_weight_streaming_kernel(L, B, N, epi):
-    """Proj forward (dcgan_eqlr.py:6-16) on the weight-streaming kernel (proj_stream.hip: dg_conv force 10 / what force 0
-    picks for bf16, K = 512, B <= 32) against the general MFMA kernel (force 2) and a float64 GEMM of the same bf16
+    """Proj forward (dcgan_eqlr.py:6-16) on the weight-streaming kernel (proj_stream.hip: DG_FORCE_PROJ_STREAM / what
+    DG_FORCE_AUTO picks for bf16, K = 512, B <= 32) against the general MFMA kernel (DG_FORCE_MFMA) and a float64 GEMM of the same bf16
     operands; ragged batch (17 of 32 MFMA columns), both epilogues, the benchmark's 131072-row shape at both register
     variants (B <= 16 / <= 32: eight ring turns per wave - a first version waited for one piece too few in the first turn
     and read one row in 8192 before it had landed) and the 128x2048 configuration's 524288 rows."""
@@ -270,7 +274,7 @@ def test_proj_forward_weight_streaming_kernel(L, B, N, epi):
     s = 1.0 / math.sqrt(N)
     code = L.EPI_LRELU if epi == "lrelu" else L.EPI_LINEAR
     outs = {}
-    for force in (10, 2, 0):
+    for force in (L.DG_FORCE_PROJ_STREAM, L.DG_FORCE_MFMA, L.DG_FORCE_AUTO):
         o = E.Ops(torch.bfloat16)
         o.force = force
         out = torch.full((B, N), 7.0, device=DEV, dtype=torch.bfloat16)
@@ -282,23 +286,24 @@ def test_proj_forward_weight_streaming_kernel(L, B, N, epi):
         finally:
             E.TRACE = None
         torch.cuda.synchronize()
-        assert fam == (2 if force == 2 else 6), (force, fam)
+        assert fam == (L.DG_CONV_FAMILY_MFMA if force == L.DG_FORCE_MFMA else L.DG_CONV_FAMILY_PROJ_STREAM), (force, fam)
         outs[force] = out.float().cpu()
     ref = (z.double().cpu() @ w.double().cpu().t()) * s + bias.double().cpu().repeat(N // C)[None, :]
     if epi == "lrelu":
         ref = torch.where(ref > 0, ref, 0.2 * ref) * math.sqrt(2.0)
-    assert bool(torch.isfinite(outs[10]).all())
-    assert rel_l2(outs[10], ref) < TOLBF and rel_l2(outs[2], ref) < TOLBF
-    assert rel_l2(outs[10], outs[2]) < 2e-3 and torch.equal(outs[0], outs[10])
-    assert float((outs[10] - ref.float()).abs().max()) < 0.05 * float(ref.abs().max())   # no single stale row
+    stream, mfma, auto = outs[L.DG_FORCE_PROJ_STREAM], outs[L.DG_FORCE_MFMA], outs[L.DG_FORCE_AUTO]
+    assert bool(torch.isfinite(stream).all())
+    assert rel_l2(stream, ref) < TOLBF and rel_l2(mfma, ref) < TOLBF
+    assert rel_l2(stream, mfma) < 2e-3 and torch.equal(auto, stream)
+    assert float((stream - ref.float()).abs().max()) < 0.05 * float(ref.abs().max())   # no single stale row
 
 
-@pytest.mark.parametrize("force", [5, 9], ids=["both-parities-tile", "single-parity-tile"])
+@pytest.mark.parametrize("force", [DG_FORCE_PINGPONG, DG_FORCE_PINGPONG_SINGLE], ids=["both-parities-tile", "single-parity-tile"])
 @pytest.mark.parametrize("Ci,H,W,B", [(128, 4, 128, 2), (64, 2, 256, 1), (128, 4, 64, 4), (128, 2, 512, 1)])
 def test_up_forward_64_channels_on_the_pingpong_kernel(L, Ci, H, W, B, force):
     """Up forward with 64 output channels (Up3: dcgan_eqlr.py:19-26 at 128 -> 64): MODE_UP, bias + leaky-relu epilogue, on
-    the ping-pong kernel's both-parities tile (512 pixels x 64 channels, force 5) and on the single-parity 256 x 64 tile
-    it replaces (force 9); 1 / 2 / 4 sample segments per tile and two column tiles per row.  (The Down / Up case list above
+    the ping-pong kernel's both-parities tile (512 pixels x 64 channels, DG_FORCE_PINGPONG) and on the single-parity 256 x 64
+    tile it replaces (DG_FORCE_PINGPONG_SINGLE); 1 / 2 / 4 sample segments per tile and two column tiles per row.  (The Down / Up case list above
     cannot hold this shape: its backward-data pass has K = 64, which the adjoint MODE_UP flavour refuses.)"""
     from dusty_gan_amd import engine as E
     Co = 64
@@ -314,12 +319,12 @@ def test_up_forward_64_channels_on_the_pingpong_kernel(L, Ci, H, W, B, force):
         tr = [t for t in E.TRACE if t[0] == "conv"][0]
     finally:
         E.TRACE = None
-    assert tr[1] == 5 and (tr[2], tr[3]) == ((512, 64) if force == 5 else (256, 64)), tr
+    assert tr[1] == L.DG_CONV_FAMILY_PINGPONG and (tr[2], tr[3]) == ((512, 64) if force == L.DG_FORCE_PINGPONG else (256, 64)), tr
     assert rel_l2(out, y) < TOLBF
 
 
 @pytest.mark.parametrize("wmode", [0, 1])
-@pytest.mark.parametrize("force", [2, 7, 8])
+@pytest.mark.parametrize("force", [DG_FORCE_MFMA, DG_FORCE_WG_DMA_PAIRS, DG_FORCE_WG_DMA_NOPAIRS])
 def test_wgrad_group_is_the_single_launches_in_one_grid(L, wmode, force):
     """dg_wgrad_group (round 5): up to four layers' weight-gradient GEMMs as ONE launch - every tile shape of the LDS-DMA kernel
     (128 / 64 input and output channels), tap pairs forced / forbidden / chosen, per-sample weights and the 3n-sample map on
@@ -363,7 +368,7 @@ def test_wgrad_group_is_the_single_launches_in_one_grid(L, wmode, force):
     groups = [t for t in tr if t[0] == "wgrad_group"]
     assert len(groups) == 1 and groups[0][1] == 4, tr          # four layers in the one launch, the fifth on its own
     assert not [t for t in tr0 if t[0] == "wgrad_group"]
-    assert [t[1] for t in tr if t[0] == "wgrad"] == [5] * 5
+    assert [t[1] for t in tr if t[0] == "wgrad"] == [L.DG_WGRAD_VARIANT_DMA] * 5
     for k, (x, y) in enumerate(zip(got, want)):
         assert float(y.abs().max()) > 0
         assert torch.equal(x, y), (k, rel_l2(x.cpu(), y.cpu()))
@@ -386,16 +391,18 @@ def test_wgrad_group_is_the_single_launches_in_one_grid(L, wmode, force):
 
 
 
-@pytest.mark.parametrize("force", [2, 7, 8], ids=["auto", "tap-pairs", "single-taps"])
+@pytest.mark.parametrize("force", [DG_FORCE_MFMA, DG_FORCE_WG_DMA_PAIRS, DG_FORCE_WG_DMA_NOPAIRS],
+                         ids=["auto", "tap-pairs", "single-taps"])
 @pytest.mark.parametrize("wmode,Ci,Co,H,W", [(0, 128, 128, 4, 128), (1, 128, 64, 4, 64), (0, 64, 128, 8, 64)])
 def test_wgrad_workspace_and_sample_map(L, wmode, Ci, Co, H, W, force):
     """The LDS-DMA weight-gradient kernel's split-K workspace form (DgWgrad.ws + dg_wgrad_reduce) and its gradient-sample
-    index map (DgWgrad.g_mod) against the register-staged kernel with atomics (force 6, itself held to autograd above):
+    index map (DgWgrad.g_mod) against the register-staged kernel with atomics (DG_FORCE_WG_REGSTAGED, itself held to autograd
+    above):
       (a) workspace partials, reduce adding onto a pre-filled dW == atomics onto the same dW;
       (b) deferred: two layers' partials summed by ONE reduce launch;
       (c) one launch over 3n input samples with g sample = b % 2n and per-sample weights == the two launches it replaces
           (the D phase's ordinary + R1 weight gradients, trainers/dcgan_amp.py:229-235).
-    W-tap pairs forced / forbidden / chosen (force 7 / 8 / 2)."""
+    W-tap pairs forced / forbidden / chosen (DG_FORCE_WG_DMA_PAIRS / _NOPAIRS / DG_FORCE_MFMA)."""
     from dusty_gan_amd import engine as E
     g = torch.Generator().manual_seed(wmode * 7 + Ci + W)
     n = 2
@@ -407,7 +414,7 @@ def test_wgrad_workspace_and_sample_map(L, wmode, Ci, Co, H, W, force):
     sa, sg = (fa * H * W * Ci, Ci, 1), (fg * H * W * Co, Co, 1)
     base = torch.randn(16, Ci, Co, generator=g).to(DEV)
     ref_o, o = E.Ops(torch.bfloat16), E.Ops(torch.bfloat16)
-    ref_o.force, ref_o.use_ws, o.force = 6, False, force
+    ref_o.force, ref_o.use_ws, o.force = L.DG_FORCE_WG_REGSTAGED, False, force
 
     def ref(B, a_off, rowscale):
         dw = base.clone()
@@ -422,8 +429,8 @@ def test_wgrad_workspace_and_sample_map(L, wmode, Ci, Co, H, W, force):
         tr = [t for t in E.TRACE if t[0] == "wgrad"][0]
     finally:
         E.TRACE = None
-    assert tr[1] == 5 and tr[5] and tr[3] >= 1, tr                     # LDS-DMA kernel, workspace in use
-    assert (tr[4] == 1) == (force == 7) or force == 2, tr               # tap pairs as forced
+    assert tr[1] == L.DG_WGRAD_VARIANT_DMA and tr[5] and tr[3] >= 1, tr                     # LDS-DMA kernel, workspace in use
+    assert (tr[4] == 1) == (force == L.DG_FORCE_WG_DMA_PAIRS) or force == L.DG_FORCE_MFMA, tr  # tap pairs as forced
     torch.cuda.synchronize()
     assert rel_l2(dw.cpu() - base.cpu(), want2.cpu() - base.cpu()) < 1e-5
     # the same launch through atomics (no workspace) still works
@@ -454,8 +461,8 @@ def test_wgrad_workspace_and_sample_map(L, wmode, Ci, Co, H, W, force):
         ref_o.wgrad(wmode, True, 3 * n, H, W, Ci, Co, a, sa, e, sg, dm.data_ptr(), 0.05, g_mod=2 * n)
 
 
-@pytest.mark.parametrize("dtype,force,B,nz,C3", [(torch.float32, 1, 3, 5, 6), (torch.float32, 2, 5, 64, 64),
-                                                 (torch.bfloat16, 2, 32, 128, 64)])
+@pytest.mark.parametrize("dtype,force,B,nz,C3", [(torch.float32, DG_FORCE_DIRECT, 3, 5, 6), (torch.float32, DG_FORCE_MFMA, 5, 64, 64),
+                                                 (torch.bfloat16, DG_FORCE_MFMA, 32, 128, 64)])
 def test_proj_gemm_and_wgrad(L, dtype, force, B, nz, C3):
     """Proj (dcgan_eqlr.py:6-16) as a GEMM with the (y,x,c) output order + its weight gradient."""
     from dusty_gan_amd.engine import Ops
@@ -813,7 +820,8 @@ def test_adam_proj_fused_matches_gemm_plus_adam(L, nb, Np, K):
                                       stepd.data_ptr(), decay, None) == L.DG_EUNSUPPORTED
 
 
-@pytest.mark.parametrize("Ci,Co,H,W,B,force", [(24, 20, 16, 32, 4, 1), (64, 128, 4, 128, 4, 2)], ids=["direct", "one-tile"])
+@pytest.mark.parametrize("Ci,Co,H,W,B,force", [(24, 20, 16, 32, 4, DG_FORCE_DIRECT), (64, 128, 4, 128, 4, DG_FORCE_MFMA)],
+                         ids=["direct", "one-tile"])
 def test_bias_gradient_staging_scratch_protocol(L, Ci, Co, H, W, B, force):
     """DgConv.dbias_ws as the direct / one-tile MFMA kernels use it (round 6): (1) the scratch is zero again when the launch
     has finished - word pairs and ticket - so the next launch of the stream can share it; (2) WITHOUT the scratch (a C-ABI caller
@@ -915,11 +923,15 @@ def test_philox_known_answer(L):
 
 
 @pytest.mark.parametrize("Ci,Co,H,W,B,dtype,cforce,wforce,family,variant", [
-    (6, 4, 8, 16, 3, torch.float32, 1, 1, 1, 1),       # direct conv + direct weight gradient (narrow nets, golden cases)
-    (24, 20, 16, 32, 4, torch.float32, 1, 1, 1, 1),
-    (64, 128, 4, 128, 4, torch.float32, 2, 2, 2, 2),   # one tile per workgroup + register-staged MFMA weight gradient (fp32 modes)
-    (128, 64, 8, 64, 4, torch.bfloat16, None, 6, 0, 2),  # ... that weight-gradient kernel at bf16 (force 6: behind the LDS-DMA form)
-    (128, 256, 2, 64, 8, torch.float32, 4, 2, 4, 2),   # lock-step persistent conv at fp32: one bias-gradient row per workgroup
+    # direct conv + direct weight gradient (narrow nets, golden cases)
+    (6, 4, 8, 16, 3, torch.float32, DG_FORCE_DIRECT, DG_FORCE_DIRECT, DG_CONV_FAMILY_DIRECT, DG_WGRAD_VARIANT_DIRECT),
+    (24, 20, 16, 32, 4, torch.float32, DG_FORCE_DIRECT, DG_FORCE_DIRECT, DG_CONV_FAMILY_DIRECT, DG_WGRAD_VARIANT_DIRECT),
+    # one tile per workgroup + register-staged MFMA weight gradient (fp32 modes)
+    (64, 128, 4, 128, 4, torch.float32, DG_FORCE_MFMA, DG_FORCE_MFMA, DG_CONV_FAMILY_MFMA, DG_WGRAD_VARIANT_MFMA),
+    # ... that weight-gradient kernel at bf16 (behind the LDS-DMA form: forced)
+    (128, 64, 8, 64, 4, torch.bfloat16, None, DG_FORCE_WG_REGSTAGED, 0, DG_WGRAD_VARIANT_MFMA),
+    # lock-step persistent conv at fp32: one bias-gradient row per workgroup
+    (128, 256, 2, 64, 8, torch.float32, DG_FORCE_LOCKSTEP, DG_FORCE_MFMA, DG_CONV_FAMILY_LOCKSTEP, DG_WGRAD_VARIANT_MFMA),
 ], ids=["direct-6x4", "direct-24x20", "one-tile-fp32", "register-staged-bf16", "lock-step-fp32"])
 def test_kernels_off_the_timed_path_sum_in_a_fixed_order(L, Ci, Co, H, W, B, dtype, cforce, wforce, family, variant):
     """Round 6: the kernels the fp32 modes and narrow nets run no longer add with float atomics in arrival order.

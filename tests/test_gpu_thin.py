@@ -1,6 +1,6 @@
 """GPU parity of the thin (<= 4-channel side) LDS/VALU kernels of csrc/conv_thin.hip against the CPU oracle:
 Down1 forward / backward-data / weight gradient (Cin = 2) and Head forward / backward-data / weight gradient
-(Cout = 1..3), in fp32 and bf16 feature-map storage, forced through the thin path (force = 3)."""
+(Cout = 1..3), in fp32 and bf16 feature-map storage, forced through the thin path (DG_FORCE_THIN)."""
 import math
 
 import pytest
@@ -40,7 +40,7 @@ def test_down1_thin(L, dtype, Hc, Wc, B):            # thin_s2_mfma's two-tiles-
     y = O.down(xr, wq.clone().requires_grad_(), br, True)
     s = 1.0 / math.sqrt(Ci * 16)
     o = Ops(dtype)
-    o.force = 3
+    o.force = L.DG_FORCE_THIN
     xd = nhwc(x).to(DEV, dtype)
     master = w.permute(2, 3, 1, 0).contiguous().to(DEV)  # [ky][kx][ci][co] fp32
     coci = w.permute(2, 3, 0, 1).contiguous().to(DEV, dtype)  # [tap][co][ci] shadow
@@ -109,7 +109,7 @@ def test_head_thin(L, dtype, nh, Hc, Wc):                                 # part
     scales = [1.0 / math.sqrt(16)] + [1.0 / math.sqrt(max(nh - 1, 1) * 16)] * (nh - 1)
     nscale = torch.tensor(scales, device=DEV)
     o = Ops(dtype)
-    o.force = 3
+    o.force = L.DG_FORCE_THIN
     xd = nhwc(x).to(DEV, dtype)
     HW = 4 * Hc * Wc
     out = torch.empty(B, nh, 2 * Hc, 2 * Wc, device=DEV)
@@ -169,7 +169,7 @@ def test_head_bwd_data_pixel_major_mfma(L, nh, Hc, Wc, B):
     prev = torch.randn(x.shape, generator=g)
     ref = gx * torch.where(prev > 0, 1.0, 0.2) * math.sqrt(2.0)
     o = Ops(dtype)
-    o.force = 3
+    o.force = L.DG_FORCE_THIN
     HW = 4 * Hc * Wc
     cp = 2 if nh <= 2 else 4                     # channel padding of the pixel-major gradient
     draw_pm = torch.zeros(B, 2 * Hc, 2 * Wc, cp)
@@ -224,7 +224,7 @@ def test_head_wgrad_pixel_major_mfma(L, nh, Hc, Wc, B):
     gws = torch.autograd.grad(y, ws, gy * rs.view(B, 1, 1, 1))
     ref = torch.cat(list(gws), dim=1)  # [ci][co][ky][kx]
     o = Ops(dtype)
-    o.force = 3
+    o.force = L.DG_FORCE_THIN
     HW = 4 * Hc * Wc
     cp = 2 if nh <= 2 else 4
     draw_pm = torch.full((B, 2 * Hc, 2 * Wc, cp), 7.0)  # unused padding channels must not leak into the real ones
@@ -243,7 +243,7 @@ def test_head_wgrad_pixel_major_mfma(L, nh, Hc, Wc, B):
     # the launch above stored one partial tile per block in the workspace (summed by dg_wgrad_reduce's wide form when there
     # are more than 64 of them) unless the map is too wide for a single pass; with fp32 atomics onto dW instead: the same
     one_pass = not (nh == 3 and Wc == 2048)
-    assert trace[0][1] == 7 and trace[0][5] == one_pass and (trace[0][3] == B * Hc // 2 if one_pass else True), trace
+    assert trace[0][1] == L.DG_WGRAD_VARIANT_THIN_MFMA and trace[0][5] == one_pass and (trace[0][3] == B * Hc // 2 if one_pass else True), trace
     o.use_ws = False
     dw2 = torch.zeros(16, C0, nh, device=DEV)
     o.wgrad(1, True, B, Hc, Wc, C0, nh, xd, (Hc * Wc * C0, C0, 1), draw_pm, (HW * cp, cp, 1), dw2.data_ptr(), 1.0,
@@ -281,7 +281,7 @@ def test_down1_wgrad_one_launch_over_real_fake_tangent(L, n, Hc):
         assert o.wgrad_takes_map(0, True, 3 * n, Hc, Wc, Ci, Co, a, sa, e, sg, two.data_ptr())
         one = torch.zeros(16, Ci, Co, device=DEV)
         o.wgrad(0, True, 3 * n, Hc, Wc, Ci, Co, a, sa, e, sg, one.data_ptr(), 0.1, rowscale=rs, g_mod=2 * n)
-        assert all(t[1] == 7 and t[5] for t in E.TRACE if t[0] == "wgrad"), E.TRACE   # the thin matrix-core kernel, partial
+        assert all(t[1] == L.DG_WGRAD_VARIANT_THIN_MFMA and t[5] for t in E.TRACE if t[0] == "wgrad"), E.TRACE   # the thin matrix-core kernel, partial
         assert E.TRACE[-1][3] == 3 * n * Hc // 2                                       # tiles in the workspace: one per block
         o.use_ws = False                                                               # fp32 atomics onto dW: the same sums
         atom = torch.zeros(16, Ci, Co, device=DEV)
@@ -301,7 +301,7 @@ def test_down1_wgrad_one_launch_over_real_fake_tangent(L, n, Hc):
             for b in range(3 * n):
                 ref[ky * 4 + kx] += 0.1 * float(rs[b]) * torch.einsum("chw,hwo->co", win[b], e_h[b % (2 * n)])
     assert rel_l2(one.cpu(), ref) < 1e-2
-    o.force = 1                                    # the direct kernel has no map: refused, not ignored
+    o.force = L.DG_FORCE_DIRECT                    # the direct kernel has no map: refused, not ignored
     with pytest.raises(L.DgError):
         o.wgrad(0, True, 3 * n, Hc, Wc, Ci, Co, a, sa, e, sg, one.data_ptr(), 0.1, g_mod=2 * n)
 
@@ -337,7 +337,7 @@ def test_thin_up_fragments_kept_with_the_shadows(L, case, Hc):
     w = master.bfloat16() if adj else coci                                                       # [tap][n][k] shadow
     x = torch.randn(B, Hc, Wc, K, generator=g).to(DEV, torch.bfloat16)
     o = Ops(torch.bfloat16)
-    o.force = 3
+    o.force = L.DG_FORCE_THIN
     outs = []
     from dusty_gan_amd import engine as E
     E.TRACE = []
@@ -348,7 +348,7 @@ def test_thin_up_fragments_kept_with_the_shadows(L, case, Hc):
         torch.cuda.synchronize()
         outs.append(out.clone())
     trace, E.TRACE = E.TRACE, None
-    assert all(t[1] == 3 and t[8] == (2 if Hc >= 2 else 0) for t in trace), trace     # thin_up_mfma (needs two rows)
+    assert all(t[1] == L.DG_CONV_FAMILY_THIN and t[8] == (2 if Hc >= 2 else 0) for t in trace), trace     # thin_up_mfma (needs two rows)
     assert float(outs[0].float().abs().mean()) > 0.01
     assert torch.equal(outs[0], outs[1])
     # argument checks
@@ -372,7 +372,7 @@ def test_depth_head_applies_tanh_and_stores_the_image_sums(L, Hc, Wc, B):
     g = torch.Generator().manual_seed(Hc + Wc)
     K = 64
     o = Ops(torch.bfloat16)
-    o.force = 3
+    o.force = L.DG_FORCE_THIN
     x = torch.randn(B, Hc, Wc, K, generator=g).to(DEV, torch.bfloat16)
     for N in (1, 2):
         w = (torch.randn(16, N, K, generator=g) * 0.5).to(DEV, torch.bfloat16)

@@ -12,6 +12,8 @@ import math
 import pytest
 import torch
 
+from dusty_gan_amd._lib import (DG_CONV_FAMILY_LOCKSTEP, DG_CONV_FAMILY_PINGPONG, DG_FORCE_LOCKSTEP, DG_FORCE_PINGPONG,
+                                DG_WGRAD_VARIANT_DMA)
 from tests import test_gpu_ops as OPS
 from tests.golden_util import rel_l2
 from tests.test_gpu_step import _cos, make_trainer, run_both
@@ -29,35 +31,36 @@ def trace():
 
 
 def _persist(trace):
-    return [t for t in trace if t[0] == "conv" and t[1] in (4, 5)]  # 4 lock-step persistent, 5 ping-pong persistent
+    return [t for t in trace if t[0] == "conv" and t[1] in (DG_CONV_FAMILY_LOCKSTEP, DG_CONV_FAMILY_PINGPONG)]
 
 
-# (Ci, Co, H, W, B, dtype, wg_cap): the large-tile kernel with `wg_cap` workgroups, i.e. >= 4 tiles per workgroup, on
+# (Ci, Co, H, W, B, dtype, wg_cap, force): the large-tile kernel with `wg_cap` workgroups, i.e. >= 4 tiles per workgroup, on
 # all three tile shapes (256 x 128, 256 x 64, 128 x 128), both modes, adj 0 / 1, bias-gradient sums with per-sample
 # weights, uneven chunk lengths (tile count not a multiple of the workgroup count)
 MULTI = [
-    (128, 256, 4, 128, 8, torch.bfloat16, 5, 5),    # 256 x 128 tiles from 2 samples' row segments
-    (256, 128, 4, 128, 8, torch.bfloat16, 3, 5),
-    (128, 128, 4, 512, 4, torch.bfloat16, 7, 5),    # two x tiles per row
-    (128, 256, 4, 64, 16, torch.bfloat16, 4, 5),    # 4 samples' row segments per tile
-    (64, 128, 4, 256, 4, torch.bfloat16, 5, 5),     # 64-channel side: 256 x 64 tiles in the backward-data passes
-    (128, 256, 4, 128, 8, torch.bfloat16, 5, 4),    # the lock-step kernel on the same geometries
-    (128, 256, 4, 64, 14, torch.bfloat16, 6, 4),    # 14 % 4 != 0: 128 x 128 tiles from 2 samples' row segments
-    (64, 128, 4, 256, 4, torch.bfloat16, 5, 4),
-    (128, 256, 4, 64, 16, torch.float32, 3, 4),     # fp32 instance (64-byte stages x 4)
-    (128, 128, 4, 256, 8, torch.float32, 5, 4),
+    (128, 256, 4, 128, 8, torch.bfloat16, 5, DG_FORCE_PINGPONG),    # 256 x 128 tiles from 2 samples' row segments
+    (256, 128, 4, 128, 8, torch.bfloat16, 3, DG_FORCE_PINGPONG),
+    (128, 128, 4, 512, 4, torch.bfloat16, 7, DG_FORCE_PINGPONG),    # two x tiles per row
+    (128, 256, 4, 64, 16, torch.bfloat16, 4, DG_FORCE_PINGPONG),    # 4 samples' row segments per tile
+    (64, 128, 4, 256, 4, torch.bfloat16, 5, DG_FORCE_PINGPONG),     # 64-channel side: 256 x 64 tiles in the backward-data passes
+    (128, 256, 4, 128, 8, torch.bfloat16, 5, DG_FORCE_LOCKSTEP),    # the lock-step kernel on the same geometries
+    (128, 256, 4, 64, 14, torch.bfloat16, 6, DG_FORCE_LOCKSTEP),    # 14 % 4 != 0: 128 x 128 tiles from 2 samples' row segments
+    (64, 128, 4, 256, 4, torch.bfloat16, 5, DG_FORCE_LOCKSTEP),
+    (128, 256, 4, 64, 16, torch.float32, 3, DG_FORCE_LOCKSTEP),     # fp32 instance (64-byte stages x 4)
+    (128, 128, 4, 256, 8, torch.float32, 5, DG_FORCE_LOCKSTEP),
 ]
 
 
-@pytest.mark.parametrize("Ci,Co,H,W,B,dtype,cap,family", MULTI)
+@pytest.mark.parametrize("Ci,Co,H,W,B,dtype,cap,force", MULTI)
 @pytest.mark.parametrize("which", ["down", "up"])
-def test_persistent_conv_several_tiles_per_workgroup(monkeypatch, trace, which, Ci, Co, H, W, B, dtype, cap, family):
+def test_persistent_conv_several_tiles_per_workgroup(monkeypatch, trace, which, Ci, Co, H, W, B, dtype, cap, force):
     from dusty_gan_amd.engine import Ops
     monkeypatch.setattr(Ops, "default_wg_cap", cap)
     from dusty_gan_amd import _lib as L
     fn = OPS.test_down_fwd_bwd_wgrad if which == "down" else OPS.test_up_fwd_bwd_wgrad
-    fn(L, Ci, Co, H, W, B, True, dtype, family)
-    pc = [t for t in trace if t[0] == "conv" and t[1] == family]   # dg_conv force 4 / 5 -> plan family 4 / 5
+    fn(L, Ci, Co, H, W, B, True, dtype, force)
+    family = {DG_FORCE_LOCKSTEP: DG_CONV_FAMILY_LOCKSTEP, DG_FORCE_PINGPONG: DG_CONV_FAMILY_PINGPONG}[force]
+    pc = [t for t in trace if t[0] == "conv" and t[1] == family]
     # forward + backward-data both on the persistent kernel (bf16: run_conv repeats the backward-data launch without the
     # saved mask bits to compare the two forms)
     assert len(pc) == (2 if dtype != torch.bfloat16 else 3), trace
@@ -127,7 +130,7 @@ def test_bench_configuration_step_vs_oracle(trace, amp):
     assert len(pc) >= 10 and max(t[6] for t in pc) > 1, pc          # persistent conv with tcount > 1 ran ...
     assert any(t[2:4] == (256, 128) for t in pc)
     if amp:
-        assert any(t[0] == "wgrad" and t[1] == 5 for t in trace)    # ... and the LDS-DMA weight-gradient kernel
+        assert any(t[0] == "wgrad" and t[1] == DG_WGRAD_VARIANT_DMA for t in trace)    # ... and the LDS-DMA weight-gradient kernel
         assert tr.optim_G.regen_grad is not None                    # Proj.weight went through dg_adam_proj_fused
     _check_step(res[0], tr, state, amp)
 

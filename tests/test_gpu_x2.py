@@ -85,7 +85,7 @@ def run_conv_x2(L, mode, adj, x, w_nk, N, scale, epi, force, bias=None, aux=None
     rs = None if rowscale is None else rowscale.to(DEV)
     E.TRACE = []
     try:
-        if force == 1:   # the direct kernel reads the split weights through dg_ld like everything else
+        if force == L.DG_FORCE_DIRECT:   # the direct kernel reads the split weights through dg_ld like everything else
             o.conv(mode, adj, True, B, Hc, Wc, K, N, xd, (Hin * Win * K, K, 1), out, (Ho * Wo * N, N, 1), tw.data_ptr(), scale, epi,
                    bias=None if biasd is None else biasd.data_ptr(), bias_mod=N, aux=auxd,
                    dbias=None if db is None else db.data_ptr(), rowscale=rs, w_dt=L.DG_BF16X2, w_strides=(N * K, 1, K))
@@ -98,12 +98,12 @@ def run_conv_x2(L, mode, adj, x, w_nk, N, scale, epi, force, bias=None, aux=None
         E.TRACE = None
         E.X2_TWIN.pop(wd.data_ptr(), None)
     torch.cuda.synchronize()
-    assert fam == (1 if force == 1 else 5), fam
+    assert fam == (L.DG_CONV_FAMILY_DIRECT if force == L.DG_FORCE_DIRECT else L.DG_CONV_FAMILY_PINGPONG), fam
     res = from_nhwc(from_x2(out).cpu(), B, N, Ho, Wo)
     return (res, db.cpu()) if want_db else res
 
 
-X2_CASES = [  # (Ci, Co, H, W, B): the ping-pong kernel's tile flavours (tests/test_gpu_ops.py CASES, force 5)
+X2_CASES = [  # (Ci, Co, H, W, B): the ping-pong kernel's tile flavours (tests/test_gpu_ops.py CASES, DG_FORCE_PINGPONG)
     (256, 128, 4, 128, 2),
     (128, 128, 2, 512, 1),
     (128, 256, 4, 64, 8),
@@ -124,24 +124,24 @@ def test_down_layer(L, Ci, Co, H, W, B):
     y = O.down(xr, wr, br, True)
     fwd, bwd = pack_down(w)
     s = 1.0 / math.sqrt(Ci * 16)
-    out = run_conv_x2(L, L.MODE_S2, 0, x, fwd, Co, s, L.EPI_LRELU, 5, bias=b)
+    out = run_conv_x2(L, L.MODE_S2, 0, x, fwd, Co, s, L.EPI_LRELU, L.DG_FORCE_PINGPONG, bias=b)
     assert rel_l2(out, y) < TOL
     gy = torch.randn(y.shape, generator=g)
     e = gy * torch.where(y > 0, 1.0, 0.2) * math.sqrt(2.0)
     gx, gw = torch.autograd.grad(y, [xr, wr], gy, retain_graph=True)
     prev = torch.randn(x.shape, generator=g)
     rs = torch.rand(B, generator=g) + 0.5
-    dx, db = run_conv_x2(L, L.MODE_UP, 1, e, bwd, Ci, s, L.EPI_MASK, 5, aux=prev, want_db=True, rowscale=rs)
+    dx, db = run_conv_x2(L, L.MODE_UP, 1, e, bwd, Ci, s, L.EPI_MASK, L.DG_FORCE_PINGPONG, aux=prev, want_db=True, rowscale=rs)
     ref_dx = gx * torch.where(prev > 0, 1.0, 0.2) * math.sqrt(2.0)
     assert rel_l2(dx, ref_dx) < TOL
     assert rel_l2(db, (ref_dx * rs.view(B, 1, 1, 1)).sum(dim=[0, 2, 3])) < TOL
     # ... and the direct kernel on the same split buffers (dg_ld / dg_st understand the form): the layout's second opinion
     if Ci * Co <= 128 * 128:
-        out1 = run_conv_x2(L, L.MODE_S2, 0, x, fwd, Co, s, L.EPI_LRELU, 1, bias=b)
+        out1 = run_conv_x2(L, L.MODE_S2, 0, x, fwd, Co, s, L.EPI_LRELU, L.DG_FORCE_DIRECT, bias=b)
         assert rel_l2(out1, y) < TOL
     # weight gradient on the LDS-DMA kernel, with per-sample weights
     o = E.Ops(torch.float32)
-    o.force = 2
+    o.force = L.DG_FORCE_MFMA
     xd, ed = to_x2(nhwc(x)), to_x2(nhwc(e))
     for rsd, ref in ((None, gw), (rs, None)):
         dw = torch.zeros(16, Ci, Co, device=DEV)
@@ -171,7 +171,7 @@ def test_up_layer(L, Ci, Co, H, W, B):
     y = O.up(xr, wr, br, True)
     fwd, bwd = pack_up(w)
     s = 1.0 / math.sqrt(Co * 16)
-    out = run_conv_x2(L, L.MODE_UP, 0, x, fwd, Co, s, L.EPI_LRELU, 5, bias=b)
+    out = run_conv_x2(L, L.MODE_UP, 0, x, fwd, Co, s, L.EPI_LRELU, L.DG_FORCE_PINGPONG, bias=b)
     assert rel_l2(out, y) < TOL
     gy = torch.randn(y.shape, generator=g)
     lr = torch.where(y > 0, 1.0, 0.2) * math.sqrt(2.0)
@@ -179,12 +179,12 @@ def test_up_layer(L, Ci, Co, H, W, B):
     gx, gw = torch.autograd.grad(y, [xr, wr], gy)
     if Co >= 128:            # (the adjoint MODE_UP... the MODE_S2 adjoint pass contracts over Co: the kernel wants >= 128)
         prev = torch.randn(x.shape, generator=g)
-        dx, db = run_conv_x2(L, L.MODE_S2, 1, e, bwd, Ci, s, L.EPI_MASK, 5, aux=prev, want_db=True)
+        dx, db = run_conv_x2(L, L.MODE_S2, 1, e, bwd, Ci, s, L.EPI_MASK, L.DG_FORCE_PINGPONG, aux=prev, want_db=True)
         ref_dx = gx * torch.where(prev > 0, 1.0, 0.2) * math.sqrt(2.0)
         assert rel_l2(dx, ref_dx) < TOL
         assert rel_l2(db, ref_dx.sum(dim=[0, 2, 3])) < TOL
     o = E.Ops(torch.float32)
-    o.force = 2
+    o.force = L.DG_FORCE_MFMA
     xd, ed = to_x2(nhwc(x)), to_x2(nhwc(e))
     dw = torch.zeros(16, Ci, Co, device=DEV)
     o.wgrad(1, True, B, H, W, Ci, Co, xd, (H * W * Ci, Ci, 1), ed, (4 * H * W * Co, Co, 1), dw.data_ptr(), s)
@@ -200,7 +200,7 @@ def test_wgrad_group_and_sample_map(L):
     n = 2
     shapes = [(64, 128, 8, 128), (128, 256, 4, 64), (256, 128, 2, 64)]   # (Ci, Co, H, W) of a Down chain
     ops = E.Ops(torch.float32)
-    ops.force = 2
+    ops.force = L.DG_FORCE_MFMA
     data = []
     for Ci, Co, H, W in shapes:
         a = to_x2(torch.randn(3 * n * 4 * H * W * Ci, generator=g))
@@ -259,7 +259,7 @@ def test_network_ends_on_the_thin_kernels(L, nheads):
         fam = [t for t in E.TRACE if t[0] == "conv"][0][1]
     finally:
         E.TRACE = None
-    assert fam == 3, fam
+    assert fam == L.DG_CONV_FAMILY_THIN, fam
     # the same launch from the fp32 copy of the split input: the reference of this comparison (hi + lo is what the kernel sees)
     xf = from_x2(xd)
     ref = torch.empty_like(out)

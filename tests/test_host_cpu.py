@@ -90,6 +90,16 @@ def test_ctypes_structs_match_header(built, tmp_path):
         _check_against_c(cname, getattr(built, cname), structs, lay, "_lib.py")
 
 
+def test_kernel_codes_match_header(built):
+    """the request codes of `force` (DG_FORCE_*) and the reported kernel codes (DG_CONV_FAMILY_*, DG_WGRAD_VARIANT_*) of
+    include/dusty_gan_hip.h: _lib.py has the same names with the same values"""
+    h = open(os.path.join(ROOT, "include", "dusty_gan_hip.h")).read()
+    pat = r"DG_(?:FORCE|CONV_FAMILY|WGRAD_VARIANT)_\w+"
+    codes = {n: int(v, 0) for n, v in re.findall(rf"^#define\s+({pat})\s+(0x[0-9a-fA-F]+|\d+)\b", h, flags=re.M)}
+    assert len(codes) == 23 and codes["DG_FORCE_FP32X3"] == 0x100, codes
+    assert {n: getattr(built, n) for n in dir(built) if re.fullmatch(pat, n)} == codes
+
+
 def test_integration_md_stubs_match_header(built, tmp_path):
     """INTEGRATION.md is the binding a maintainer copies: every ctypes Structure it shows must have the header's field
     names, order, offsets and sizeof (round 3 shipped a DgConv stub two fields short), and every `lib.dg_*` call it shows
