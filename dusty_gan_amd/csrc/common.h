@@ -177,66 +177,45 @@ __device__ __forceinline__ float dg_wave_sum(float v) {
   return v;
 }
 
-// ---- deterministic cross-block sums (round 5).  A float atomicAdd from many blocks sums in arrival order: the last bits of
-// the total - a per-sample image sum, a logit - differ from run to run, and everything downstream with them.  For
-// accumulators inside the registered arena (dg_det_arena: the step's AccArena, plus a shadow of DG_DET_STRIDE bytes per float,
-// zero at rest) a block instead adds its partial as 32.32 FIXED POINT to the slot's 64-bit shadow word - integer addition is
-// associative, the order no longer matters - and takes a ticket; the block that draws the last ticket converts the total and
-// adds it to the float ONCE, leaving the shadow zero.  The integer add is acknowledged (s_waitcnt vmcnt(0): atomics execute
-// memory-side) before the ticket is taken, so the last ticket holder reads every contribution.  Range +-2^31, resolution
-// 2.3e-10 per contribution; a non-finite or larger partial reaches the float as it is (a NaN stays a NaN).  Anything outside
-// the arena, or with no arena registered, falls back to the float atomic.
-// What the parity modes rely on (round-5 advice): the window.  Each CONTRIBUTION is range-checked, the running total is not -
-// it wraps beyond +-2^31, so a slot's contributors must stay below that in sum: the step's slots hold per-sample image sums
-// (<= H W = 2.6e5 at 128x2048), logits (O(1)), R1's per-sample |g|^2 (O(1)) and the augment adjoint's window sums: eight
-// orders of magnitude of head-room.  The resolution is ABSOLUTE (2^-32 per contribution): a sum whose true value is far below
-// 1e-6 - R1's |g|^2 late in a collapsed training run - keeps fewer significant bits here than a float atomic would; the
-// logged penalty then reads a few 1e-10 off, its gradient is untouched (the tangent is formed from g itself, not from ssq).
-// Ordering: the integer add is a memory-side atomic; `s_waitcnt vmcnt(0)` returns when it has been performed, and the ticket is
-// a second memory-side atomic on the same line issued behind it - the last ticket holder's exchange follows every add.
-// One 128-byte line per slot (round 6): device-scope atomics execute memory-side and adds to ONE line serialise - with 16 bytes
-// per slot the 32 per-sample sums of a batch shared four lines, and every image-sized kernel that sums per sample paid 4-5 us
-// for its 512-1536 adds (scripts/bench_pointwise.py: head_post_fwd 10.6 us with sums, 6.9 without).
-#define DG_DET_STRIDE 128
-struct DgDet { float* base; unsigned long long* shadow; long n; };
-__device__ __forceinline__ void dg_acc_add(float* dst, float v, unsigned contributors, const DgDet d) {
-  const long k = dst - d.base;
-  if (d.shadow == nullptr || k < 0 || k >= d.n || contributors <= 1) { atomicAdd(dst, v); return; }
-  unsigned long long* acc = d.shadow + (DG_DET_STRIDE / 8) * k;
-  unsigned* ticket = (unsigned*)(acc + 1);
-  if (!(fabsf(v) < 2147483000.f)) { atomicAdd(dst, v); v = 0.f; }
-  const long long q = __double2ll_rn((double)v * 4294967296.0);
-  atomicAdd(acc, (unsigned long long)q);
+// ---- deterministic cross-workgroup sums (round 5).  A float atomicAdd from many workgroups sums in arrival order: the last
+// bits of the total differ from run to run, and everything downstream with them.  Every cross-workgroup sum here follows one
+// protocol instead, with a last-arrival TICKET.  Each contributor adds its partial into shared slots with device-scope atomics
+// (in fixed point, dg_fix1 / dg_fix2, wherever the total must not depend on the arrival order: integer adds are associative),
+// then calls dg_ticket_last or its wave or block form.  The ONE caller that draws the last of `arrivals` tickets gets true: it
+// reads the slots back with atomics (atomicExch, never plain loads), writes the total once and leaves every slot zero; the helper
+// leaves the ticket zero.  The scratches are zero at rest, so consecutive launches share them.
+// Ordering, without a fence (one would write back L2): the adds execute memory-side, `s_waitcnt vmcnt(0)` returns once they
+// have been performed, and the ticket is a memory-side atomic issued behind them - the last holder's exchanges follow every add.
+__device__ __forceinline__ bool dg_ticket_last(unsigned* ticket, unsigned arrivals) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (atomicAdd(ticket, 1u) == contributors - 1) {
-    const long long tot = (long long)atomicExch(acc, 0ull);
-    atomicExch(ticket, 0u);
-    atomicAdd(dst, (float)((double)tot * (1.0 / 4294967296.0)));
-  }
+  if (atomicAdd(ticket, 1u) != arrivals - 1) return false;
+  atomicExch(ticket, 0u);
+  return true;
+}
+// lane 0 (which must be active) draws for its wave; every lane gets the answer
+__device__ __forceinline__ bool dg_wave_ticket_last(unsigned* ticket, unsigned arrivals) {
+  unsigned last = 0;
+  if (__lane_id() == 0) last = dg_ticket_last(ticket, arrivals);
+  return __builtin_amdgcn_readfirstlane(last);
+}
+// every thread of the block calls it once (barriers); thread 0 draws for the block, every thread gets the answer
+__device__ __forceinline__ bool dg_block_ticket_last(unsigned* ticket, unsigned arrivals) {
+  __shared__ unsigned s_last;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (every wave's adds performed before thread 0 draws)
+  __syncthreads();
+  if ((threadIdx.x | threadIdx.y | threadIdx.z) == 0) s_last = dg_ticket_last(ticket, arrivals);
+  __syncthreads();
+  return s_last;
 }
 
-// dg_acc_add that also tells its caller whether it drew the LAST ticket: 1 = last (total = the sum of all `contributors`
-// partials of this round, already added to *dst), 0 = not last, -1 = dst is outside the registered arena (a float atomic was
-// issued; nobody knows who is last).  For a second-level sum by the last contributors only (blur_r1_tangent_kernel's batch mean:
-// 32 adds to one word instead of 512).
-__device__ __forceinline__ int dg_acc_add_last(float* dst, float v, unsigned contributors, const DgDet d, float& total) {
-  const long k = dst - d.base;
-  if (d.shadow == nullptr || k < 0 || k >= d.n) { atomicAdd(dst, v); return -1; }
-  unsigned long long* acc = d.shadow + (DG_DET_STRIDE / 8) * k;
-  unsigned* ticket = (unsigned*)(acc + 1);
-  if (!(fabsf(v) < 2147483000.f)) { atomicAdd(dst, v); v = 0.f; }
-  const long long q = __double2ll_rn((double)v * 4294967296.0);
-  atomicAdd(acc, (unsigned long long)q);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (atomicAdd(ticket, 1u) == contributors - 1) {
-    const long long tot = (long long)atomicExch(acc, 0ull);
-    atomicExch(ticket, 0u);
-    total = (float)((double)tot * (1.0 / 4294967296.0));
-    atomicAdd(dst, total);
-    return 1;
-  }
-  return 0;
+// ---- one-word (32.32) fixed point: q = rint(v 2^32).  Range +-2^31 per term (larger or non-finite: false, the caller's float
+// path, so a NaN stays a NaN); resolution 2^-32, ABSOLUTE.  The running total is not range-checked: it wraps beyond +-2^31.
+__device__ __forceinline__ bool dg_fix1(float v, long long& q) {
+  if (!(fabsf(v) < 2147483000.f)) return false;
+  q = __double2ll_rn((double)v * 4294967296.0);
+  return true;
 }
+__device__ __forceinline__ float dg_fix1_value(long long q) { return (float)((double)q * (1.0 / 4294967296.0)); }
 
 // ---- two-word fixed point (round 6): float sums that do not depend on the order of their terms, without the one-word form's
 // absolute resolution.  v = hi 2^-20 + lo 2^-60 with hi = rint(v 2^20) and lo = the residual, which float arithmetic forms exactly
@@ -255,11 +234,59 @@ __device__ __forceinline__ bool dg_fix2(float v, long long& hi, long long& lo) {
 __device__ __forceinline__ float dg_fix2_value(long long hi, long long lo) {
   return (float)((double)hi * (1.0 / 1048576.0) + (double)lo * (1.0 / 1152921504606846976.0));
 }
-// ... across the workgroups of one launch, through the caller's staging scratch (DgConv.dbias_ws: zero on entry, left zero): word
-// pair i belongs to bias channel i, the LAST u64 of the scratch is the ticket.  Every workgroup adds its channel sums
-// (dg_dbias_ws_add), then ALL its threads call dg_dbias_ws_finish once: the adds are acknowledged (memory-side atomics), a ticket
-// is drawn, and the workgroup that draws the last one adds the totals onto dbias - one float add per channel and launch.
+
+// ---- dg_acc_add: accumulators inside the registered arena (dg_det_arena: the step's AccArena, plus a shadow of DG_DET_STRIDE
+// bytes per float, zero at rest) are summed in 32.32 in the slot's 64-bit shadow word, the ticket in the word after it.  Anything
+// outside the arena, or with no arena registered, falls back to the float atomic.
+// What the parity modes rely on (round-5 advice): the window.  A slot's contributors must stay below +-2^31 in sum: the step's
+// slots hold per-sample image sums (<= H W = 2.6e5 at 128x2048), logits (O(1)), R1's per-sample |g|^2 (O(1)) and the augment
+// adjoint's window sums: eight orders of magnitude of head-room.  The resolution is ABSOLUTE (2^-32 per contribution): a sum whose
+// true value is far below 1e-6 - R1's |g|^2 late in a collapsed training run - keeps fewer significant bits here than a float
+// atomic would; the logged penalty then reads a few 1e-10 off, its gradient is untouched (the tangent is formed from g itself).
+// One 128-byte line per slot (round 6): device-scope atomics execute memory-side and adds to ONE line serialise - with 16 bytes
+// per slot the 32 per-sample sums of a batch shared four lines, and every image-sized kernel that sums per sample paid 4-5 us
+// for its 512-1536 adds (scripts/bench_pointwise.py: head_post_fwd 10.6 us with sums, 6.9 without).
+#define DG_DET_STRIDE 128
+struct DgDet { float* base; unsigned long long* shadow; long n; };
+// dg_acc_add that also tells its caller whether it drew the LAST ticket: 1 = last (total = the sum of all `contributors`
+// partials of this round, already added to *dst), 0 = not last, -1 = dst is outside the registered arena (a float atomic was
+// issued; nobody knows who is last).  For a second-level sum by the last contributors only (blur_r1_tangent_kernel's batch mean:
+// 32 adds to one word instead of 512).
+__device__ __forceinline__ int dg_acc_add_last(float* dst, float v, unsigned contributors, const DgDet d, float& total) {
+  const long k = dst - d.base;
+  if (d.shadow == nullptr || k < 0 || k >= d.n) { atomicAdd(dst, v); return -1; }
+  unsigned long long* acc = d.shadow + (DG_DET_STRIDE / 8) * k;
+  long long q = 0;
+  if (!dg_fix1(v, q)) atomicAdd(dst, v);
+  atomicAdd(acc, (unsigned long long)q);
+  if (!dg_ticket_last((unsigned*)(acc + 1), contributors)) return 0;
+  total = dg_fix1_value((long long)atomicExch(acc, 0ull));
+  atomicAdd(dst, total);
+  return 1;
+}
+// (a single contributor adds its float directly)
+__device__ __forceinline__ void dg_acc_add(float* dst, float v, unsigned contributors, const DgDet d) {
+  float total;
+  if (contributors <= 1) atomicAdd(dst, v);
+  else dg_acc_add_last(dst, v, contributors, d, total);
+}
+
+// ---- the staging scratches' layouts.  DgConv.dbias_ws (DG_DBIAS_SLOTS x DG_DBIAS_SLOT_FLOATS floats), one layout per kernel:
+//   conv_direct, conv_mfma   u64 pair (2i, 2i+1) = channel i in dg_fix2 form; the ticket in the LAST u64
+//   thin_smallk_kernel       u64 word i < 64 = channel n_base + i in 32.32; the ticket in u64 word 64
+//   thin_s2_mfma_kernel      per slot of DG_DBIAS_SLOT_FLOATS floats: floats 0..63 = float channel sums, the ticket at float 64
+// head_post_bwd4_kernel's bias_ws (DG_BIAS_WS_SAMPLE_FLOATS per sample): u64 word h < 3 = head h in 32.32, the ticket in u64
+// word 3; the launch's accumulators, in the same form, at float DG_BIAS_WS_ACC (the upper half of sample 0's slot).
 #define DG_DBIAS_WS_WORDS (DG_DBIAS_SLOTS * DG_DBIAS_SLOT_FLOATS / 2)
+#define DG_BIAS_WS_SAMPLE_FLOATS 1024
+#define DG_BIAS_WS_ACC 512
+__device__ __forceinline__ unsigned* dg_dbias_ws_ticket(float* ws) { return (unsigned*)((unsigned long long*)ws + DG_DBIAS_WS_WORDS - 1); }
+__device__ __forceinline__ unsigned* dg_thin_ws_ticket(float* ws) { return (unsigned*)((unsigned long long*)ws + 64); }
+__device__ __forceinline__ unsigned* dg_dbias_slot_ticket(float* slot) { return (unsigned*)(slot + 64); }
+__device__ __forceinline__ unsigned* dg_bias_ws_ticket(unsigned long long* w) { return (unsigned*)(w + 3); }
+// dg_fix2 sums across the workgroups of one launch, through DgConv.dbias_ws: every workgroup adds its channel sums
+// (dg_dbias_ws_add), then ALL its threads call dg_dbias_ws_finish once; the last workgroup adds the totals onto dbias - one
+// float add per channel and launch.
 __device__ __forceinline__ bool dg_dbias_ws_ok(const float* ws, int bias_mod) {
   return ws != nullptr && 2 * bias_mod + 2 <= DG_DBIAS_WS_WORDS;
 }
@@ -269,21 +296,14 @@ __device__ __forceinline__ void dg_dbias_ws_add(float* ws, int ch, long long hi,
   if (lo) atomicAdd(&w[2 * ch + 1], (unsigned long long)lo);
 }
 __device__ __forceinline__ void dg_dbias_ws_finish(float* ws, int bias_mod, float* dbias) {
+  if (!dg_block_ticket_last(dg_dbias_ws_ticket(ws), gridDim.x * gridDim.y * gridDim.z)) return;
   unsigned long long* w = (unsigned long long*)ws;
-  __shared__ unsigned s_dbias_ticket;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  const unsigned nblk = gridDim.x * gridDim.y * gridDim.z;
   const unsigned nthr = blockDim.x * blockDim.y * blockDim.z;
   const unsigned t = threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z);
-  if (t == 0) s_dbias_ticket = atomicAdd((unsigned*)&w[DG_DBIAS_WS_WORDS - 1], 1u);
-  __syncthreads();
-  if (s_dbias_ticket != nblk - 1) return;
   for (int i = (int)t; i < bias_mod; i += (int)nthr) {
     const long long hi = (long long)atomicExch(&w[2 * i], 0ull), lo = (long long)atomicExch(&w[2 * i + 1], 0ull);
     if (hi | lo) atomicAdd(&dbias[i], dg_fix2_value(hi, lo));
   }
-  if (t == 0) atomicExch((unsigned*)&w[DG_DBIAS_WS_WORDS - 1], 0u);
 }
 
 // tanh for the depth head (Generator.forward, models/gans/dcgan_eqlr.py:71) in ~17 VALU instructions: libm's tanhf made

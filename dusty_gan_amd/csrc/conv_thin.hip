@@ -158,26 +158,13 @@ __global__ __launch_bounds__(256) void thin_smallk_kernel(ConvP p, int tiles_x, 
 #pragma unroll
       for (int r = 0; r < 16; ++r) v += part[r * 64 + tid];
       v *= p.rowscale ? p.rowscale[b] : 1.f;
-      if (p.dbias_ws && fabsf(v) < 2147483000.f) {
-        unsigned long long* w = (unsigned long long*)p.dbias_ws;
-        atomicAdd(&w[tid], (unsigned long long)__double2ll_rn((double)v * 4294967296.0));
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (memory-side atomics acknowledged before the ticket is drawn)
-      } else {
-        atomicAdd(&p.dbias[(n_base + tid) % p.bias_mod], v);
-      }
+      long long q;
+      if (p.dbias_ws && dg_fix1(v, q)) atomicAdd((unsigned long long*)p.dbias_ws + tid, (unsigned long long)q);
+      else atomicAdd(&p.dbias[(n_base + tid) % p.bias_mod], v);
     }
-    if (p.dbias_ws) {
-      __shared__ unsigned s_ticket;
-      __syncthreads();
-      if (tid == 0) s_ticket = atomicAdd((unsigned*)((unsigned long long*)p.dbias_ws + 64), 1u);
-      __syncthreads();
-      if (s_ticket == gridDim.x - 1 && tid < 64) {
-        unsigned long long* w = (unsigned long long*)p.dbias_ws;
-        const long long tot = (long long)atomicExch(&w[tid], 0ull);
-        atomicAdd(&p.dbias[(n_base + tid) % p.bias_mod], (float)((double)tot * (1.0 / 4294967296.0)));
-        if (tid == 0) atomicExch((unsigned*)(w + 64), 0u);
-      }
-    }
+    if (p.dbias_ws && dg_block_ticket_last(dg_thin_ws_ticket(p.dbias_ws), gridDim.x) && tid < 64)
+      atomicAdd(&p.dbias[(n_base + tid) % p.bias_mod],
+                dg_fix1_value((long long)atomicExch((unsigned long long*)p.dbias_ws + tid, 0ull)));
   }
 }
 
@@ -1603,14 +1590,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CP == 2 ? 3
         const unsigned mine = (gridDim.x - slot + DG_DBIAS_SLOTS - 1) / DG_DBIAS_SLOTS;   // blocks that use this slot
         float* w = p.dbias_ws + slot * DG_DBIAS_SLOT_FLOATS;
         atomicAdd(&w[tid], s_db[tid]);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // (acknowledged memory-side; a fence would write back L2)
-        unsigned t = 0;
-        if (tid == 0) t = atomicAdd((unsigned*)&w[64], 1u);
-        t = __builtin_amdgcn_readfirstlane(t);
-        if (t == mine - 1) {
-          atomicAdd(&p.dbias[tid % p.bias_mod], atomicExch(&w[tid], 0.f));
-          if (tid == 0) atomicExch((unsigned*)&w[64], 0u);
-        }
+        if (dg_wave_ticket_last(dg_dbias_slot_ticket(w), mine)) atomicAdd(&p.dbias[tid % p.bias_mod], atomicExch(&w[tid], 0.f));
       } else {
         atomicAdd(&p.dbias[tid % p.bias_mod], s_db[tid]);
       }

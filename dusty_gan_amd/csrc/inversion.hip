@@ -64,14 +64,11 @@ __global__ __launch_bounds__(IL_THREADS) void inv_loss_grad_kernel(const float* 
     loss[b] = s / msum[b];
     return;
   }
-  // the partial goes to memory-side (atomic exchange), the ticket after it is acknowledged; the last block of the sample
-  // adds the partials in chunk order and leaves its ticket zero
+  // the partial goes to memory-side (atomic exchange); the last block of the sample adds the partials in chunk order
   atomicExch(&parts[(long)b * nch + blockIdx.x], s);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (atomicAdd(&tickets[b], 1u) != (unsigned)nch - 1) return;
+  if (!dg_ticket_last(&tickets[b], nch)) return;
   float tot = 0.f;
   for (int c = 0; c < nch; ++c) tot += atomicExch(&parts[(long)b * nch + c], 0.f);
-  atomicExch(&tickets[b], 0u);
   loss[b] = tot / msum[b];
 }
 
@@ -174,13 +171,7 @@ __global__ __launch_bounds__(SA_THREADS) void sphere_adam_kernel(SphereArgs a) {
   }
   if (a.prime) return;
   // the step index advances once every row has read it: the last row's workgroup to finish (ticket) adds one
-  if (tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (atomicAdd(a.ticket, 1u) == (unsigned)a.B - 1) {
-      atomicExch(a.ticket, 0u);
-      atomicAdd(a.step, 1ull);
-    }
-  }
+  if (tid == 0 && dg_ticket_last(a.ticket, a.B)) atomicAdd(a.step, 1ull);
 }
 
 constexpr int DM_THREADS = 1024;

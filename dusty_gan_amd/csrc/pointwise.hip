@@ -915,33 +915,25 @@ __global__ __launch_bounds__(256) void head_post_bwd4_kernel(const float* __rest
     if (threadIdx.x == 0) {
       if (bias_ws && gridDim.x > 1) {
         // Round 5: the staged sums are 32.32 FIXED POINT (integer adds commute: the total no longer depends on the order in
-        // which blocks and samples arrive - common.h dg_acc_add has the argument).  Two levels, as before: the blocks of a
+        // which blocks and samples arrive - common.h has the protocol and its argument).  Two levels, as before: the blocks of a
         // sample add into that sample's slot; the last block of a sample (ticket) moves the slot's totals, still integers,
         // into the launch's accumulators (upper half of slot 0) and takes a second ticket; the last SAMPLE converts and adds
         // each head's total to dbias once.  Everything is left zero.
-        unsigned long long* w = (unsigned long long*)(bias_ws + (long)b * 1024);   // 4 KB apart
-        unsigned long long* gacc = (unsigned long long*)(bias_ws + 512);            // (slot 0, bytes 2048 ..)
+        unsigned long long* w = (unsigned long long*)(bias_ws + (long)b * DG_BIAS_WS_SAMPLE_FLOATS);
+        unsigned long long* gacc = (unsigned long long*)(bias_ws + DG_BIAS_WS_ACC);
         const float sv[3] = {s0, s1, s2};
-        bool odd = false;
 #pragma unroll
         for (int h = 0; h <= arch; ++h) {
-          if (!(fabsf(sv[h]) < 2147483000.f)) { atomicAdd(&dbias[h], sv[h]); odd = true; }
-          else atomicAdd(&w[h], (unsigned long long)__double2ll_rn((double)sv[h] * 4294967296.0));
+          long long q;
+          if (dg_fix1(sv[h], q)) atomicAdd(&w[h], (unsigned long long)q);
+          else atomicAdd(&dbias[h], sv[h]);
         }
-        (void)odd;
-        // the adds above before the ticket: they are acknowledged from memory-side when vmcnt drains (a __threadfence()
-        // here is buffer_wbl2 - a write-back of the megabytes of gradient this kernel has just stored, per block)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (atomicAdd((unsigned*)&w[3], 1u) == gridDim.x - 1) {
+        if (dg_ticket_last(dg_bias_ws_ticket(w), gridDim.x)) {
 #pragma unroll
           for (int h = 0; h <= arch; ++h) atomicAdd(&gacc[h], atomicExch(&w[h], 0ull));
-          atomicExch((unsigned*)&w[3], 0u);
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          if (atomicAdd((unsigned*)&gacc[3], 1u) == gridDim.y - 1) {
+          if (dg_ticket_last(dg_bias_ws_ticket(gacc), gridDim.y)) {
 #pragma unroll
-            for (int h = 0; h <= arch; ++h)
-              atomicAdd(&dbias[h], (float)((double)(long long)atomicExch(&gacc[h], 0ull) * (1.0 / 4294967296.0)));
-            atomicExch((unsigned*)&gacc[3], 0u);
+            for (int h = 0; h <= arch; ++h) atomicAdd(&dbias[h], dg_fix1_value((long long)atomicExch(&gacc[h], 0ull)));
           }
         }
       } else {
