@@ -94,7 +94,7 @@ XSUM_PARTS = 8   # DG_XSUM_PARTS of include/dusty_gan_hip.h
 class DgFetch(C.Structure):
     _fields_ = [("pol", C.c_void_p), ("mask", C.c_void_p), ("pool_ctr", C.c_void_p), ("npool", C.c_int),
                 ("min_depth", C.c_float), ("max_depth", C.c_float), ("drop_const", C.c_float), ("B", C.c_int), ("HW", C.c_long),
-                ("out", C.c_void_p), ("parts", C.c_void_p)]
+                ("out", C.c_void_p), ("parts", C.c_void_p), ("nslab", C.c_long), ("flip_tab", C.c_void_p)]
 
 
 class DgAugSet(C.Structure):
@@ -166,6 +166,8 @@ PROTOTYPES = {
     "dg_head_post_bwd_aug": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _F, _F, _I, _I, _I, _F, _F, _P, _P, _P,
                              _I, _P, _P],
     "dg_fetch_reals_pool_sum": [_P, _P, _P, _I, _F, _F, _F, _I, _L, _P, _P, _P],
+    "dg_fetch_reals_resident_sum": [_P, _P, _L, _P, _F, _F, _F, _I, _L, _P, _P, _P],
+    "dg_resident_gather": [_P, _L, _I, _L, _L, _P, _P, _P, _P],
     "dg_nsgan_d": [_P, _P, _I, _F, _P, _P, _P, _P],
     "dg_nsgan_g": [_P, _I, _F, _P, _P, _P],
     "dg_nsgan_d_step": [_P, _P, _I, _F, _P, _P, _P, _P, _P, _P],

@@ -626,40 +626,67 @@ __device__ __forceinline__ float prologue_fetch_px(float pol, float m, float min
   inv = inv * 2.f - 1.f;
   return m * inv + (1.f - m) * drop_const;
 }
+// one fetch block's sweep of `chunk` pixels; kDerived: `mask` is not read, the validity is pol > 0 (a resident store keeps no
+// mask: datasets/resident.py states why that is the stored mask bit for bit)
+template <bool kDerived>
+__device__ __forceinline__ float prologue_fetch_sweep(const float* pol, const float* mask, float* out, long chunk,
+                                                      const DgFetch& f) {
+  float acc = 0.f;
+  constexpr int U = 4;                                   // four trips' loads in flight per lane (8 x 16 bytes)
+  for (long k0 = (long)threadIdx.x * 4; k0 < chunk; k0 += U * 1024) {
+    float4 p4[U], m4[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long k = k0 + u * 1024;
+      if (k < chunk) {
+        p4[u] = *(const float4*)(pol + k);
+        if (kDerived) {
+          m4[u] = make_float4(p4[u].x > 0.f ? 1.f : 0.f, p4[u].y > 0.f ? 1.f : 0.f, p4[u].z > 0.f ? 1.f : 0.f,
+                              p4[u].w > 0.f ? 1.f : 0.f);
+        } else {
+          m4[u] = *(const float4*)(mask + k);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long k = k0 + u * 1024;
+      if (k >= chunk) break;
+      float4 o;
+      o.x = prologue_fetch_px(p4[u].x, m4[u].x, f.min_depth, f.max_depth, f.drop_const);
+      o.y = prologue_fetch_px(p4[u].y, m4[u].y, f.min_depth, f.max_depth, f.drop_const);
+      o.z = prologue_fetch_px(p4[u].z, m4[u].z, f.min_depth, f.max_depth, f.drop_const);
+      o.w = prologue_fetch_px(p4[u].w, m4[u].w, f.min_depth, f.max_depth, f.drop_const);
+      *(float4*)(out + k) = o;
+      acc += (o.x + o.y) + (o.z + o.w);
+    }
+  }
+  return acc;
+}
 __global__ __launch_bounds__(256) void step_prologue_kernel(PrologueZero z, PrologueDraws dr, PrologueFetch fe) {
   if (fe.blocks > 0 && (int)blockIdx.x >= fe.first_block) {
     __shared__ float red[16];
     const DgFetch& f = fe.f;
     const int j = (int)blockIdx.x - fe.first_block;
-    const float* pol = f.pol;
-    const float* mask = f.mask;
-    if (f.pool_ctr) {
-      const long off = (long)(*f.pool_ctr % (unsigned long long)f.npool) * ((long)f.B * f.HW);
-      pol += off;
-      mask += off;
-    }
     const long i0 = (long)j * fe.chunk;
-    float acc = 0.f;
-    constexpr int U = 4;                                   // four trips' loads in flight per lane (8 x 16 bytes)
-    for (long k0 = (long)threadIdx.x * 4; k0 < fe.chunk; k0 += U * 1024) {
-      float4 p4[U], m4[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const long k = k0 + u * 1024;
-        if (k < fe.chunk) { p4[u] = *(const float4*)(pol + i0 + k); m4[u] = *(const float4*)(mask + i0 + k); }
+    float acc;
+    if (f.nslab > 0) {
+      // resident store: slab (*ctr % nslab) of the epoch, each sample's variant from the flip table of the epoch's parity.  The
+      // block's DG_XSUM_PARTS-th of one sample is a contiguous run of that sample's stored image.
+      const unsigned long long ctr = *f.pool_ctr, ns = (unsigned long long)f.nslab;
+      const long row = (long)(ctr % ns) * f.B + j / DG_XSUM_PARTS;
+      const long var = f.flip_tab ? (long)f.flip_tab[(long)((ctr / ns) & 1ull) * f.nslab * f.B + row] : 0;
+      const float* pol = f.pol + (var * f.nslab * f.B + row) * f.HW + (long)(j % DG_XSUM_PARTS) * fe.chunk;
+      acc = prologue_fetch_sweep<true>(pol, nullptr, f.out + i0, fe.chunk, f);
+    } else {
+      const float* pol = f.pol;
+      const float* mask = f.mask;
+      if (f.pool_ctr) {
+        const long off = (long)(*f.pool_ctr % (unsigned long long)f.npool) * ((long)f.B * f.HW);
+        pol += off;
+        mask += off;
       }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const long k = k0 + u * 1024;
-        if (k >= fe.chunk) break;
-        float4 o;
-        o.x = prologue_fetch_px(p4[u].x, m4[u].x, f.min_depth, f.max_depth, f.drop_const);
-        o.y = prologue_fetch_px(p4[u].y, m4[u].y, f.min_depth, f.max_depth, f.drop_const);
-        o.z = prologue_fetch_px(p4[u].z, m4[u].z, f.min_depth, f.max_depth, f.drop_const);
-        o.w = prologue_fetch_px(p4[u].w, m4[u].w, f.min_depth, f.max_depth, f.drop_const);
-        *(float4*)(f.out + i0 + k) = o;
-        acc += (o.x + o.y) + (o.z + o.w);
-      }
+      acc = prologue_fetch_sweep<false>(pol + i0, mask + i0, f.out + i0, fe.chunk, f);
     }
     const float sblk = dg_block_sum(acc, red);
     if (threadIdx.x == 0) f.parts[j] = sblk;
@@ -903,9 +930,12 @@ static int step_prologue_impl(float* const* ptrs, const long* counts, int k, con
   PrologueFetch fe{};
   if (fetch) {
     const DgFetch& f = *fetch;
-    if (!f.pol || !f.mask || !f.out || !f.parts || f.B <= 0 || f.HW <= 0 || (f.pool_ctr && f.npool <= 0)) return DG_EINVAL;
+    const bool resident = f.nslab > 0;
+    if (!f.pol || !f.out || !f.parts || f.B <= 0 || f.HW <= 0 || f.nslab < 0) return DG_EINVAL;
+    if (resident ? !f.pool_ctr : (!f.mask || (f.pool_ctr && f.npool <= 0))) return DG_EINVAL;
     // 16-byte accesses, whole 1024-pixel sweeps per block, DG_XSUM_PARTS blocks per sample
-    if (f.HW % (1024L * DG_XSUM_PARTS) != 0 || (((size_t)f.pol | (size_t)f.mask | (size_t)f.out) & 15) != 0) return DG_EUNSUPPORTED;
+    if (f.HW % (1024L * DG_XSUM_PARTS) != 0 || (((size_t)f.pol | (size_t)(resident ? nullptr : f.mask) | (size_t)f.out) & 15) != 0)
+      return DG_EUNSUPPORTED;
     fe.f = f;
     fe.chunk = f.HW / DG_XSUM_PARTS;
     fe.blocks = f.B * DG_XSUM_PARTS;

@@ -1676,6 +1676,53 @@ __global__ __launch_bounds__(256) void fetch_reals_kernel(const float* __restric
   if (threadIdx.x == 0) dg_acc_add(&xsum[i0 / HW], sblk, (unsigned)(HW / chunk), g_det);
 }
 
+// fetch_reals_kernel's summing form on a resident scan store (DgFetch's resident form, include/dusty_gan_hip.h): the block's
+// `chunk` pixels of one sample, the batch and the sample's stored variant picked on the device; the mask is pol > 0
+// (datasets/resident.py).  Same per-lane order and block sum as fetch_reals_kernel: the sums are dg_fetch_reals_sum's bits.
+__global__ __launch_bounds__(256) void fetch_reals_resident_kernel(const float* __restrict__ store,
+                                                                   const unsigned long long* __restrict__ pool_ctr, long nslab,
+                                                                   const unsigned char* __restrict__ flip_tab, float min_d,
+                                                                   float max_d, float drop_const, int B, long HW,
+                                                                   float* __restrict__ out, float* __restrict__ xsum, int chunk) {
+  __shared__ float red[16];
+  const long i0 = (long)blockIdx.x * chunk, b = i0 / HW;
+  const unsigned long long ctr = *pool_ctr, ns = (unsigned long long)nslab;
+  const long row = (long)(ctr % ns) * B + b;
+  const long var = flip_tab ? (long)flip_tab[(long)((ctr / ns) & 1ull) * nslab * B + row] : 0;
+  const float* pol = store + (var * nslab * B + row) * HW + (i0 - b * HW);
+  float acc = 0.f;
+#pragma unroll 4
+  for (int k = threadIdx.x; k < chunk; k += 256) {
+    const float p = pol[k];
+    const float v = fetch_real_px(p, p > 0.f ? 1.f : 0.f, min_d, max_d, drop_const);
+    out[i0 + k] = v;
+    acc += v;
+  }
+  const float sblk = dg_block_sum(acc, red);
+  if (threadIdx.x == 0) dg_acc_add(&xsum[b], sblk, (unsigned)(HW / chunk), g_det);
+}
+
+// batch `slab` of a resident store as {depth, mask}: V consecutive pixels of one sample per lane (V = 4: 16-byte accesses)
+template <int V>
+__global__ __launch_bounds__(256) void resident_gather_kernel(const float* __restrict__ store, long nslab, int B, long HW,
+                                                              long slab, const unsigned char* __restrict__ flip,
+                                                              float* __restrict__ depth, float* __restrict__ mask) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * HW / V) return;
+  const long e = i * V, b = e / HW;
+  const long var = flip ? (long)flip[b] : 0;
+  const float* src = store + (var * nslab + slab) * (long)B * HW + e;   // sample (var, slab B + b), pixel e - b HW
+  if constexpr (V == 4) {
+    const float4 p = *(const float4*)src;
+    *(float4*)(depth + e) = p;
+    *(float4*)(mask + e) = make_float4(p.x > 0.f ? 1.f : 0.f, p.y > 0.f ? 1.f : 0.f, p.z > 0.f ? 1.f : 0.f, p.w > 0.f ? 1.f : 0.f);
+  } else {
+    const float p = *src;
+    depth[e] = p;
+    mask[e] = p > 0.f ? 1.f : 0.f;
+  }
+}
+
 // y = a * x
 __global__ void scale_kernel(const float* __restrict__ x, float a, long n, float* __restrict__ y) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2197,6 +2244,30 @@ int dg_fetch_reals_pool_sum(const float* pol_pool, const float* mask_pool, const
   const int chunk = sum_chunk(HW);
   fetch_reals_kernel<<<nblk((long)B * HW, chunk), 256, 0, s>>>(pol_pool, mask_pool, min_depth, max_depth, drop_const,
                                                                 (long)B * HW, out, xsum, HW, chunk, pool_ctr, npool);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
+
+int dg_fetch_reals_resident_sum(const float* store, const unsigned long long* pool_ctr, long nslab,
+                                const unsigned char* flip_tab, float min_depth, float max_depth, float drop_const, int B,
+                                long HW, float* out, float* xsum, void* s_) {
+  if (!store || !pool_ctr || !out || !xsum || nslab < 1 || B <= 0 || HW <= 0) return DG_EINVAL;
+  if (HW % 256 != 0) return DG_EUNSUPPORTED;
+  const int chunk = sum_chunk(HW);
+  fetch_reals_resident_kernel<<<nblk((long)B * HW, chunk), 256, 0, (hipStream_t)s_>>>(
+      store, pool_ctr, nslab, flip_tab, min_depth, max_depth, drop_const, B, HW, out, xsum, chunk);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
+
+int dg_resident_gather(const float* store, long nslab, int B, long HW, long slab, const unsigned char* flip, float* depth,
+                       float* mask, void* s_) {
+  if (!store || !depth || !mask || nslab < 1 || B <= 0 || HW <= 0 || slab < 0 || slab >= nslab) return DG_EINVAL;
+  hipStream_t s = (hipStream_t)s_;
+  if (HW % 4 == 0 && (((size_t)store | (size_t)depth | (size_t)mask) & 15) == 0)
+    resident_gather_kernel<4><<<nblk((long)B * HW / 4), 256, 0, s>>>(store, nslab, B, HW, slab, flip, depth, mask);
+  else
+    resident_gather_kernel<1><<<nblk((long)B * HW), 256, 0, s>>>(store, nslab, B, HW, slab, flip, depth, mask);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }

@@ -1,4 +1,5 @@
 """Dataset registry -- reference: datasets/__init__.py:4-27 (same names, same NotImplementedError behaviour)."""
+from .resident import ResidentScanLoader  # noqa: F401
 from .scans import KITTIOdometry, ScanLoader, SparseMPO  # noqa: F401
 
 

@@ -398,11 +398,17 @@ class Trainer:
                                           min_depth=cfg.dataset.min_depth, max_depth=cfg.dataset.max_depth)
             self.loader = cycle(self.dataset)
         else:
-            from ..datasets import ScanLoader, define_dataset
+            from ..datasets import ResidentScanLoader, ScanLoader, define_dataset
             self.dataset = define_dataset(self.cfg.dataset, phase="train")  # NotImplementedError for unknown names
-            self._scan_loader = ScanLoader(self.dataset, self.local_batch, self.device, world=_world(), rank=_rank(),
-                                           num_workers=int(local_cfg["num_workers"] if isinstance(local_cfg, dict)
-                                                           else local_cfg.num_workers))
+            nw = int(local_cfg["num_workers"] if isinstance(local_cfg, dict) else local_cfg.num_workers)
+            if self.cfg.dataset.get("resident", False):
+                # the rank's shard built in HBM once; the step picks each batch by the device-side counter (datasets/resident.py)
+                self._scan_loader = ResidentScanLoader(self.dataset, self.local_batch, self.device, world=_world(),
+                                                       rank=_rank(), num_workers=nw,
+                                                       max_gb=self.cfg.dataset.get("resident_max_gb", None))
+            else:
+                self._scan_loader = ScanLoader(self.dataset, self.local_batch, self.device, world=_world(), rank=_rank(),
+                                               num_workers=nw)
             self.loader = cycle(self._scan_loader)
 
         # losses (reference :104-113)
@@ -460,7 +466,7 @@ class Trainer:
         self._geng = None
         self._pending = None
         self._dev_scal = None
-        self._pool_ctr = None   # device-resident loader position of the synthetic pool (dg_fetch_reals_pool_sum)
+        self._pool_ctr = None   # device-resident loader position of the synthetic pool or the resident store
         self._fetch_in_prologue = os.environ.get("DUSTY_GAN_FETCH_IN_PROLOGUE", "1") != "0"   # (A/B switch, tests)
         self._pool_host = 0     # its host mirror: checked against batches_drawn before every graph step
         # the logged scalars leave the device with the step's last launch, into a ring of mapped pinned host memory
@@ -555,8 +561,18 @@ class Trainer:
             ra.advance(2 * n_sets * B)
         return jobs, advance
 
+    def _resident(self):
+        """the resident scan store (datasets/resident.py), or None"""
+        from ..datasets.resident import ResidentScanLoader
+        inner = getattr(self, "_scan_loader", None)
+        return inner if isinstance(inner, ResidentScanLoader) else None
+
     def _pooled(self):
-        """the loader is the device-resident synthetic pool and its batches can be picked by a device-side index"""
+        """the loader is device-resident - the synthetic pool, or a resident scan store at a shape the prologue fetch takes (the
+        others replay on static copies of the gathered batch) - and its batches can be picked by a device-side index"""
+        res = self._resident()
+        if res is not None:
+            return res.prologue_eligible()
         ds = getattr(self, "dataset", None)
         return (isinstance(ds, SyntheticLiDAR) and getattr(ds, "pool_depth", None) is not None
                 and (self.H * self.W) % 256 == 0)
@@ -565,9 +581,10 @@ class Trainer:
         """fetch_reals as the first launch of a step: the step's accumulator arena is opened first, so the per-sample sums
         the kernel produces beside x_real survive until DiffAugment reads them.  pooled: `raw_batch` is the batch the
         synthetic loader just yielded (number batches_drawn - 1); the kernel picks that same batch ON THE DEVICE from the
-        pool by a counter the step advances (dg_fetch_reals_pool_sum), so a hipGraph replay needs no copy of it."""
+        pool by a counter the step advances (dg_fetch_reals_pool_sum), so a hipGraph replay needs no copy of it.  The resident
+        scan store is read the same way: slab (counter % batches per epoch), flips from the epoch's table (datasets/resident.py)."""
         if pooled:
-            ds = self.dataset
+            ds, res = self.dataset, self._resident()
             if self._pool_ctr is None:
                 # (the batch this call fetches: the last one drawn, or - an accumulated step draws its num_accumulation batches
                 #  up front - the first of those)
@@ -576,8 +593,11 @@ class Trainer:
                 self._pool_host = first
             L.Counters.flush_if(self._pool_ctr)
             x = None
-            job = (self.lidar.fetch_job(ds.pool_depth, ds.pool_mask, self._pool_ctr, float(self.cfg.model.gen.drop_const))
-                   if self._fetch_in_prologue else None)
+            dc = float(self.cfg.model.gen.drop_const)
+            job = None
+            if self._fetch_in_prologue:
+                job = (res.fetch_job(self.lidar, self._pool_ctr, dc) if res is not None
+                       else self.lidar.fetch_job(ds.pool_depth, ds.pool_mask, self._pool_ctr, dc))
             if job is not None:
                 # round 6: the fetch rides on the step's first launch (arena + gradient zero-fill + the draws); its per-sample
                 # sums leave as XSUM_PARTS partials per sample (nothing that launch would have to zero first).  A further
@@ -590,8 +610,8 @@ class Trainer:
             else:
                 if begin:
                     self._begin_step(draw_B=self.local_batch)
-                x = self.lidar.fetch_reals_pool(ds.pool_depth, ds.pool_mask, self._pool_ctr,
-                                                float(self.cfg.model.gen.drop_const))
+                x = (res.fetch_reals_pool(self.lidar, self._pool_ctr, dc) if res is not None
+                     else self.lidar.fetch_reals_pool(ds.pool_depth, ds.pool_mask, self._pool_ctr, dc))
             L.Counters.add(self._pool_ctr, 1)   # (queued: applied with the step's other counters, inside the graph)
             if not torch.cuda.is_current_stream_capturing():
                 self._pool_host += 1            # (host mirror of the device index; a capture executes nothing)
@@ -1216,6 +1236,9 @@ class Trainer:
                 L.Counters.flush_if(self._pool_ctr)
                 self._pool_host = self.batches_drawn - self.n_acc
                 self._pool_ctr.fill_(self._pool_host)
+            if pooled and self._resident() is not None:
+                # the flip tables of the epochs this step's micro-batches fall in, written before anything is launched
+                self._resident().ensure_tables(self.batches_drawn - self.n_acc, self.batches_drawn - 1)
         mbs = batch if isinstance(batch, list) else [batch]
 
         def fetch_all(srcs):   # every micro-batch's fetch_reals at the head of the step (the first one opens the arena)
@@ -1469,9 +1492,10 @@ class Trainer:
         self.batches_drawn = n
         self._pool_ctr = None   # the device-side pool index is re-derived from batches_drawn at the next pooled fetch
         src = getattr(self, "dataset", None)
+        from ..datasets.resident import ResidentScanLoader
         from ..datasets.scans import ScanLoader
         inner = getattr(self, "_scan_loader", None)
-        if isinstance(inner, ScanLoader):
+        if isinstance(inner, (ScanLoader, ResidentScanLoader)):   # (either resumes the other's checkpoint: same position)
             per = len(inner)
             inner.epoch, inner.skip = n // per, n % per
         elif isinstance(src, SyntheticLiDAR):

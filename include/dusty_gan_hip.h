@@ -583,9 +583,24 @@ typedef struct DgFetch {
   long HW;
   float* out;                           /* [B][HW] */
   float* parts;                         /* [B][DG_XSUM_PARTS] */
+  /* the resident form (nslab > 0; all zero = the pool form above): pol = a scan split's store [nvar][nslab B][HW] in sampler
+   * order (variant 1 = the horizontally flipped sample), mask unused (derived as pol > 0, see datasets/resident.py), npool
+   * unused.  Batch = slab (*pool_ctr % nslab); sample b of it reads variant flip_tab[((*pool_ctr / nslab) & 1) nslab B +
+   * slab B + b] - two per-sample flip tables, chosen by epoch parity - or variant 0 when flip_tab is NULL. */
+  long nslab;
+  const unsigned char* flip_tab;        /* [2][nslab B] {0, 1}, or NULL */
 } DgFetch;
 int dg_step_prologue_fetch(float* const* zero_ptrs, const long* zero_counts, int k, const DgDraw* draws, int ndraw,
                            const DgFetch* fetch, void* stream);
+/* the resident form of dg_fetch_reals_pool_sum (same arithmetic and per-block sums; the batch and its flips picked on the device
+ * as in DgFetch's resident form): fetch_reals of a step's further micro-batch where the fetch does not ride on the prologue */
+int dg_fetch_reals_resident_sum(const float* store, const unsigned long long* pool_ctr, long nslab,
+                                const unsigned char* flip_tab, float min_depth, float max_depth, float drop_const, int B,
+                                long HW, float* out, float* xsum, void* stream);
+/* batch `slab` of a resident store as the file loader yields it: depth [B][HW] = the stored polar depth of sample b's variant
+ * flip[b] (flip NULL: variant 0), mask [B][HW] = depth > 0 ? 1 : 0.  16-byte accesses where HW % 4 == 0. */
+int dg_resident_gather(const float* store, long nslab, int B, long HW, long slab, const unsigned char* flip, float* depth,
+                       float* mask, void* stream);
 int dg_aug_draw_dev(uint64_t seed, uint64_t stream_id, const unsigned long long* offset_dev, int B, int H, int W,
                     float* uf, int* qi, void* stream);
 /* Adam with the (0-based, already-completed) step count in device memory: this call is step *step_dev + 1 */
