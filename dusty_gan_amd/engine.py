@@ -7,6 +7,7 @@ device memory (flat parameter stores, workspaces) and nothing else.  See DESIGN.
 import ctypes as C
 import math
 import os
+import warnings
 from collections import OrderedDict
 
 import torch
@@ -67,6 +68,7 @@ class ParamStore:
         # name -> tensor for [tap][ci][co] (x2_cico) and [tap][co][ci] (x2_coci); rebuilt behind every shadow refresh
         self.x2 = False
         self.x2_cico, self.x2_coci = {}, {}
+        self._x2_key = None  # the fp32 shadows' pointers the twins were built for
 
     # -- views
     def view(self, name, buf=None):
@@ -166,7 +168,7 @@ class ParamStore:
         if not fat:
             return
         key = (self.shadow.data_ptr(),) + tuple(self.coci[name].data_ptr() for name, _ in fat)
-        if getattr(self, "_x2_key", None) != key:   # (first use, or the fp32 shadows moved: new twins, new registrations)
+        if self._x2_key != key:   # (first use, or the fp32 shadows moved: new twins, new registrations)
             self._drop_x2()
             self._x2_key = key
             for name, s in fat:
@@ -317,6 +319,39 @@ def wgrad_algorithmic(wmode, B, Hc, Wc, Ci, Co, aes, ges):
     return 2.0 * rows * Ci * Co * 16, rows * (fa * Ci * aes + fg * Co * ges) + 16 * Ci * Co * 4
 
 
+def _es(dt):
+    """bytes per element of a C-ABI dtype code (DG_BF16X2: a pair of bf16 halves)"""
+    return 2 if dt == L.DG_BF16 else 4
+
+
+def _conv_tag(p):
+    """shape tag of a DgConv in TRACE / PROFILE records"""
+    return f"mode{p.mode}adj{p.adj} B{p.B} {p.Hc}x{p.Wc} K{p.K} N{p.N}"
+
+
+def _wgrad_tag(p):
+    """shape tag of a DgWgrad in TRACE / PROFILE records"""
+    return f"wmode{p.wmode} B{p.B} {p.Hc}x{p.Wc} Ci{p.Ci} Co{p.Co}"
+
+
+def _wgrad_cost(p):
+    return wgrad_algorithmic(p.wmode, p.B, p.Hc, p.Wc, p.Ci, p.Co, _es(p.a_dtype), _es(p.g_dtype))
+
+
+def _launch(call, what, record):
+    """Issue one conv / wgrad launch: L.check(call(), what).  Under PROFILE (bench.py's instrumented pass) HIP events on the
+    launch stream go around this one kernel; record() -> (kernel family, FLOPs, bytes, tag) is evaluated only then."""
+    if PROFILE is None:
+        L.check(call(), what)
+        return
+    name, flops, nbytes, tag = record()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    L.check(call(), what)
+    e1.record()
+    PROFILE.append((name, flops, nbytes, e0, e1, tag))
+
+
 class WgradWorkspace:
     """Split-K partial tiles of the step's weight-gradient launches (DgWgrad.ws): the MFMA LDS-DMA kernel stores every
     split's [16][Ci][Co] partial here with plain stores, and `flush` sums them into the gradients with ONE
@@ -401,15 +436,10 @@ class WgradWorkspace:
             arr = (L.DgWgradReduce * len(chunk))()
             for a, (ws, dw, numel, splits, acc) in zip(arr, chunk):
                 a.ws, a.dw, a.numel, a.splits, a.accumulate = ws, dw, numel, splits, acc
-            if PROFILE is None:
-                L.check(L.lib().dg_wgrad_reduce(arr, len(chunk), L.stream_ptr()), "dg_wgrad_reduce")
-                continue
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            L.check(L.lib().dg_wgrad_reduce(arr, len(chunk), L.stream_ptr()), "dg_wgrad_reduce")
-            e1.record()
-            nbytes = sum(4 * numel * (splits + 1 + acc) for _, _, numel, splits, acc in chunk)
-            PROFILE.append(("wgrad_reduce_kernel", 0.0, nbytes, e0, e1, f"{len(chunk)} layers"))
+            def record():
+                nbytes = sum(4 * numel * (splits + 1 + acc) for _, _, numel, splits, acc in chunk)
+                return "wgrad_reduce_kernel", 0.0, nbytes, f"{len(chunk)} layers"
+            _launch(lambda: L.lib().dg_wgrad_reduce(arr, len(chunk), L.stream_ptr()), "dg_wgrad_reduce", record)
 
 
 class _PerStreamWorkspace:
@@ -466,7 +496,6 @@ def grads_ready():
     on another stream of this device mean that stream's gradients are incomplete - said out loud (round-4 advice)."""
     other = WGRAD_WS.pending_elsewhere()
     if other:
-        import warnings
         warnings.warn(f"engine.grads_ready(): {other} layer(s) have split-K partials pending on ANOTHER stream of this device; "
                       "call grads_ready() on the stream that ran their backward pass before reading those gradients")
     WGRAD_WS.flush()
@@ -584,7 +613,7 @@ class Ops:
         # THIS Ops: per engine, nothing process-wide)
         self.x3 = bool(x3) and dtype == torch.float32
         self.dt = L.dtype_code(dtype)
-        self.es = 2 if dtype == torch.bfloat16 else 4
+        self.es = _es(self.dt)
         # dg_conv / dg_wgrad `force`: a request code L.DG_FORCE_* (AUTO; the parity tests pin DIRECT, MFMA, THIN, the persistent
         # LOCKSTEP / PINGPONG[_SINGLE] convs, PROJ_STREAM, the WG_* weight-gradient kernels)
         self.force = L.DG_FORCE_AUTO
@@ -639,8 +668,7 @@ class Ops:
         p.B, p.Hc, p.Wc, p.K, p.N = B, Hc, Wc, K, N
         in_dt = self.dt if in_dt is None else in_dt
         out_dt = self.dt if out_dt is None else out_dt
-        ies = 2 if in_dt == L.DG_BF16 else 4
-        oes = 2 if out_dt == L.DG_BF16 else 4
+        ies, oes = _es(in_dt), _es(out_dt)
         p.in_ = L.ptr(x) + ies * x_off
         p.in_sb, p.in_sp, p.in_sk = x_strides
         p.out = L.ptr(out) + oes * out_off
@@ -660,8 +688,7 @@ class Ops:
         sum_parts = 0
         if tanh_sums is not None:
             p.tanh_sum_parts = L.ptr(tanh_sums)
-            pl = L.DgConvPlan()
-            L.check(self.lib.dg_conv_plan(C.byref(p), self._f, self.wg_cap, C.byref(pl)), "dg_conv_plan")
+            pl = self._conv_plan(p)
             sum_parts = pl.sum_parts if B * pl.sum_parts <= tanh_sums.numel() else 0
             if not sum_parts:
                 p.tanh_sum_parts = None
@@ -674,45 +701,45 @@ class Ops:
             if ws is None:
                 ws = Ops._dbias_ws[str(x.device)] = torch.zeros(L.DBIAS_WS_FLOATS, dtype=torch.float32, device=x.device)
             p.dbias_ws = L.ptr(ws)
+        # the plan of the descriptor as it is launched.  (The tanh_sums query above is not it: the launchers read tanh_sum_parts
+        # and the mask fields.  The deterministic dbias query is: dbias_part, filled behind it, is read by device code only.)
+        final = None
+
+        def plan():
+            nonlocal final
+            if final is None:
+                final = self._conv_plan(p)
+            return final
         db_rows = 0
         if dbias is not None and DETERMINISTIC:
-            pl = L.DgConvPlan()
-            L.check(self.lib.dg_conv_plan(C.byref(p), self._f, self.wg_cap, C.byref(pl)), "dg_conv_plan")
+            pl = plan()
             if pl.dbias_rows > 0:
                 part = WGRAD_WS.take(pl.dbias_rows * N, x.device)
                 if part is not None:
                     db_rows, p.dbias_part = pl.dbias_rows, part
         if TRACE is not None:
-            pl = L.DgConvPlan()
-            L.check(self.lib.dg_conv_plan(C.byref(p), self._f, self.wg_cap, C.byref(pl)), "dg_conv_plan")
-            TRACE.append(("conv", pl.family, pl.bm, pl.bn, pl.tiles, pl.workgroups, pl.tiles_per_wg,
-                          f"mode{mode}adj{adj} B{B} {Hc}x{Wc} K{K} N{N}", pl.thin_mfma,
+            pl = plan()
+            TRACE.append(("conv", pl.family, pl.bm, pl.bn, pl.tiles, pl.workgroups, pl.tiles_per_wg, _conv_tag(p), pl.thin_mfma,
                           (1 if p.mask_out else 0) | (pl.mask_bits & 2 if p.mask_in else 0)))
-        if PROFILE is None:
-            L.check(self.lib.dg_conv_ex(C.byref(p), self._f, self.wg_cap, L.stream_ptr()), "dg_conv_ex")
-            self._db_rows_done(p, db_rows, dbias, N, defer_db)
-            if x2_out is not None:
-                x2_pack(out, x2_out, out_off, B * N)
-            return sum_parts
-        # bench.py's instrumented pass: HIP events on the launch stream around this one kernel
-        pl = L.DgConvPlan()
-        L.check(self.lib.dg_conv_plan(C.byref(p), self._f, self.wg_cap, C.byref(pl)), "dg_conv_plan")
-        name = {L.DG_CONV_FAMILY_THIN: "conv_thin_kernel", L.DG_CONV_FAMILY_DIRECT: "conv_direct_kernel"}.get(pl.family,
-                                                                                                             "conv_mfma_kernel")
-        wes = 2 if p.w_dtype == L.DG_BF16 else 4
-        mb = 0
-        if p.mask_out or p.mask_in:
-            mb = pl.mask_bits if p.mask_in else 1  # (mask_out behind a kernel without it: the packing launch writes the same bytes)
-        flops, nbytes = conv_algorithmic(mode, B, Hc, Wc, K, N, ies, oes, wes, epi == L.EPI_MASK, mb)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        L.check(self.lib.dg_conv_ex(C.byref(p), self._f, self.wg_cap, L.stream_ptr()), "dg_conv_ex")
-        e1.record()
-        PROFILE.append((name, flops, nbytes, e0, e1, f"mode{mode}adj{adj} B{B} {Hc}x{Wc} K{K} N{N}"))
+
+        def record():
+            pl = plan()
+            names = {L.DG_CONV_FAMILY_THIN: "conv_thin_kernel", L.DG_CONV_FAMILY_DIRECT: "conv_direct_kernel"}
+            mb = 0
+            if p.mask_out or p.mask_in:   # (mask_out behind a kernel without it: the packing launch writes the same bytes)
+                mb = pl.mask_bits if p.mask_in else 1
+            cost = conv_algorithmic(mode, B, Hc, Wc, K, N, ies, oes, _es(p.w_dtype), epi == L.EPI_MASK, mb)
+            return (names.get(pl.family, "conv_mfma_kernel"),) + cost + (_conv_tag(p),)
+        _launch(lambda: self.lib.dg_conv_ex(C.byref(p), self._f, self.wg_cap, L.stream_ptr()), "dg_conv_ex", record)
         self._db_rows_done(p, db_rows, dbias, N, defer_db)
         if x2_out is not None:
             x2_pack(out, x2_out, out_off, B * N)
         return sum_parts
+
+    def _conv_plan(self, p):
+        pl = L.DgConvPlan()
+        L.check(self.lib.dg_conv_plan(C.byref(p), self._f, self.wg_cap, C.byref(pl)), "dg_conv_plan")
+        return pl
 
     def _db_rows_done(self, p, rows, dbias, N, defer_db):
         """the launch left `rows` partial bias-gradient rows in the workspace: queue their sum onto dbias"""
@@ -738,31 +765,26 @@ class Ops:
                 and len(self._group) < self.GROUP_MAX and pl.ws_floats <= WgradWorkspace.FLOATS):
             # inside `with ops.grouped():` - the launch joins the group's ONE launch (dg_wgrad_group) at the end of the block:
             # its geometry (K split, workspace) is decided there, for the group as a whole
-            self._group.append((p, (wmode, B, Hc, Wc, Ci, Co), (a, g, rowscale), dw_ptr, int(accumulate)))
+            self._group.append((p, (a, g, rowscale), dw_ptr, int(accumulate)))
             return
         if pl is not None and pl.ws_floats > 0:
             p.ws = WGRAD_WS.take(pl.ws_floats, a.device)
         if TRACE is not None:
-            TRACE.append(("wgrad", self.lib.dg_wgrad_kernel_variant(C.byref(p), self._f),
-                          f"wmode{wmode} B{B} {Hc}x{Wc} Ci{Ci} Co{Co}", 0 if pl is None else pl.splits,
-                          0 if pl is None else pl.tap_pairs, bool(p.ws), g_mod))
-        if PROFILE is None:
-            L.check(self.lib.dg_wgrad(C.byref(p), accumulate, self._f, L.stream_ptr()), "dg_wgrad")
-        else:
-            v = self.lib.dg_wgrad_kernel_variant(C.byref(p), self._f)
-            name = {L.DG_WGRAD_VARIANT_THIN: "wgrad_thin_kernel", L.DG_WGRAD_VARIANT_THIN_MFMA: "wgrad_thin_kernel",
-                    L.DG_WGRAD_VARIANT_DIRECT: "wgrad_direct_kernel"}.get(v, "wgrad_mfma_kernel")
-            flops, nbytes = wgrad_algorithmic(wmode, B, Hc, Wc, Ci, Co, 2 if p.a_dtype == L.DG_BF16 else 4,
-                                              2 if p.g_dtype == L.DG_BF16 else 4)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            L.check(self.lib.dg_wgrad(C.byref(p), accumulate, self._f, L.stream_ptr()), "dg_wgrad")
-            e1.record()
-            PROFILE.append((name, flops, nbytes, e0, e1, f"wmode{wmode} B{B} {Hc}x{Wc} Ci{Ci} Co{Co}"))
+            TRACE.append(("wgrad", self.lib.dg_wgrad_kernel_variant(C.byref(p), self._f), _wgrad_tag(p),
+                          0 if pl is None else pl.splits, 0 if pl is None else pl.tap_pairs, bool(p.ws), g_mod))
+        self._wgrad_launch(p, accumulate)
         if p.ws:
             WGRAD_WS.add(p.ws, dw_ptr, (1 if wmode == 2 else 16) * Ci * Co, pl.splits, int(accumulate))
             if not defer:
                 WGRAD_WS.flush()
+
+    def _wgrad_launch(self, p, accumulate):
+        def record():
+            v = self.lib.dg_wgrad_kernel_variant(C.byref(p), self._f)
+            name = {L.DG_WGRAD_VARIANT_THIN: "wgrad_thin_kernel", L.DG_WGRAD_VARIANT_THIN_MFMA: "wgrad_thin_kernel",
+                    L.DG_WGRAD_VARIANT_DIRECT: "wgrad_direct_kernel"}.get(v, "wgrad_mfma_kernel")
+            return (name,) + _wgrad_cost(p) + (_wgrad_tag(p),)
+        _launch(lambda: self.lib.dg_wgrad(C.byref(p), accumulate, self._f, L.stream_ptr()), "dg_wgrad", record)
 
     GROUP_MAX = 4   # (GROUP_MAX of csrc/wgrad_mfma_dma.hip)
 
@@ -811,49 +833,31 @@ class Ops:
             for i in range(n):
                 L.check(self.lib.dg_wgrad_plan(C.byref(arr[i]), 1, self._f, C.byref(plans[i])), "dg_wgrad_plan")
         sizes = [(plans[i].ws_floats + 63) // 64 * 64 for i in range(n)]
-        base = WGRAD_WS.take(sum(sizes), items[0][2][0].device)
-        if base is None:     # (larger than the workspace cap: atomics onto dW, one launch each)
+        base = WGRAD_WS.take(sum(sizes), items[0][1][0].device)
+        if base is None:     # (larger than the workspace cap: atomics onto dW, one launch each; PROFILE has never timed these)
             for it in items:
-                L.check(self.lib.dg_wgrad(C.byref(it[0]), it[4], self._f, L.stream_ptr()), "dg_wgrad")
+                L.check(self.lib.dg_wgrad(C.byref(it[0]), it[3], self._f, L.stream_ptr()), "dg_wgrad")
             return
         off = 0
         for i in range(n):
             arr[i].ws = base + 4 * off
             off += sizes[i]
-        descs = [f"wmode{d[0]} B{d[1]} {d[2]}x{d[3]} Ci{d[4]} Co{d[5]}" for _, d, _, _, _ in items]
+        descs = [_wgrad_tag(it[0]) for it in items]
         if TRACE is not None:
             for i, it in enumerate(items):
                 TRACE.append(("wgrad", L.DG_WGRAD_VARIANT_DMA, descs[i], plans[i].splits, plans[i].tap_pairs, True, it[0].g_mod))
             if grouped:
                 TRACE.append(("wgrad_group", n, descs))
-
-        def algo(i):
-            p, (wmode, B, Hc, Wc, Ci, Co) = items[i][0], items[i][1]
-            return wgrad_algorithmic(wmode, B, Hc, Wc, Ci, Co, 2 if p.a_dtype == L.DG_BF16 else 4, 2 if p.g_dtype == L.DG_BF16 else 4)
         if grouped:
-            if PROFILE is None:
-                L.check(self.lib.dg_wgrad_group(arr, n, self._f, Ops.group_rounds, L.stream_ptr()), "dg_wgrad_group")
-            else:
-                fb = [algo(i) for i in range(n)]
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                L.check(self.lib.dg_wgrad_group(arr, n, self._f, Ops.group_rounds, L.stream_ptr()), "dg_wgrad_group")
-                e1.record()
-                PROFILE.append(("wgrad_mfma_kernel", sum(f for f, _ in fb), sum(b for _, b in fb), e0, e1, f"group of {n} layers"))
+            def record():
+                fb = [_wgrad_cost(it[0]) for it in items]
+                return "wgrad_mfma_kernel", sum(f for f, _ in fb), sum(b for _, b in fb), f"group of {n} layers"
+            _launch(lambda: self.lib.dg_wgrad_group(arr, n, self._f, Ops.group_rounds, L.stream_ptr()), "dg_wgrad_group", record)
         else:
-            for i in range(n):
-                if PROFILE is None:
-                    L.check(self.lib.dg_wgrad(C.byref(arr[i]), 1, self._f, L.stream_ptr()), "dg_wgrad")
-                    continue
-                f, b = algo(i)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                L.check(self.lib.dg_wgrad(C.byref(arr[i]), 1, self._f, L.stream_ptr()), "dg_wgrad")
-                e1.record()
-                PROFILE.append(("wgrad_mfma_kernel", f, b, e0, e1, descs[i]))
+            for i in range(n):   # (all on the LDS-DMA kernel: "wgrad_mfma_kernel" records)
+                self._wgrad_launch(arr[i], 1)
         for i, it in enumerate(items):
-            (wmode, B, Hc, Wc, Ci, Co) = it[1]
-            WGRAD_WS.add(arr[i].ws, it[3], 16 * Ci * Co, plans[i].splits, it[4])
+            WGRAD_WS.add(arr[i].ws, it[2], 16 * it[0].Ci * it[0].Co, plans[i].splits, it[3])
 
     def wgrad_takes_map(self, wmode, ring, B, Hc, Wc, Ci, Co, a, a_strides, g, g_strides, dw_ptr):
         """whether the kernel that would run this launch has the g-sample index map (DgWgrad.g_mod): the LDS-DMA kernel
@@ -878,9 +882,9 @@ class Ops:
         p.B, p.Hc, p.Wc, p.Ci, p.Co = B, Hc, Wc, Ci, Co
         a_dt = self.dt if a_dt is None else a_dt
         g_dt = self.dt if g_dt is None else g_dt
-        p.a = L.ptr(a) + (2 if a_dt == L.DG_BF16 else 4) * a_off
+        p.a = L.ptr(a) + _es(a_dt) * a_off
         p.a_sb, p.a_sp, p.a_sc = a_strides
-        p.g = L.ptr(g) + (2 if g_dt == L.DG_BF16 else 4) * g_off
+        p.g = L.ptr(g) + _es(g_dt) * g_off
         p.g_sb, p.g_sp, p.g_sc = g_strides
         p.dw, p.scale, p.rowscale = dw_ptr, scale, L.ptr(rowscale)
         p.a_dtype, p.g_dtype = a_dt, g_dt
@@ -905,6 +909,9 @@ class GEngine:
         self.x2_asked = bool(x2)
         self.x2 = self.x2_asked and self.ops.x3 and x2_eligible(cfg)
         self.ws_B = 0
+        self.chs = [cfg.ch[3], cfg.ch[2], cfg.ch[1], cfg.ch[0]]  # channels of a0..a3
+        self.ta = None    # tangent activations and their buffers (tangent_forward)
+        self._dzT = None  # grad_z's operand and result (grad_z_buffers)
 
     def alloc(self, B, device):
         if self.ws_B == B and self.a[0].device == device:
@@ -912,7 +919,7 @@ class GEngine:
         c = self.cfg
         T = self.dtype
         hw = [(c.h0 << i, c.w0 << i) for i in range(5)]  # grids of a0..a3 and the image
-        chs = [c.ch[3], c.ch[2], c.ch[1], c.ch[0]]
+        chs = self.chs
         self.grid = hw
         self.a = [torch.empty(B * hw[i][0] * hw[i][1] * chs[i], dtype=T, device=device) for i in range(4)]
         self.dp = [torch.empty_like(t) for t in self.a]  # gradients w.r.t. the pre-activations of a0..a3
@@ -957,34 +964,22 @@ class GEngine:
             st.enable_x2()
         st.refresh_shadows(self.dtype)
         sp = L.stream_ptr()
-        chs = [c.ch[3], c.ch[2], c.ch[1], c.ch[0]]
         if not z_ready:
             z = z.contiguous().float()
             L.check(lib.dg_cast(L.ptr(z), L.ptr(self.zT), o.dt, B * c.nz, sp), "dg_cast")
-        # Proj (dcgan_eqlr.py:6-16): GEMM [B,nz] x [N',nz]^T, N' = h0*w0*C3 in (y,x,c) order
-        Np = c.h0 * c.w0 * chs[0]
-        o.conv(L.MODE_GEMM, 0, 1, B, 1, 1, c.nz, Np, self.zT, (c.nz, 0, 1), self.a[0], (Np, 0, 1), st.sptr("proj_w"),
-               1.0 / math.sqrt(Np), L.EPI_LRELU, bias=st.fptr("proj_b"), bias_mod=chs[0])
-        # Up x3 (dcgan_eqlr.py:19-26)
+        self._proj_fwd(st, B, self.zT, self.a[0])
         for i in (1, 2, 3):
-            hc, wc = self.grid[i - 1]
-            ci, co = chs[i - 1], chs[i]
-            o.conv(L.MODE_UP, 0, c.ring, B, hc, wc, ci, co, self.a[i - 1], (hc * wc * ci, ci, 1), self.a[i],
-                   (4 * hc * wc * co, co, 1), L.ptr(st.coci[f"up{i}_w"]), 1.0 / math.sqrt(co * 16), L.EPI_LRELU,
-                   bias=st.fptr(f"up{i}_b"), bias_mod=co)
-        # Head (dcgan_eqlr.py:29-46), all heads in one pass, planar fp32 output
-        hc, wc = self.grid[3]
+            self._fwd(st, B, i, self.a[i - 1], self.a[i])
+        hc = self.grid[3][0]
         # (weight (tap, n = head, k = ci) in the fp32 master [tap][ci][co]: strides (ci co, 1, co))
-        frag = (st.up_frag("head_w", (chs[3] * c.nheads, 1, c.nheads), c.nheads, hc, 0)
-                if (c.ring and chs[3] == 64 and c.nheads <= 3) else None)
+        frag = (st.up_frag("head_w", (self.chs[3] * c.nheads, 1, c.nheads), c.nheads, hc, 0)
+                if (c.ring and self.chs[3] == 64 and c.nheads <= 3) else None)
         arch = ARCH_ID[c.arch]
         # the baseline generator's head (one channel, then torch.tanh, dcgan_eqlr.py:69-72): the thin matrix-core kernel applies
         # the tanh itself and stores the image's per-sample sums as partials (DgConv.tanh_sum_parts, round 6) - no head
         # post-processing launch; `depth` then IS gout
-        parts = o.conv(L.MODE_UP, 0, c.ring, B, hc, wc, chs[3], c.nheads, self.a[3], (hc * wc * chs[3], chs[3], 1), self.gout,
-                       (c.nheads * self.HW, 1, self.HW), L.ptr(st.coci["head_w"]), 1.0, L.EPI_LINEAR,
-                       bias=st.fptr("head_b"), bias_mod=c.nheads, out_dt=L.DG_F32, nscale=self.nscale, up_frag=frag,
-                       tanh_sums=self.dsum_parts if (arch == 0 and GEngine.head_tanh_fused) else None)
+        parts = self._fwd(st, B, 4, self.a[3], self.gout, up_frag=frag,
+                          tanh_sums=self.dsum_parts if (arch == 0 and GEngine.head_tanh_fused) else None)
         if parts:
             out = OrderedDict()
             out["depth"] = L.tag_sums(self.gout.view(B, 1, c.H, c.W), self.dsum_parts, parts=parts)
@@ -1013,6 +1008,67 @@ class GEngine:
             out["mask"] = self.mask
         return out
 
+    # ------------------------------------------------------------------ the layers' launches: each geometry written once
+    def _layer(self, i):
+        """Up_i (i = 1..3) or the Head (i = 4), from a[i-1]: parameter name, coarse grid, channels in / out, the (sample, pixel,
+        channel) strides of its input and of its output (the Head's: planar), eq-lr scale (the Head's is per channel: nscale)"""
+        hc, wc = self.grid[i - 1]
+        ci = self.chs[i - 1]
+        if i == 4:
+            return "head", hc, wc, ci, self.cfg.nheads, (hc * wc * ci, ci, 1), (self.cfg.nheads * self.HW, 1, self.HW), 1.0
+        co = self.chs[i]
+        return f"up{i}", hc, wc, ci, co, (hc * wc * ci, ci, 1), (4 * hc * wc * co, co, 1), 1.0 / math.sqrt(co * 16)
+
+    def _proj_fwd(self, st, B, src, dst, tangent=False):
+        """Proj (dcgan_eqlr.py:6-16): GEMM [B,nz] x [N',nz]^T, N' = h0*w0*C3 in (y,x,c) order"""
+        c = self.cfg
+        Np = c.h0 * c.w0 * self.chs[0]
+        kw = dict(aux=self.a[0]) if tangent else dict(bias=st.fptr("proj_b"), bias_mod=self.chs[0])
+        self.ops.conv(L.MODE_GEMM, 0, 1, B, 1, 1, c.nz, Np, src, (c.nz, 0, 1), dst, (Np, 0, 1), st.sptr("proj_w"),
+                      1.0 / math.sqrt(Np), L.EPI_MASK if tangent else L.EPI_LRELU, **kw)
+
+    def _fwd(self, st, B, i, src, dst, tangent=False, **head_kw):
+        """Up x3 (dcgan_eqlr.py:19-26) / Head (dcgan_eqlr.py:29-46: all heads in one pass, planar fp32 output).  tangent (as in
+        `_proj_fwd`): no bias, the saved leaky-relu mask of the layer's activation instead of the leaky-relu"""
+        name, hc, wc, ci, co, sa, so, s = self._layer(i)
+        kw = (dict(aux=self.a[i]) if i < 4 else {}) if tangent else dict(bias=st.fptr(name + "_b"), bias_mod=co)
+        if i == 4:
+            kw.update(out_dt=L.DG_F32, nscale=self.nscale, **head_kw)
+        epi = L.EPI_LINEAR if i == 4 else (L.EPI_MASK if tangent else L.EPI_LRELU)
+        return self.ops.conv(L.MODE_UP, 0, self.cfg.ring, B, hc, wc, ci, co, src, sa, dst, so, L.ptr(st.coci[name + "_w"]), s,
+                             epi, **kw)
+
+    def _gout(self, i, chain):
+        """the gradient at layer i's output as a conv / wgrad operand (tensor, strides, dtype code - None: the compute dtype) in
+        the gradient chain (draw, draw_pm, dp).  The Head's, bf16: the pixel-major copy feeds the two thin MFMA kernels"""
+        draw, draw_pm, dp = chain
+        if i < 4:
+            return dp[i], self._layer(i)[6], None
+        if draw_pm is not None:
+            return draw_pm, (self.HW * self.cp, self.cp, 1), None
+        return draw, self._layer(4)[6], L.DG_F32
+
+    def _wgrad(self, st, B, i, a, chain):
+        """layer i's weight gradient: input `a` (x) the chain's gradient at its output; deferred (WGRAD_WS)"""
+        name, hc, wc, ci, co, sa, _, s = self._layer(i)
+        g, sg, gdt = self._gout(i, chain)
+        self.ops.wgrad(1, self.cfg.ring, B, hc, wc, ci, co, a, sa, g, sg, st.fptr(name + "_w", st.grad), s, g_dt=gdt, defer=True)
+
+    def _bwd_data(self, st, B, i, chain, want_dbias):
+        """layer i's backward-data into chain dp[i-1]: the gradient w.r.t. the pre-activation of a[i-1], fused lrelu' mask
+        (+ the bias gradient of the layer below)"""
+        name, hc, wc, ci, co, sa, _, s = self._layer(i)
+        g, sg, gdt = self._gout(i, chain)
+        dbias = st.fptr(f"up{i - 1}_b" if i > 1 else "proj_b", st.grad) if want_dbias else None
+        self.ops.conv(L.MODE_S2, 1, self.cfg.ring, B, hc, wc, co, ci, g, sg, chain[2][i - 1], sa, st.sptr(name + "_w"), s,
+                      L.EPI_MASK, aux=self.a[i - 1], dbias=dbias, bias_mod=ci, in_dt=gdt, defer_db=True)
+
+    def _head_saved(self):
+        """what the head post-processing's backward kernels read of the forward pass: (gout, pixel noise, image noise, mask)"""
+        arch = ARCH_ID[self.cfg.arch]
+        return (L.ptr(self.gout), L.ptr(self.noise_pixel) if arch else None, L.ptr(self.noise_image) if arch == 2 else None,
+                L.ptr(self.mask) if arch else None)
+
     def proj_wgrad(self, st: ParamStore, dp0, zT, nb, accumulate=False):
         """Proj weight gradient dW[n'][k] = s * sum_b dp0[b][n'] z[b][k] over `nb` samples (the local batch, or the
         all-gathered global batch in data-parallel runs: utils/dist.py).  Plain stores unless accumulating."""
@@ -1036,14 +1092,11 @@ class GEngine:
                                         second_of=None)
         c, o, lib = self.cfg, self.ops, L.lib()
         B = ddepth.shape[0]
-        sp = L.stream_ptr()
-        chs = [c.ch[3], c.ch[2], c.ch[1], c.ch[0]]
         arch = ARCH_ID[c.arch]
         s_depth, s_conf = self.head_scales
-        head = (L.ptr(self.gout), L.ptr(self.noise_pixel) if arch else None, L.ptr(self.noise_image) if arch == 2 else None,
-                L.ptr(self.mask) if arch else None)
+        head = self._head_saved()
         tail = (s_depth, s_conf, None if self.draw_pm is not None else L.ptr(self.draw), st.fptr("head_b", st.grad),
-                L.ptr(self.draw_pm), self.cp, L.ptr(self.hp_ws), sp)
+                L.ptr(self.draw_pm), self.cp, L.ptr(self.hp_ws), L.stream_ptr())
         if isinstance(ddepth, AugGrad):  # DiffAugment's adjoint gather inside this launch: the upstream gradient is never written
             g = ddepth
             rc = lib.dg_head_post_bwd_aug(*head, L.ptr(g.gy), *g.args, g.A.mask, L.ptr(g.gsum), arch, c.tau, c.drop_const, B,
@@ -1055,61 +1108,27 @@ class GEngine:
                 ddepth = None
         if ddepth is not None:
             L.check(lib.dg_head_post_bwd(*head, L.ptr(ddepth), arch, c.tau, c.drop_const, B, self.HW, *tail), "dg_head_post_bwd")
-        pl = (c.nheads * self.HW, 1, self.HW)
-        pm = self.draw_pm is not None  # bf16: the pixel-major copy of the head gradient feeds the two thin MFMA kernels
-        cp = self.cp
-        hsrc, hstr, hkw_w, hkw_c = ((self.draw_pm, (self.HW * cp, cp, 1), {}, {}) if pm else
-                                    (self.draw, pl, {"g_dt": L.DG_F32}, {"in_dt": L.DG_F32}))
-
-        def head_wgrad():
-            hc, wc = self.grid[3]
-            o.wgrad(1, c.ring, B, hc, wc, chs[3], c.nheads, self.a[3], (hc * wc * chs[3], chs[3], 1), hsrc, hstr,
-                    st.fptr("head_w", st.grad), 1.0, defer=True, **hkw_w)
-
-        def head_bwd_data():  # gradient w.r.t. Up3's pre-activation, fused lrelu' mask + bias grad
-            hc, wc = self.grid[3]
-            o.conv(L.MODE_S2, 1, c.ring, B, hc, wc, c.nheads, chs[3], hsrc, hstr, self.dp[3],
-                   (hc * wc * chs[3], chs[3], 1), st.sptr("head_w"), 1.0, L.EPI_MASK, aux=self.a[3],
-                   dbias=st.fptr("up3_b", st.grad), bias_mod=chs[3], defer_db=True, **hkw_c)
-
-        def up_wgrad(i):
-            hc, wc = self.grid[i - 1]
-            ci, co = chs[i - 1], chs[i]
-            o.wgrad(1, c.ring, B, hc, wc, ci, co, self.a[i - 1], (hc * wc * ci, ci, 1), self.dp[i],
-                    (4 * hc * wc * co, co, 1), st.fptr(f"up{i}_w", st.grad), 1.0 / math.sqrt(co * 16), defer=True)
-
-        def up_bwd_data(i):
-            hc, wc = self.grid[i - 1]
-            ci, co = chs[i - 1], chs[i]
-            prev_b = f"up{i - 1}_b" if i > 1 else "proj_b"
-            o.conv(L.MODE_S2, 1, c.ring, B, hc, wc, co, ci, self.dp[i], (4 * hc * wc * co, co, 1), self.dp[i - 1],
-                   (hc * wc * ci, ci, 1), st.sptr(f"up{i}_w"), 1.0 / math.sqrt(co * 16), L.EPI_MASK, aux=self.a[i - 1],
-                   dbias=st.fptr(prev_b, st.grad), bias_mod=ci, defer_db=True)
-
+        chain = (self.draw, self.draw_pm, self.dp)
         # The weight gradients of Up1-3 only read finished buffers (a[i-1], dp[i]: nothing below overwrites them), so they are
         # collected while the backward-data chain is issued and leave as ONE launch behind it (dg_wgrad_group, round 5: the ring
         # fill and the partial-tile stores of one layer under the matrix work of the next - the three B-sized launches ran at
         # 0.31 of the matrix peak, a quarter of each being ramp).
         if chain_first:
-            head_bwd_data()
-            for i in (3, 2, 1):
-                up_bwd_data(i)
+            for i in (4, 3, 2, 1):
+                self._bwd_data(st, B, i, chain, True)
             if after_chain is not None:
                 after_chain()
             with o.grouped():
-                up_wgrad(1)
-                up_wgrad(2)
-                up_wgrad(3)
+                for i in (1, 2, 3):
+                    self._wgrad(st, B, i, self.a[i - 1], chain)
             if after_up1 is not None:
                 after_up1()
-            head_wgrad()
+            self._wgrad(st, B, 4, self.a[3], chain)
         else:
-            with o.grouped():
-                head_wgrad()
-                head_bwd_data()
-                for i in (3, 2, 1):
-                    up_wgrad(i)
-                    up_bwd_data(i)
+            with o.grouped():   # (the Head's runs on a thin kernel: it leaves at once)
+                for i in (4, 3, 2, 1):
+                    self._wgrad(st, B, i, self.a[i - 1], chain)
+                    self._bwd_data(st, B, i, chain, True)
         if not skip_proj:
             self.proj_wgrad(st, self.dp[0], self.zT, B, accumulate_proj)
 
@@ -1124,53 +1143,25 @@ class GEngine:
                         a (x) tangent-chain + tangent-activations (x) first-order chain, bias gradients the sums of
                         the tangent chain.  acts = tangent activations, chain = (draw1, draw_pm1, dp1) of the
                         first-order walk."""
-        c, o, lib = self.cfg, self.ops, L.lib()
+        c, lib = self.cfg, L.lib()
         B = self.ws_B if head_ready else ddepth.shape[0]
-        sp = L.stream_ptr()
-        chs = [c.ch[3], c.ch[2], c.ch[1], c.ch[0]]
         arch = ARCH_ID[c.arch]
         s_depth, s_conf = self.head_scales
         full = acts is not None
         assert not (full and head_ready)
-        g = st.grad
-        common = (L.ptr(self.gout), L.ptr(self.noise_pixel) if arch else None,
-                  L.ptr(self.noise_image) if arch == 2 else None, L.ptr(self.mask) if arch else None, L.ptr(ddepth))
         if full:
-            L.check(lib.dg_head_post_bwd2(*common, L.ptr(thead), arch, c.tau, c.drop_const, B, self.HW, s_depth, s_conf,
-                                          L.ptr(draw), st.fptr("head_b", g), L.ptr(draw_pm), self.cp, sp),
-                    "dg_head_post_bwd2")
+            L.check(lib.dg_head_post_bwd2(*self._head_saved(), L.ptr(ddepth), L.ptr(thead), arch, c.tau, c.drop_const, B, self.HW,
+                                          s_depth, s_conf, L.ptr(draw), st.fptr("head_b", st.grad), L.ptr(draw_pm), self.cp,
+                                          L.stream_ptr()), "dg_head_post_bwd2")
         elif not head_ready:
-            L.check(lib.dg_head_post_bwd(*common, arch, c.tau, c.drop_const, B, self.HW, s_depth, s_conf,
-                                         None if draw_pm is not None else L.ptr(draw),   # (pixel-major copy only)
-                                         None, L.ptr(draw_pm), self.cp, None, sp), "dg_head_post_bwd")
-        hc, wc = self.grid[3]
-        pl = (c.nheads * self.HW, 1, self.HW)
-        pm = draw_pm is not None
-        cp = self.cp
-        gsrc, gstr, gdt = (draw_pm, (self.HW * cp, cp, 1), None) if pm else (draw, pl, L.DG_F32)
-        if full:
-            draw1, draw_pm1, dp1 = chain
-            g1 = (draw_pm1, (self.HW * cp, cp, 1), None) if pm else (draw1, pl, L.DG_F32)
-            for a_src, (gs, gst, gd) in ((self.a[3], (gsrc, gstr, gdt)), (acts[3], g1)):
-                kw = {} if gd is None else {"g_dt": gd}
-                o.wgrad(1, c.ring, B, hc, wc, chs[3], c.nheads, a_src, (hc * wc * chs[3], chs[3], 1), gs, gst,
-                        st.fptr("head_w", g), 1.0, defer=True, **kw)
-        kw = {} if gdt is None else {"in_dt": gdt}
-        o.conv(L.MODE_S2, 1, c.ring, B, hc, wc, c.nheads, chs[3], gsrc, gstr, dp[3], (hc * wc * chs[3], chs[3], 1),
-               st.sptr("head_w"), 1.0, L.EPI_MASK, aux=self.a[3], dbias=st.fptr("up3_b", g) if full else None,
-               bias_mod=chs[3], defer_db=True, **kw)
-        for i in (3, 2, 1):
-            hc, wc = self.grid[i - 1]
-            ci, co = chs[i - 1], chs[i]
-            s = 1.0 / math.sqrt(co * 16)
-            if full:
-                for a_src, g_src in ((self.a[i - 1], dp[i]), (acts[i - 1], chain[2][i])):
-                    o.wgrad(1, c.ring, B, hc, wc, ci, co, a_src, (hc * wc * ci, ci, 1), g_src, (4 * hc * wc * co, co, 1),
-                            st.fptr(f"up{i}_w", g), s, defer=True)
-            prev_b = f"up{i - 1}_b" if i > 1 else "proj_b"
-            o.conv(L.MODE_S2, 1, c.ring, B, hc, wc, co, ci, dp[i], (4 * hc * wc * co, co, 1), dp[i - 1],
-                   (hc * wc * ci, ci, 1), st.sptr(f"up{i}_w"), s, L.EPI_MASK, aux=self.a[i - 1],
-                   dbias=st.fptr(prev_b, g) if full else None, bias_mod=ci, defer_db=True)
+            L.check(lib.dg_head_post_bwd(*self._head_saved(), L.ptr(ddepth), arch, c.tau, c.drop_const, B, self.HW, s_depth,
+                                         s_conf, None if draw_pm is not None else L.ptr(draw),   # (pixel-major copy only)
+                                         None, L.ptr(draw_pm), self.cp, None, L.stream_ptr()), "dg_head_post_bwd")
+        for i in (4, 3, 2, 1):
+            if full:   # (not grouped)
+                self._wgrad(st, B, i, self.a[i - 1], (draw, draw_pm, dp))   # a (x) tangent chain
+                self._wgrad(st, B, i, acts[i - 1], chain)                   # tangent activations (x) first-order chain
+            self._bwd_data(st, B, i, (draw, draw_pm, dp), full)
         if full and second_of:
             self.proj_wgrad(st, dp[0], self.zT, B, True)        # z (x) tangent chain
             self.proj_wgrad(st, chain[2][0], self.vT, B, True)  # v (x) first-order chain
@@ -1187,7 +1178,7 @@ class GEngine:
         c = self.cfg
         Np = c.h0 * c.w0 * c.ch[3]
         Bp = (self.ws_B + 63) // 64 * 64
-        if getattr(self, "_dzT", None) is None or self._dzT.shape != (Np, Bp) or self._dzT.dtype != self.dtype:
+        if self._dzT is None or self._dzT.shape != (Np, Bp) or self._dzT.dtype != self.dtype:
             self._dzT = torch.zeros(Np, Bp, dtype=self.dtype, device=self.dp[0].device)
             self._dzw = torch.empty(c.nz, Bp, dtype=torch.float32, device=self.dp[0].device)
         return Bp
@@ -1214,8 +1205,7 @@ class GEngine:
         the saved leaky-relu masks, no biases.  Fills self.ta[0..3] (tangent activations) and self.tout [B,heads,H,W]."""
         c, o, lib = self.cfg, self.ops, L.lib()
         B = v.shape[0]
-        chs = [c.ch[3], c.ch[2], c.ch[1], c.ch[0]]
-        if getattr(self, "ta", None) is None or self.ta[0].numel() != self.a[0].numel():
+        if self.ta is None or self.ta[0].numel() != self.a[0].numel():
             self.ta = [torch.empty_like(t) for t in self.a]
             self.dp2 = [torch.empty_like(t) for t in self.a]
             if self.x2:
@@ -1226,19 +1216,9 @@ class GEngine:
             self.draw2 = torch.empty_like(self.gout)
             self.draw_pm2 = None if self.draw_pm is None else torch.empty_like(self.draw_pm)
         L.check(lib.dg_cast(L.ptr(v.contiguous().float()), L.ptr(self.vT), o.dt, B * c.nz, L.stream_ptr()), "dg_cast")
-        Np = c.h0 * c.w0 * chs[0]
-        o.conv(L.MODE_GEMM, 0, 1, B, 1, 1, c.nz, Np, self.vT, (c.nz, 0, 1), self.ta[0], (Np, 0, 1), st.sptr("proj_w"),
-               1.0 / math.sqrt(Np), L.EPI_MASK, aux=self.a[0])
-        for i in (1, 2, 3):
-            hc, wc = self.grid[i - 1]
-            ci, co = chs[i - 1], chs[i]
-            o.conv(L.MODE_UP, 0, c.ring, B, hc, wc, ci, co, self.ta[i - 1], (hc * wc * ci, ci, 1), self.ta[i],
-                   (4 * hc * wc * co, co, 1), L.ptr(st.coci[f"up{i}_w"]), 1.0 / math.sqrt(co * 16), L.EPI_MASK,
-                   aux=self.a[i])
-        hc, wc = self.grid[3]
-        o.conv(L.MODE_UP, 0, c.ring, B, hc, wc, chs[3], c.nheads, self.ta[3], (hc * wc * chs[3], chs[3], 1), self.tout,
-               (c.nheads * self.HW, 1, self.HW), L.ptr(st.coci["head_w"]), 1.0, L.EPI_LINEAR, out_dt=L.DG_F32,
-               nscale=self.nscale)
+        self._proj_fwd(st, B, self.vT, self.ta[0], tangent=True)
+        for i in (1, 2, 3, 4):
+            self._fwd(st, B, i, self.ta[i - 1], self.ta[i] if i < 4 else self.tout, tangent=True)
 
     def backward_second(self, st: ParamStore, y, proj_terms=True):
         """the parameter gradient of <v, d(sum x y)/dz> (v folded into the tangents): accumulates into st.grad.
