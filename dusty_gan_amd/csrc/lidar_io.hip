@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void scan_to_polar_kernel(
     xyz[o + 2 * hw] = valid ? z / max_d : 0.f;
   }
   if (x_real) {  // fetch_reals: invert_depth -> [-1,1] -> dropped pixels = drop_const (same arithmetic as
-                 // fetch_reals_kernel in pointwise.hip)
+                 // fetch_real_px in step_inputs.h)
     const float depth = p * (max_d - min_d) + min_d;
     const float disp = 1.f / depth;
     float inv = (disp - 1.f / max_d) / (1.f / min_d - 1.f / max_d);

@@ -1,6 +1,6 @@
-// Optimizer / parameter-state kernels: fused Adam (+EMA, + low-precision shadow write), the transposed weight
-// shadow used by the MFMA forward kernels, and the Philox4x32-10 generator for z / Gumbel / DiffAugment draws.
-#include "common.h"
+// Optimizer / parameter-state kernels: fused Adam (+EMA, + low-precision shadow write), the casts and the transposed weight
+// shadow used by the MFMA forward kernels (whose last launch of a step also advances the step's counters: step_inputs.h).
+#include "step_inputs.h"
 #include "thin_up_frag.h"
 #include <cstdlib>
 typedef __attribute__((ext_vector_type(4))) float f32x4_opt;
@@ -325,20 +325,6 @@ __global__ __launch_bounds__(256) void adam_proj_fused_kernel(float* __restrict_
 
 // all conv segments of a network in one launch: desc[5 i + (0..4)] = (source element offset in `master`, destination
 // pointer, Ci, Co, first tile index); a tile = (tap, 32 x 32 block of [ci][co]) as in transpose_shadow_kernel
-struct CounterAdds {
-  unsigned long long* c[8]; unsigned long long d[8]; int k;
-  int snap_idx, snap_n, snap_ring; const float* snap_src; float* snap_dst;   // snap_idx < 0: no snapshot
-};
-__device__ __forceinline__ void counter_adds_body(const CounterAdds& a) {   // (one block's threads 0 .. k-1)
-  if ((int)threadIdx.x >= a.k) return;
-  const unsigned long long v = *a.c[threadIdx.x];
-  *a.c[threadIdx.x] = v + a.d[threadIdx.x];
-  if ((int)threadIdx.x == a.snap_idx) {          // the thread that advances the counter also files the snapshot under its old value
-    float* dst = a.snap_dst + (long)(v % (unsigned long long)a.snap_ring) * a.snap_n;
-    for (int i = 0; i < a.snap_n; ++i) dst[i] = a.snap_src[i];
-    __threadfence_system();                      // (dst may be mapped host memory)
-  }
-}
 struct UpFrags { DgUpFrag f[4]; int n; int first_block; };   // blocks >= first_block: 3 x UP_FRAG_BLOCKS per fragment set
 // (+ optionally one last block that advances the step's counters and files its scalars: dg_transpose_shadow_multi_tail)
 template <typename T>
@@ -456,272 +442,6 @@ __global__ __launch_bounds__(256) void transpose_shadow_kernel(const float* __re
   }
 }
 
-// (philox4x32_10: common.h)
-// raw bits: out[4*i + j] = philox(seed, counter = (offset + i, stream))[j]
-__global__ void philox_bits_kernel(uint64_t seed, uint64_t stream, uint64_t offset, long n4, uint32_t* __restrict__ out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  uint32_t r[4];
-  philox4x32_10(seed, offset + (uint64_t)i, stream, r);
-  out[4 * i + 0] = r[0]; out[4 * i + 1] = r[1]; out[4 * i + 2] = r[2]; out[4 * i + 3] = r[3];
-}
-
-// kind 0: uniform in [0,1) with 24 bits (bits >> 8) * 2^-24
-// kind 1: standard normal by Box-Muller on pairs (u in (0,1]: 1 - uniform)
-// kind 2: uniform(lo,hi)
-// kind 3: integer in [ilo, ihi) as int32 (modulo of the 32-bit draw; range << 2^32 so the bias is < 2^-20)
-__global__ void philox_fill_kernel(uint64_t seed, uint64_t stream, uint64_t offset, int kind, float lo, float hi,
-                                   int ilo, int ihi, long n, void* __restrict__ out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;  // group of 4 outputs
-  if (4 * i >= n) return;
-  uint32_t r[4];
-  philox4x32_10(seed, offset + (uint64_t)i, stream, r);
-  float f[4];
-  int q[4];
-  const float s24 = 1.f / 16777216.f;
-  if (kind == 1) {
-#pragma unroll
-    for (int j = 0; j < 4; j += 2) {
-      const float u1 = 1.f - (float)(r[j] >> 8) * s24;  // (0,1]
-      const float u2 = (float)(r[j + 1] >> 8) * s24;
-      const float rad = sqrtf(-2.f * logf(u1));
-      f[j] = rad * cosf(6.283185307179586f * u2);
-      f[j + 1] = rad * sinf(6.283185307179586f * u2);
-    }
-  } else if (kind == 3) {
-    const uint32_t range = (uint32_t)(ihi - ilo);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) q[j] = ilo + (int)(r[j] % range);
-  } else {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float u = (float)(r[j] >> 8) * s24;
-      f[j] = kind == 2 ? lo + (hi - lo) * u : u;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const long o = 4 * i + j;
-    if (o < n) {
-      if (kind == 3) ((int*)out)[o] = q[j];
-      else ((float*)out)[o] = f[j];
-    }
-  }
-}
-
-// One DiffAugment parameter set per sample (utils/diff_augment.py:27-28,36-38,46-48,59-60,86-87): three
-// uniform(-1,1) draws and four integer draws, from two Philox counters per sample.
-__global__ void aug_draw_kernel(uint64_t seed, uint64_t stream, uint64_t offset, int B, int sh, int sw, int nx, int ny,
-                                float* __restrict__ uf, int* __restrict__ qi) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  uint32_t r0[4], r1[4];
-  philox4x32_10(seed, offset + 2 * (uint64_t)b, stream, r0);
-  philox4x32_10(seed, offset + 2 * (uint64_t)b + 1, stream, r1);
-  const float s24 = 1.f / 16777216.f;
-  for (int j = 0; j < 3; ++j) uf[j * B + b] = -1.f + 2.f * (float)(r0[j] >> 8) * s24;
-  qi[0 * B + b] = -sh + (int)(r1[0] % (uint32_t)(2 * sh + 1));
-  qi[1 * B + b] = -sw + (int)(r1[1] % (uint32_t)(2 * sw + 1));
-  qi[2 * B + b] = (int)(r1[2] % (uint32_t)nx);
-  qi[3 * B + b] = (int)(r1[3] % (uint32_t)ny);
-}
-
-// ---- device-resident counters: the same draws with the Philox offset / Adam step count read from device memory, so
-//      a whole training step can be captured once in a hipGraph and replayed (a host-side offset would be frozen in
-//      the captured kernel arguments).  dg_counter_add advances a counter after its consumers (stream order).
-__global__ void counter_add_kernel(unsigned long long* c, unsigned long long delta) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *c += delta;
-}
-__global__ void counter_add_multi_kernel(CounterAdds a) {
-  if (blockIdx.x == 0) counter_adds_body(a);
-}
-// (the bodies are device functions: dg_step_prologue's kernel runs the same draws as extra blocks of one launch)
-__device__ __forceinline__ void philox_fill_body(uint64_t seed, uint64_t stream, uint64_t offset, int kind, float lo, float hi,
-                                                 int ilo, int ihi, long n, void* __restrict__ out, bf16* __restrict__ out_bf16,
-                                                 long i) {
-  if (4 * i >= n) return;
-  uint32_t r[4];
-  philox4x32_10(seed, offset + (uint64_t)i, stream, r);
-  const float s24 = 1.f / 16777216.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const long o = 4 * i + j;
-    if (o >= n) break;
-    if (kind == 3) {
-      ((int*)out)[o] = ilo + (int)(r[j] % (uint32_t)(ihi - ilo));
-    } else if (kind == 1) {
-      const int a = j & ~1;
-      const float u1 = 1.f - (float)(r[a] >> 8) * s24, u2 = (float)(r[a + 1] >> 8) * s24;
-      const float rad = sqrtf(-2.f * logf(u1));
-      const float v = (j & 1) ? rad * sinf(6.283185307179586f * u2) : rad * cosf(6.283185307179586f * u2);
-      ((float*)out)[o] = v;
-      if (out_bf16) out_bf16[o] = (bf16)v;
-    } else {
-      const float u = (float)(r[j] >> 8) * s24;
-      const float v = kind == 2 ? lo + (hi - lo) * u : u;
-      ((float*)out)[o] = v;
-      if (out_bf16) out_bf16[o] = (bf16)v;
-    }
-  }
-}
-__global__ void philox_fill_dev_kernel(uint64_t seed, uint64_t stream, const unsigned long long* __restrict__ offp,
-                                       int kind, float lo, float hi, int ilo, int ihi, long n, void* __restrict__ out) {
-  philox_fill_body(seed, stream, *offp, kind, lo, hi, ilo, ihi, n, out, nullptr, (long)blockIdx.x * blockDim.x + threadIdx.x);
-}
-// GumbelSigmoid.logistic_noise (models/dusty.py:30-36) straight from the generator: element o of U1 is word o & 3 of Philox
-// counter offset + o / 4, U2 the same (n + 3) / 4 counters further - exactly what two uniform fills of n elements followed
-// by dg_logistic_noise produce, in one launch and without the two 4 n-byte round trips
-__device__ __forceinline__ void philox_logistic_body(uint64_t seed, uint64_t stream, uint64_t offset, float eps, long n,
-                                                     float* __restrict__ out, long i) {
-  if (4 * i >= n) return;
-  const uint64_t n4 = (uint64_t)((n + 3) / 4);
-  uint32_t r1[4], r2[4];
-  philox4x32_10(seed, offset + (uint64_t)i, stream, r1);
-  philox4x32_10(seed, offset + n4 + (uint64_t)i, stream, r2);
-  const float s24 = 1.f / 16777216.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const long o = 4 * i + j;
-    if (o >= n) break;
-    const float u1 = (float)(r1[j] >> 8) * s24, u2 = (float)(r2[j] >> 8) * s24;
-    out[o] = -logf(logf(u1 + eps) / logf(u2 + eps) + eps);
-  }
-}
-__global__ void philox_logistic_dev_kernel(uint64_t seed, uint64_t stream, const unsigned long long* __restrict__ offp,
-                                           float eps, long n, float* __restrict__ out) {
-  philox_logistic_body(seed, stream, *offp, eps, n, out, (long)blockIdx.x * blockDim.x + threadIdx.x);
-}
-__device__ __forceinline__ void aug_draw_body(uint64_t seed, uint64_t stream, uint64_t offset, int B, int sh, int sw, int nx,
-                                              int ny, float* __restrict__ uf, int* __restrict__ qi, int b) {
-  if (b >= B) return;
-  uint32_t r0[4], r1[4];
-  philox4x32_10(seed, offset + 2 * (uint64_t)b, stream, r0);
-  philox4x32_10(seed, offset + 2 * (uint64_t)b + 1, stream, r1);
-  const float s24 = 1.f / 16777216.f;
-  for (int j = 0; j < 3; ++j) uf[j * B + b] = -1.f + 2.f * (float)(r0[j] >> 8) * s24;
-  qi[0 * B + b] = -sh + (int)(r1[0] % (uint32_t)(2 * sh + 1));
-  qi[1 * B + b] = -sw + (int)(r1[1] % (uint32_t)(2 * sw + 1));
-  qi[2 * B + b] = (int)(r1[2] % (uint32_t)nx);
-  qi[3 * B + b] = (int)(r1[3] % (uint32_t)ny);
-}
-__global__ void aug_draw_dev_kernel(uint64_t seed, uint64_t stream, const unsigned long long* __restrict__ offp, int B,
-                                    int sh, int sw, int nx, int ny, float* __restrict__ uf, int* __restrict__ qi) {
-  aug_draw_body(seed, stream, *offp, B, sh, sw, nx, ny, uf, qi, blockIdx.x * blockDim.x + threadIdx.x);
-}
-
-// One launch for what a training step needs before its first real kernel: the zero-fill of the accumulator arena and the
-// gradient buffers (dg_zero_multi) and every parameter draw of the step - latents (with their bfloat16 copy), Gumbel
-// logistic noise, DiffAugment parameters - as extra blocks.  Four dependent launches of 4-8 us each otherwise.
-struct PrologueZero { float* p[4]; long first[5]; int k; int blocks; };
-struct PrologueDraws { DgDraw d[6]; int first_block[7]; int n; };
-// fetch_reals as more blocks of the same launch (round 6; trainers/dcgan_amp.py:154-160, utils/lidar.py:31-36): block j of the
-// job owns pixels [j chunk, (j + 1) chunk) of the batch - chunk = HW / DG_XSUM_PARTS, so a sample is DG_XSUM_PARTS blocks - and
-// STORES its partial sum to parts[j]: the per-sample sums DiffAugment's contrast needs leave as DG_XSUM_PARTS partials per
-// sample, summed by the reader in a fixed order.  No accumulator that this very launch would have to zero first, no atomics.
-struct PrologueFetch { DgFetch f; int first_block; int blocks; long chunk; };
-__device__ __forceinline__ float prologue_fetch_px(float pol, float m, float min_d, float max_d, float drop_const) {
-  const float depth = pol * (max_d - min_d) + min_d;   // (pointwise.hip fetch_real_px: the same expressions)
-  const float disp = 1.f / depth;
-  float inv = (disp - 1.f / max_d) / (1.f / min_d - 1.f / max_d);
-  inv = inv * 2.f - 1.f;
-  return m * inv + (1.f - m) * drop_const;
-}
-// one fetch block's sweep of `chunk` pixels; kDerived: `mask` is not read, the validity is pol > 0 (a resident store keeps no
-// mask: datasets/resident.py states why that is the stored mask bit for bit)
-template <bool kDerived>
-__device__ __forceinline__ float prologue_fetch_sweep(const float* pol, const float* mask, float* out, long chunk,
-                                                      const DgFetch& f) {
-  float acc = 0.f;
-  constexpr int U = 4;                                   // four trips' loads in flight per lane (8 x 16 bytes)
-  for (long k0 = (long)threadIdx.x * 4; k0 < chunk; k0 += U * 1024) {
-    float4 p4[U], m4[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long k = k0 + u * 1024;
-      if (k < chunk) {
-        p4[u] = *(const float4*)(pol + k);
-        if (kDerived) {
-          m4[u] = make_float4(p4[u].x > 0.f ? 1.f : 0.f, p4[u].y > 0.f ? 1.f : 0.f, p4[u].z > 0.f ? 1.f : 0.f,
-                              p4[u].w > 0.f ? 1.f : 0.f);
-        } else {
-          m4[u] = *(const float4*)(mask + k);
-        }
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const long k = k0 + u * 1024;
-      if (k >= chunk) break;
-      float4 o;
-      o.x = prologue_fetch_px(p4[u].x, m4[u].x, f.min_depth, f.max_depth, f.drop_const);
-      o.y = prologue_fetch_px(p4[u].y, m4[u].y, f.min_depth, f.max_depth, f.drop_const);
-      o.z = prologue_fetch_px(p4[u].z, m4[u].z, f.min_depth, f.max_depth, f.drop_const);
-      o.w = prologue_fetch_px(p4[u].w, m4[u].w, f.min_depth, f.max_depth, f.drop_const);
-      *(float4*)(out + k) = o;
-      acc += (o.x + o.y) + (o.z + o.w);
-    }
-  }
-  return acc;
-}
-__global__ __launch_bounds__(256) void step_prologue_kernel(PrologueZero z, PrologueDraws dr, PrologueFetch fe) {
-  if (fe.blocks > 0 && (int)blockIdx.x >= fe.first_block) {
-    __shared__ float red[16];
-    const DgFetch& f = fe.f;
-    const int j = (int)blockIdx.x - fe.first_block;
-    const long i0 = (long)j * fe.chunk;
-    float acc;
-    if (f.nslab > 0) {
-      // resident store: slab (*ctr % nslab) of the epoch, each sample's variant from the flip table of the epoch's parity.  The
-      // block's DG_XSUM_PARTS-th of one sample is a contiguous run of that sample's stored image.
-      const unsigned long long ctr = *f.pool_ctr, ns = (unsigned long long)f.nslab;
-      const long row = (long)(ctr % ns) * f.B + j / DG_XSUM_PARTS;
-      const long var = f.flip_tab ? (long)f.flip_tab[(long)((ctr / ns) & 1ull) * f.nslab * f.B + row] : 0;
-      const float* pol = f.pol + (var * f.nslab * f.B + row) * f.HW + (long)(j % DG_XSUM_PARTS) * fe.chunk;
-      acc = prologue_fetch_sweep<true>(pol, nullptr, f.out + i0, fe.chunk, f);
-    } else {
-      const float* pol = f.pol;
-      const float* mask = f.mask;
-      if (f.pool_ctr) {
-        const long off = (long)(*f.pool_ctr % (unsigned long long)f.npool) * ((long)f.B * f.HW);
-        pol += off;
-        mask += off;
-      }
-      acc = prologue_fetch_sweep<false>(pol + i0, mask + i0, f.out + i0, fe.chunk, f);
-    }
-    const float sblk = dg_block_sum(acc, red);
-    if (threadIdx.x == 0) f.parts[j] = sblk;
-    return;
-  }
-  if ((int)blockIdx.x < z.blocks) {
-    const long stride = (long)z.blocks * 256, total = z.first[z.k];
-    for (long i4 = (long)blockIdx.x * 256 + threadIdx.x; 4 * i4 < total; i4 += stride) {
-      const long i = 4 * i4;
-      int j = 0;
-#pragma unroll
-      for (int q = 1; q < 4; ++q)
-        if (q < z.k && i >= z.first[q]) j = q;
-      *(float4*)(z.p[j] + (i - z.first[j])) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    return;
-  }
-  const int blk = (int)blockIdx.x - z.blocks;
-  int j = 0;
-  for (int q = 1; q < dr.n; ++q)
-    if (blk >= dr.first_block[q]) j = q;
-  const DgDraw& d = dr.d[j];
-  const long i = (long)(blk - dr.first_block[j]) * 256 + threadIdx.x;
-  const uint64_t offset = *d.offset_dev + d.base;
-  if (d.kind == 0) {
-    philox_fill_body(d.seed, d.stream_id, offset, d.fill_kind, d.lo, d.hi, d.ilo, d.ihi, d.n, d.out, (bf16*)d.out_bf16, i);
-  } else if (d.kind == 1) {
-    philox_logistic_body(d.seed, d.stream_id, offset, d.eps, d.n, (float*)d.out, i);
-  } else {
-    const int sh = (int)(d.H * (1.0 / 8.0) / 2 + 0.5), sw = (int)(d.W * (1.0 / 8.0) / 2 + 0.5);
-    const int ch = (int)(d.H * 0.5 + 0.5), cw = (int)(d.W * 0.5 + 0.5);
-    aug_draw_body(d.seed, d.stream_id, offset, d.B, sh, sw, d.H + (1 - ch % 2), d.W + (1 - cw % 2), d.uf, d.qi, (int)i);
-  }
-}
-
 static inline unsigned nblk(long n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
 extern "C" {
@@ -791,176 +511,6 @@ int dg_transpose_shadow(const float* master, void* dst, int dtype, int Ci, int C
   dim3 grid((Co + 31) / 32, (Ci + 31) / 32, 16);
   if (dtype == DG_BF16) transpose_shadow_kernel<bf16><<<grid, 256, 0, s>>>(master, (bf16*)dst, Ci, Co);
   else transpose_shadow_kernel<float><<<grid, 256, 0, s>>>(master, (float*)dst, Ci, Co);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_philox_bits(uint64_t seed, uint64_t stream, uint64_t offset, long n4, uint32_t* out, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  philox_bits_kernel<<<nblk(n4), 256, 0, s>>>(seed, stream, offset, n4, out);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_philox_fill(uint64_t seed, uint64_t stream, uint64_t offset, int kind, float lo, float hi, int ilo, int ihi,
-                   long n, void* out, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  if (kind < 0 || kind > 3) return DG_EINVAL;
-  if (kind == 3 && ihi <= ilo) return DG_EINVAL;
-  philox_fill_kernel<<<nblk((n + 3) / 4), 256, 0, s>>>(seed, stream, offset, kind, lo, hi, ilo, ihi, n, out);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_aug_draw(uint64_t seed, uint64_t stream, uint64_t offset, int B, int H, int W, float* uf, int* qi, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  const int sh = (int)(H * (1.0 / 8.0) / 2 + 0.5), sw = (int)(W * (1.0 / 8.0) / 2 + 0.5);  // diff_augment.py:58
-  const int ch = (int)(H * 0.5 + 0.5), cw = (int)(W * 0.5 + 0.5);                          // diff_augment.py:85
-  aug_draw_kernel<<<nblk(B), 256, 0, s>>>(seed, stream, offset, B, sh, sw, H + (1 - ch % 2), W + (1 - cw % 2), uf, qi);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_counter_add(unsigned long long* counter, unsigned long long delta, void* s_) {
-  counter_add_kernel<<<1, 64, 0, (hipStream_t)s_>>>(counter, delta);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-// k <= 8 DISTINCT counters advanced by one launch (a step's Philox offsets and Adam step counts, queued by the caller
-// behind their consumers: one graph node instead of one per counter)
-static int fill_counter_adds(CounterAdds& a, unsigned long long* const* counters, const unsigned long long* deltas, int k,
-                             int snap_idx, const float* src, int n, float* dst_ring, int ring) {
-  if (k < 1 || k > 8 || !counters || !deltas) return DG_EINVAL;
-  if (snap_idx >= 0 && (snap_idx >= k || !src || !dst_ring || n < 1 || n > 64 || ring < 1)) return DG_EINVAL;
-  a = CounterAdds{};
-  a.snap_idx = snap_idx; a.snap_n = n; a.snap_ring = ring; a.snap_src = src; a.snap_dst = dst_ring;
-  for (int i = 0; i < k; ++i) {
-    if (!counters[i]) return DG_EINVAL;
-    for (int j = 0; j < i; ++j)
-      if (counters[j] == counters[i]) return DG_EINVAL;
-    a.c[i] = counters[i]; a.d[i] = deltas[i];
-  }
-  a.k = k;
-  return DG_OK;
-}
-static int counter_add_multi(unsigned long long* const* counters, const unsigned long long* deltas, int k, int snap_idx,
-                             const float* src, int n, float* dst_ring, int ring, void* s_) {
-  CounterAdds a{};
-  const int rc = fill_counter_adds(a, counters, deltas, k, snap_idx, src, n, dst_ring, ring);
-  if (rc != DG_OK) return rc;
-  counter_add_multi_kernel<<<1, 64, 0, (hipStream_t)s_>>>(a);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-int dg_counter_add_multi(unsigned long long* const* counters, const unsigned long long* deltas, int k, void* s_) {
-  return counter_add_multi(counters, deltas, k, -1, nullptr, 0, nullptr, 1, s_);
-}
-// ... and slot (old value of counters[snap_idx]) % ring of `dst_ring` (n floats per slot; device memory or mapped pinned host
-// memory) receives src[0..n): the step's logged scalars leave the device from the step's last launch - no copy node behind
-// the graph, and the host reads slot i once an event recorded behind step i has completed, never blocking the launch stream
-int dg_counter_add_multi_snap(unsigned long long* const* counters, const unsigned long long* deltas, int k, int snap_idx,
-                              const float* src, int n, float* dst_ring, int ring, void* s_) {
-  if (snap_idx < 0) return DG_EINVAL;
-  return counter_add_multi(counters, deltas, k, snap_idx, src, n, dst_ring, ring, s_);
-}
-
-int dg_philox_fill_dev(uint64_t seed, uint64_t stream, const unsigned long long* offset_dev, int kind, float lo,
-                       float hi, int ilo, int ihi, long n, void* out, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  if (kind < 0 || kind > 3) return DG_EINVAL;
-  if (kind == 3 && ihi <= ilo) return DG_EINVAL;
-  philox_fill_dev_kernel<<<nblk((n + 3) / 4), 256, 0, s>>>(seed, stream, offset_dev, kind, lo, hi, ilo, ihi, n, out);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-// logistic noise of n elements from the device-resident Philox offset; the caller advances the counter by 2 ((n + 3) / 4)
-int dg_philox_logistic_dev(uint64_t seed, uint64_t stream, const unsigned long long* offset_dev, float eps, long n,
-                           float* out, void* s_) {
-  if (!offset_dev || !out || n <= 0) return DG_EINVAL;
-  philox_logistic_dev_kernel<<<nblk((n + 3) / 4), 256, 0, (hipStream_t)s_>>>(seed, stream, offset_dev, eps, n, out);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-// zero-fill of k <= 4 fp32 buffers (as dg_zero_multi; k may be 0) + ndraw <= 6 draws (DgDraw) + optionally fetch_reals of one
-// batch (DgFetch) in one launch
-static int step_prologue_impl(float* const* ptrs, const long* counts, int k, const DgDraw* draws, int ndraw, const DgFetch* fetch,
-                              void* s_) {
-  if (k < 0 || k > 4 || ndraw < 0 || ndraw > 6 || (k && (!ptrs || !counts)) || (ndraw && !draws)) return DG_EINVAL;
-  PrologueZero z{};
-  long tot = 0;
-  for (int i = 0; i < k; ++i) {
-    if (!ptrs[i] || counts[i] < 0 || counts[i] % 4 != 0 || ((size_t)ptrs[i] & 15) != 0) return DG_EINVAL;
-    z.p[i] = ptrs[i]; z.first[i] = tot;
-    tot += counts[i];
-  }
-  z.first[k] = tot;
-  z.k = k;
-  unsigned zb = nblk(tot / 4);
-  if (zb > 2048) zb = 2048;
-  z.blocks = (int)zb;
-  PrologueDraws dr{};
-  long blocks = 0;
-  for (int i = 0; i < ndraw; ++i) {
-    const DgDraw& d = draws[i];
-    if (!d.offset_dev) return DG_EINVAL;
-    long threads;
-    if (d.kind == 0) {
-      if (!d.out || d.n <= 0 || d.fill_kind < 0 || d.fill_kind > 3 || (d.fill_kind == 3 && (d.ihi <= d.ilo || d.out_bf16)))
-        return DG_EINVAL;
-      threads = (d.n + 3) / 4;
-    } else if (d.kind == 1) {
-      if (!d.out || d.n <= 0) return DG_EINVAL;
-      threads = (d.n + 3) / 4;
-    } else if (d.kind == 2) {
-      if (!d.uf || !d.qi || d.B <= 0 || d.H <= 0 || d.W <= 0) return DG_EINVAL;
-      threads = d.B;
-    } else {
-      return DG_EINVAL;
-    }
-    dr.d[i] = d;
-    dr.first_block[i] = (int)blocks;
-    blocks += (threads + 255) / 256;
-    if (blocks > (1L << 30)) return DG_EUNSUPPORTED;
-  }
-  dr.first_block[ndraw] = (int)blocks;
-  dr.n = ndraw;
-  PrologueFetch fe{};
-  if (fetch) {
-    const DgFetch& f = *fetch;
-    const bool resident = f.nslab > 0;
-    if (!f.pol || !f.out || !f.parts || f.B <= 0 || f.HW <= 0 || f.nslab < 0) return DG_EINVAL;
-    if (resident ? !f.pool_ctr : (!f.mask || (f.pool_ctr && f.npool <= 0))) return DG_EINVAL;
-    // 16-byte accesses, whole 1024-pixel sweeps per block, DG_XSUM_PARTS blocks per sample
-    if (f.HW % (1024L * DG_XSUM_PARTS) != 0 || (((size_t)f.pol | (size_t)(resident ? nullptr : f.mask) | (size_t)f.out) & 15) != 0)
-      return DG_EUNSUPPORTED;
-    fe.f = f;
-    fe.chunk = f.HW / DG_XSUM_PARTS;
-    fe.blocks = f.B * DG_XSUM_PARTS;
-    fe.first_block = (int)(zb + blocks);
-  }
-  if (zb + blocks + fe.blocks == 0) return DG_OK;
-  step_prologue_kernel<<<(unsigned)(zb + blocks + fe.blocks), 256, 0, (hipStream_t)s_>>>(z, dr, fe);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-int dg_step_prologue(float* const* ptrs, const long* counts, int k, const DgDraw* draws, int ndraw, void* s_) {
-  return step_prologue_impl(ptrs, counts, k, draws, ndraw, nullptr, s_);
-}
-int dg_step_prologue_fetch(float* const* ptrs, const long* counts, int k, const DgDraw* draws, int ndraw, const DgFetch* fetch,
-                           void* s_) {
-  if (!fetch) return DG_EINVAL;
-  return step_prologue_impl(ptrs, counts, k, draws, ndraw, fetch, s_);
-}
-
-int dg_aug_draw_dev(uint64_t seed, uint64_t stream, const unsigned long long* offset_dev, int B, int H, int W,
-                    float* uf, int* qi, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  const int sh = (int)(H * (1.0 / 8.0) / 2 + 0.5), sw = (int)(W * (1.0 / 8.0) / 2 + 0.5);
-  const int ch = (int)(H * 0.5 + 0.5), cw = (int)(W * 0.5 + 0.5);
-  aug_draw_dev_kernel<<<nblk(B), 256, 0, s>>>(seed, stream, offset_dev, B, sh, sw, H + (1 - ch % 2), W + (1 - cw % 2), uf, qi);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }

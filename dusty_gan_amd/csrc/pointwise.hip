@@ -1,6 +1,6 @@
 // HBM-bound kernels of the step: BlurVH, the final (4 x w0) dot, head post-processing (tanh + Gumbel point-drop),
 // DiffAugment, NSGAN losses, fetch_reals and small reductions.  Images are fp32 [B,1,H,W]; feature maps are T.
-#include "common.h"
+#include "step_inputs.h"   // (fetch_reals' pixel, source addressing and validation: shared with the step prologue)
 
 // the registered accumulator arena of this device (dg_det_arena; common.h dg_acc_add): read by the kernels of this file that
 // sum across blocks into arena slots - per-sample image sums, logits, the augment adjoint's window sums
@@ -1636,104 +1636,45 @@ __global__ __launch_bounds__(256) void mean_acc_kernel(const float* __restrict__
   if (threadIdx.x == 0) acc[0] += t / n;
 }
 
-// fetch_reals (trainers/dcgan_amp.py:154-160; utils/lidar.py:31-36; utils/__init__.py:70-73)
-__device__ __forceinline__ float fetch_real_px(float pol, float m, float min_d, float max_d, float drop_const) {
-  const float depth = pol * (max_d - min_d) + min_d;
-  const float disp = 1.f / depth;
-  float inv = (disp - 1.f / max_d) / (1.f / min_d - 1.f / max_d);
-  inv = inv * 2.f - 1.f;
-  return m * inv + (1.f - m) * drop_const;
+// fetch_reals, stand-alone (step_inputs.h: the pixel and the three forms of the source; step_inputs.hip runs the same fetch as
+// blocks of the step prologue): block i owns `chunk` pixels of the batch, all of one sample.  kResident: a resident scan
+// store, whose mask is pol > 0.  xsum != nullptr: per-sample sums of the result, one accumulator add per block (see
+// head_post_fwd_kernel) - single floats strided by 256 per lane, then the block sum: the same order on every form of the
+// source, so the sums of a resident fetch are dg_fetch_reals_sum's bits.  xsum == nullptr: chunk = 256, any pixel count.
+template <bool kResident>
+__device__ __forceinline__ float fetch_px_at(const float* __restrict__ pol, const float* __restrict__ mask, int k, const DgFetch& f) {
+  const float p = pol[k];
+  return fetch_real_px(p, kResident ? (p > 0.f ? 1.f : 0.f) : mask[k], f.min_depth, f.max_depth, f.drop_const);
 }
-// xsum != nullptr: per-sample sums of the result, one atomic per block of `chunk` pixels (see head_post_fwd_kernel)
-// pool_ctr != nullptr: `pol` / `mask` are pools of `npool` batches of n pixels and the batch is *pool_ctr % npool (a
-// device-resident loader position: a captured training step replays on the next pooled batch without a copy)
-__global__ __launch_bounds__(256) void fetch_reals_kernel(const float* __restrict__ pol, const float* __restrict__ mask,
-                                                          float min_d, float max_d, float drop_const, long n,
-                                                          float* __restrict__ out, float* __restrict__ xsum, long HW,
-                                                          int chunk, const unsigned long long* __restrict__ pool_ctr,
-                                                          int npool) {
-  __shared__ float red[16];
-  if (pool_ctr) {
-    const long off = (long)(*pool_ctr % (unsigned long long)npool) * n;
-    pol += off;
-    mask += off;
-  }
-  if (!xsum) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = fetch_real_px(pol[i], mask[i], min_d, max_d, drop_const);
-    return;
-  }
-  const long i0 = (long)blockIdx.x * chunk;
+template <bool kResident>
+__device__ __forceinline__ float fetch_sum_sweep(const float* __restrict__ pol, const float* __restrict__ mask,
+                                                 float* __restrict__ out, int chunk, const DgFetch& f) {
   float acc = 0.f;
 #pragma unroll 4
   for (int k = threadIdx.x; k < chunk; k += 256) {               // (independent pixels: their loads in flight together)
-    const long i = i0 + k;
-    const float v = fetch_real_px(pol[i], mask[i], min_d, max_d, drop_const);
-    out[i] = v;
+    const float v = fetch_px_at<kResident>(pol, mask, k, f);
+    out[k] = v;
     acc += v;
   }
-  const float sblk = dg_block_sum(acc, red);
-  if (threadIdx.x == 0) dg_acc_add(&xsum[i0 / HW], sblk, (unsigned)(HW / chunk), g_det);
+  return acc;
 }
-
-// fetch_reals_kernel's summing form on a resident scan store (DgFetch's resident form, include/dusty_gan_hip.h): the block's
-// `chunk` pixels of one sample, the batch and the sample's stored variant picked on the device; the mask is pol > 0
-// (datasets/resident.py).  Same per-lane order and block sum as fetch_reals_kernel: the sums are dg_fetch_reals_sum's bits.
-__global__ __launch_bounds__(256) void fetch_reals_resident_kernel(const float* __restrict__ store,
-                                                                   const unsigned long long* __restrict__ pool_ctr, long nslab,
-                                                                   const unsigned char* __restrict__ flip_tab, float min_d,
-                                                                   float max_d, float drop_const, int B, long HW,
-                                                                   float* __restrict__ out, float* __restrict__ xsum, int chunk) {
+template <bool kResident>
+__global__ __launch_bounds__(256) void fetch_reals_kernel(DgFetch f, float* __restrict__ xsum, int chunk) {
   __shared__ float red[16];
-  const long i0 = (long)blockIdx.x * chunk, b = i0 / HW;
-  const unsigned long long ctr = *pool_ctr, ns = (unsigned long long)nslab;
-  const long row = (long)(ctr % ns) * B + b;
-  const long var = flip_tab ? (long)flip_tab[(long)((ctr / ns) & 1ull) * nslab * B + row] : 0;
-  const float* pol = store + (var * nslab * B + row) * HW + (i0 - b * HW);
-  float acc = 0.f;
-#pragma unroll 4
-  for (int k = threadIdx.x; k < chunk; k += 256) {
-    const float p = pol[k];
-    const float v = fetch_real_px(p, p > 0.f ? 1.f : 0.f, min_d, max_d, drop_const);
-    out[i0 + k] = v;
-    acc += v;
+  const long i0 = (long)blockIdx.x * chunk, b = i0 / f.HW;
+  const FetchSrc src = fetch_src<kResident>(f, b, i0 - b * f.HW);
+  if (!xsum) {
+    if (i0 + threadIdx.x < (long)f.B * f.HW) f.out[i0 + threadIdx.x] = fetch_px_at<kResident>(src.pol, src.mask, threadIdx.x, f);
+    return;
   }
-  const float sblk = dg_block_sum(acc, red);
-  if (threadIdx.x == 0) dg_acc_add(&xsum[b], sblk, (unsigned)(HW / chunk), g_det);
-}
-
-// batch `slab` of a resident store as {depth, mask}: V consecutive pixels of one sample per lane (V = 4: 16-byte accesses)
-template <int V>
-__global__ __launch_bounds__(256) void resident_gather_kernel(const float* __restrict__ store, long nslab, int B, long HW,
-                                                              long slab, const unsigned char* __restrict__ flip,
-                                                              float* __restrict__ depth, float* __restrict__ mask) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long)B * HW / V) return;
-  const long e = i * V, b = e / HW;
-  const long var = flip ? (long)flip[b] : 0;
-  const float* src = store + (var * nslab + slab) * (long)B * HW + e;   // sample (var, slab B + b), pixel e - b HW
-  if constexpr (V == 4) {
-    const float4 p = *(const float4*)src;
-    *(float4*)(depth + e) = p;
-    *(float4*)(mask + e) = make_float4(p.x > 0.f ? 1.f : 0.f, p.y > 0.f ? 1.f : 0.f, p.z > 0.f ? 1.f : 0.f, p.w > 0.f ? 1.f : 0.f);
-  } else {
-    const float p = *src;
-    depth[e] = p;
-    mask[e] = p > 0.f ? 1.f : 0.f;
-  }
+  const float sblk = dg_block_sum(fetch_sum_sweep<kResident>(src.pol, src.mask, f.out + i0, chunk, f), red);
+  if (threadIdx.x == 0) dg_acc_add(&xsum[b], sblk, (unsigned)(f.HW / chunk), g_det);
 }
 
 // y = a * x
 __global__ void scale_kernel(const float* __restrict__ x, float a, long n, float* __restrict__ y) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) y[i] = a * x[i];
-}
-
-// logistic noise of GumbelSigmoid (models/dusty.py:30-36) from two uniform fields
-__global__ void logistic_noise_kernel(const float* __restrict__ u1, const float* __restrict__ u2, float eps, long n,
-                                      float* __restrict__ out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = -logf(logf(u1[i] + eps) / logf(u2[i] + eps) + eps);
 }
 
 // ----------------------------------------------------------------------------------------------------------
@@ -2215,73 +2156,56 @@ int dg_nsgan_g(const float* y_fake, int B, float w_gan, float* dy, float* scal, 
   return DG_OK;
 }
 
-int dg_fetch_reals(const float* pol, const float* mask, float min_depth, float max_depth, float drop_const, long n,
-                   float* out, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  fetch_reals_kernel<<<nblk(n), 256, 0, s>>>(pol, mask, min_depth, max_depth, drop_const, n, out, nullptr, 1, 256, nullptr, 1);
+// the four stand-alone forms of fetch_reals: each names its source in a DgFetch (include/dusty_gan_hip.h) for one launcher.
+// xsum != nullptr: xsum[b] += sum of out[b] over its HW pixels (xsum zeroed by the caller; HW % 256 == 0 or DG_EUNSUPPORTED)
+static int fetch_reals_launch(DgFetch f, float min_depth, float max_depth, float drop_const, float* out, float* xsum, void* s_) {
+  f.min_depth = min_depth; f.max_depth = max_depth; f.drop_const = drop_const; f.out = out;
+  const int rc = fetch_check(f);
+  if (rc != DG_OK) return rc;
+  if (xsum && f.HW % 256 != 0) return DG_EUNSUPPORTED;
+  const int chunk = xsum ? sum_chunk(f.HW) : 256;
+  const unsigned grid = nblk((long)f.B * f.HW, chunk);
+  if (f.nslab > 0) fetch_reals_kernel<true><<<grid, 256, 0, (hipStream_t)s_>>>(f, xsum, chunk);
+  else fetch_reals_kernel<false><<<grid, 256, 0, (hipStream_t)s_>>>(f, xsum, chunk);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }
-// ... + xsum[b] += sum of out[b] over its HW pixels (xsum zeroed by the caller; HW % 256 == 0 or DG_EUNSUPPORTED)
+int dg_fetch_reals(const float* pol, const float* mask, float min_depth, float max_depth, float drop_const, long n,
+                   float* out, void* s_) {
+  DgFetch f{};
+  f.pol = pol; f.mask = mask; f.B = 1; f.HW = n;
+  return fetch_reals_launch(f, min_depth, max_depth, drop_const, out, nullptr, s_);
+}
 int dg_fetch_reals_sum(const float* pol, const float* mask, float min_depth, float max_depth, float drop_const, int B,
                        long HW, float* out, float* xsum, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
   if (!xsum) return DG_EINVAL;
-  if (HW % 256 != 0) return DG_EUNSUPPORTED;
-  const int chunk = sum_chunk(HW);
-  fetch_reals_kernel<<<nblk((long)B * HW, chunk), 256, 0, s>>>(pol, mask, min_depth, max_depth, drop_const, (long)B * HW, out,
-                                                                xsum, HW, chunk, nullptr, 1);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
+  DgFetch f{};
+  f.pol = pol; f.mask = mask; f.B = B; f.HW = HW;
+  return fetch_reals_launch(f, min_depth, max_depth, drop_const, out, xsum, s_);
 }
 // ... from a device-resident pool of `npool` batches: batch index = *pool_ctr % npool, read on the device
 int dg_fetch_reals_pool_sum(const float* pol_pool, const float* mask_pool, const unsigned long long* pool_ctr, int npool,
                             float min_depth, float max_depth, float drop_const, int B, long HW, float* out, float* xsum,
                             void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  if (!xsum || !pool_ctr || npool < 1) return DG_EINVAL;
-  if (HW % 256 != 0) return DG_EUNSUPPORTED;
-  const int chunk = sum_chunk(HW);
-  fetch_reals_kernel<<<nblk((long)B * HW, chunk), 256, 0, s>>>(pol_pool, mask_pool, min_depth, max_depth, drop_const,
-                                                                (long)B * HW, out, xsum, HW, chunk, pool_ctr, npool);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
+  if (!xsum || !pool_ctr) return DG_EINVAL;
+  DgFetch f{};
+  f.pol = pol_pool; f.mask = mask_pool; f.pool_ctr = pool_ctr; f.npool = npool; f.B = B; f.HW = HW;
+  return fetch_reals_launch(f, min_depth, max_depth, drop_const, out, xsum, s_);
 }
-
+// ... from a resident scan store: the batch and each sample's stored variant picked on the device
 int dg_fetch_reals_resident_sum(const float* store, const unsigned long long* pool_ctr, long nslab,
                                 const unsigned char* flip_tab, float min_depth, float max_depth, float drop_const, int B,
                                 long HW, float* out, float* xsum, void* s_) {
-  if (!store || !pool_ctr || !out || !xsum || nslab < 1 || B <= 0 || HW <= 0) return DG_EINVAL;
-  if (HW % 256 != 0) return DG_EUNSUPPORTED;
-  const int chunk = sum_chunk(HW);
-  fetch_reals_resident_kernel<<<nblk((long)B * HW, chunk), 256, 0, (hipStream_t)s_>>>(
-      store, pool_ctr, nslab, flip_tab, min_depth, max_depth, drop_const, B, HW, out, xsum, chunk);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
+  if (!xsum || nslab < 1) return DG_EINVAL;
+  DgFetch f{};
+  f.pol = store; f.pool_ctr = pool_ctr; f.nslab = nslab; f.flip_tab = flip_tab; f.B = B; f.HW = HW;
+  return fetch_reals_launch(f, min_depth, max_depth, drop_const, out, xsum, s_);
 }
 
-int dg_resident_gather(const float* store, long nslab, int B, long HW, long slab, const unsigned char* flip, float* depth,
-                       float* mask, void* s_) {
-  if (!store || !depth || !mask || nslab < 1 || B <= 0 || HW <= 0 || slab < 0 || slab >= nslab) return DG_EINVAL;
-  hipStream_t s = (hipStream_t)s_;
-  if (HW % 4 == 0 && (((size_t)store | (size_t)depth | (size_t)mask) & 15) == 0)
-    resident_gather_kernel<4><<<nblk((long)B * HW / 4), 256, 0, s>>>(store, nslab, B, HW, slab, flip, depth, mask);
-  else
-    resident_gather_kernel<1><<<nblk((long)B * HW), 256, 0, s>>>(store, nslab, B, HW, slab, flip, depth, mask);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
 
 int dg_scale(const float* x, float a, long n, float* y, void* s_) {
   hipStream_t s = (hipStream_t)s_;
   scale_kernel<<<nblk(n), 256, 0, s>>>(x, a, n, y);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_logistic_noise(const float* u1, const float* u2, float eps, long n, float* out, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  logistic_noise_kernel<<<nblk(n), 256, 0, s>>>(u1, u2, eps, n, out);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }

@@ -1,4 +1,4 @@
-"""Philox4x32-10 stream on the device (csrc/optim.hip).  The reference draws z, Gumbel uniforms and DiffAugment
+"""Philox4x32-10 stream on the device (csrc/step_inputs.hip).  The reference draws z, Gumbel uniforms and DiffAugment
 parameters from torch's unseeded device generator (trainers/dcgan_amp.py:151-152; models/dusty.py:33-34;
 utils/diff_augment.py:27-28,59-60,86-87); here every draw is a counter-based Philox call so a (seed, rank) pair
 reproduces a run and parity tests can inject the draws instead."""

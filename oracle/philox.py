@@ -1,5 +1,5 @@
 """Philox4x32-10 restated in numpy (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11).
-TEST INFRASTRUCTURE: checks csrc/optim.hip's generator bit for bit.  Pinned by the Random123 known-answer vectors
+TEST INFRASTRUCTURE: checks csrc/step_inputs.hip's generator bit for bit.  Pinned by the Random123 known-answer vectors
 (tests/test_oracle_golden.py::test_philox_kat)."""
 import numpy as np
 

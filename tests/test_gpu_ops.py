@@ -922,6 +922,34 @@ def test_philox_known_answer(L):
     assert abs(float(z.mean())) < 5e-3 and abs(float(z.std()) - 1.0) < 5e-3
 
 
+def test_host_offset_draws_equal_the_device_offset_draws(L):
+    """dg_philox_fill(offset = k) and dg_philox_fill_dev on a device counter that holds k write the same bits for every kind
+    (n not a multiple of 4: the last counter's words are partly unused), and so do dg_aug_draw / dg_aug_draw_dev.  GAN
+    inversion draws its latents through the host-offset entry and the trainer through the device-offset one."""
+    lib = L.lib()
+    k, n, seed, stream = 977, 4099, 20240229, 5
+    ctr = torch.full((1,), k, dtype=torch.int64, device=DEV)
+    for kind in range(4):
+        dt = torch.int32 if kind == 3 else torch.float32
+        a = torch.full((n + 4,), -7, dtype=dt, device=DEV)   # (4 elements of margin: neither entry writes past n)
+        b = a.clone()
+        args = (kind, -0.75, 2.5, -3, 19, n)
+        L.check(lib.dg_philox_fill(seed, stream, k, *args, a.data_ptr(), None), "dg_philox_fill")
+        L.check(lib.dg_philox_fill_dev(seed, stream, ctr.data_ptr(), *args, b.data_ptr(), None), "dg_philox_fill_dev")
+        torch.cuda.synchronize()
+        assert torch.equal(a, b), kind
+        assert bool((a[n:] == -7).all()) and not bool((a[:n] == -7).all()), kind
+    for B, H, W in ((37, 64, 1024), (5, 10, 36)):
+        uf = [torch.empty(3, B, device=DEV) for _ in range(2)]
+        qi = [torch.empty(4, B, dtype=torch.int32, device=DEV) for _ in range(2)]
+        L.check(lib.dg_aug_draw(seed, stream, k, B, H, W, uf[0].data_ptr(), qi[0].data_ptr(), None), "dg_aug_draw")
+        L.check(lib.dg_aug_draw_dev(seed, stream, ctr.data_ptr(), B, H, W, uf[1].data_ptr(), qi[1].data_ptr(), None),
+                "dg_aug_draw_dev")
+        torch.cuda.synchronize()
+        assert torch.equal(uf[0], uf[1]) and torch.equal(qi[0], qi[1]), (B, H, W)
+    assert int(ctr.item()) == k
+
+
 @pytest.mark.parametrize("Ci,Co,H,W,B,dtype,cforce,wforce,family,variant", [
     # direct conv + direct weight gradient (narrow nets, golden cases)
     (6, 4, 8, 16, 3, torch.float32, DG_FORCE_DIRECT, DG_FORCE_DIRECT, DG_CONV_FAMILY_DIRECT, DG_WGRAD_VARIANT_DIRECT),
