@@ -185,6 +185,9 @@ PROTOTYPES = {
     "dg_inv_to_xyz": [_P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P],
     "dg_unit_map": [_P, _L, _I, _P, _P],
     "dg_normals": [_P, _I, _I, _I, _I, _P, _P],
+    "dg_scan_project": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "dg_angle_accum": [_P, _I, _I, _I, _I, _D, _D, _P, _P, _P],
+    "dg_angle_finish": [_P, _P, _I, _I, _P, _P],
     "dg_fps": [_P, _I, _I, _I, _P, _P, _P, _P],
     "dg_chamfer_dir": [_P, _I, _I, _P, _I, _I, _P, _P],
     "dg_chamfer_paired": [_P, _I, _P, _I, _I, _P, _P],

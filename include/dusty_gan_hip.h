@@ -434,6 +434,29 @@ int dg_unit_map(const float* x, long n, int mode, float* y, void* stream);
  * (d = 2): points [B,3,H,W] -> normal image [B,3,H,W] in [0,1] */
 int dg_normals(const float* points, int B, int H, int W, int d, float* out, void* stream);
 
+/* ---- raw Velodyne scans -> the dataset's files (process_kitti.py; csrc/scan_project.hip) ---------------------
+ * dg_scan_project: process_point_clouds  process_kitti.py:76-118 for S raw scans.  points [N,4] fp32 = the scans' (x, y, z,
+ * reflectance) records back to back, offsets [S+1] int64 (offsets[0] = 0, ascending, offsets[S] = N: scan s is points
+ * [offsets[s], offsets[s+1])); out [S,H,W,4] fp32.  H must be 64 (DG_EUNSUPPORTED otherwise: the reference hard-codes the
+ * last ring's row, 63).  Caller-owned workspaces, no initial contents required: keys [S*H*W] u64 (the z-buffer: depth bits
+ * << 32 | point index, 64-bit atomicMin), status [S] int32.  Every cell holds the NEAREST point that fell into it (float32
+ * depth; on a depth tie the LOWER point index), zeros where none did.  status[s] = 1: scan s has a ring row below -64, where
+ * numpy's negative index raises - out[s] is all zeros and the caller reports the scan; rows in [-64,-1] wrap to row + 64 as
+ * numpy's do.  cell [N] int32 (nullable): every point's row * W + column (-1: not scattered).  Bit-identical from run to
+ * run and whatever S is.
+ * dg_angle_accum / dg_angle_finish: compute_avg_angles  process_kitti.py:143-183.  scans [S,H,W,C] fp32 projected scans
+ * (C >= 3) at their own size; per pixel the 32.32 fixed-point sums of pitch = atan2(z, |xy|) and yaw = atan2(y, x) of
+ * KITTIOdometry.preprocess's unit-space, range-masked xyz, and the count of pixels with depth > 1e-8, are ADDED to sums
+ * [2,H,W] int64 and count [H,W] int32 (the caller zero-fills both before the first chunk): integer sums, so the result does
+ * not depend on how the dataset is cut into chunks.  dg_angle_finish: angles [2,H,W] fp32 = sums / count, pitch first; a
+ * never-valid pixel gets the mean pitch of its row's valid pixels and the mean yaw of its column's (NaN where the row /
+ * column has none - the reference asserts there). */
+int dg_scan_project(const float* points, const long* offsets, int S, int H, int W, unsigned long long* keys, int* status,
+                    int* cell, float* out, void* stream);
+int dg_angle_accum(const float* scans, int S, int H, int W, int C, double min_depth, double max_depth, long long* sums,
+                   int* count, void* stream);
+int dg_angle_finish(const long long* sums, const int* count, int H, int W, float* angles, void* stream);
+
 /* ---- validation metrics (the reference's CUDA extensions and their torch drivers) -------
  * dg_fps: furthest point sampling  utils/sampling/fps/furthest_point_sampling.cu:97-207 (+ gather_points :38-60 when
  * `out` is given).  xyz [B,n,3] fp32, m <= n samples per cloud, temp [B,n] fp32 workspace, idx [B,m] int32, out
