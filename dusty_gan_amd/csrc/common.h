@@ -248,6 +248,9 @@ __device__ __forceinline__ float dg_fix2_value(long long hi, long long lo) {
 // for its 512-1536 adds (scripts/bench_pointwise.py: head_post_fwd 10.6 us with sums, 6.9 without).
 #define DG_DET_STRIDE 128
 struct DgDet { float* base; unsigned long long* shadow; long n; };
+// the current device's registered arena, all zeros when none is (pointwise.hip, beside dg_det_arena): what a launcher passes, by
+// value, to a kernel that calls dg_acc_add
+DgDet dg_det_current();
 // dg_acc_add that also tells its caller whether it drew the LAST ticket: 1 = last (total = the sum of all `contributors`
 // partials of this round, already added to *dst), 0 = not last, -1 = dst is outside the registered arena (a float atomic was
 // issued; nobody knows who is last).  For a second-level sum by the last contributors only (blur_r1_tangent_kernel's batch mean:

@@ -1,8 +1,8 @@
 // What the kernels that feed a training step share ACROSS translation units (the library is built without relocatable device
 // code, so a body two files run lives in a header):
 //   * the counter adds: step_inputs.hip's dg_counter_add* launches and the tail block of optim.hip's shadow refresh;
-//   * fetch_reals' pixel, source addressing and validation: pointwise.hip's stand-alone kernel (whose sums go through that
-//     file's accumulator arena) and the fetch blocks of step_inputs.hip's step prologue.
+//   * fetch_reals' pixel, source addressing and validation: step_inputs.hip's stand-alone kernel and the fetch blocks of its
+//     step prologue.
 #pragma once
 #include "common.h"
 

@@ -1,9 +1,8 @@
 // What feeds a training step: the Philox4x32-10 draws (latents, Gumbel logistic noise, DiffAugment parameters), the
 // device-resident counters behind them, the resident scan store's gather, and the step prologue - one launch that zero-fills,
 // draws and fetches the real batch.  Every draw has ONE body; its stand-alone entry points and the prologue's blocks run it.
-// (fetch_reals' stand-alone kernel sums through pointwise.hip's accumulator arena and lives there; step_inputs.h holds what
-// the two share.)
 #include "step_inputs.h"
+#include "pointwise.h"   // (nblk, sum_chunk)
 
 // (philox4x32_10: common.h)
 // raw bits: out[4*i + j] = philox(seed, counter = (offset + i, stream))[j]
@@ -140,6 +139,41 @@ __global__ __launch_bounds__(256) void resident_gather_kernel(const float* __res
   }
 }
 
+// fetch_reals, stand-alone (step_inputs.h: the pixel and the three forms of the source; the step prologue below runs the same
+// fetch as blocks of its launch): block i owns `chunk` pixels of the batch, all of one sample.  kResident: a resident scan
+// store, whose mask is pol > 0.  xsum != nullptr: per-sample sums of the result, one accumulator add per block (see
+// head_post_fwd_kernel) - single floats strided by 256 per lane, then the block sum: the same order on every form of the
+// source, so the sums of a resident fetch are dg_fetch_reals_sum's bits.  xsum == nullptr: chunk = 256, any pixel count.
+template <bool kResident>
+__device__ __forceinline__ float fetch_px_at(const float* __restrict__ pol, const float* __restrict__ mask, int k, const DgFetch& f) {
+  const float p = pol[k];
+  return fetch_real_px(p, kResident ? (p > 0.f ? 1.f : 0.f) : mask[k], f.min_depth, f.max_depth, f.drop_const);
+}
+template <bool kResident>
+__device__ __forceinline__ float fetch_sum_sweep(const float* __restrict__ pol, const float* __restrict__ mask,
+                                                 float* __restrict__ out, int chunk, const DgFetch& f) {
+  float acc = 0.f;
+#pragma unroll 4
+  for (int k = threadIdx.x; k < chunk; k += 256) {               // (independent pixels: their loads in flight together)
+    const float v = fetch_px_at<kResident>(pol, mask, k, f);
+    out[k] = v;
+    acc += v;
+  }
+  return acc;
+}
+template <bool kResident>
+__global__ __launch_bounds__(256) void fetch_reals_kernel(DgFetch f, float* __restrict__ xsum, int chunk, const DgDet det) {
+  __shared__ float red[16];
+  const long i0 = (long)blockIdx.x * chunk, b = i0 / f.HW;
+  const FetchSrc src = fetch_src<kResident>(f, b, i0 - b * f.HW);
+  if (!xsum) {
+    if (i0 + threadIdx.x < (long)f.B * f.HW) f.out[i0 + threadIdx.x] = fetch_px_at<kResident>(src.pol, src.mask, threadIdx.x, f);
+    return;
+  }
+  const float sblk = dg_block_sum(fetch_sum_sweep<kResident>(src.pol, src.mask, f.out + i0, chunk, f), red);
+  if (threadIdx.x == 0) dg_acc_add(&xsum[b], sblk, (unsigned)(f.HW / chunk), det);
+}
+
 // One launch for what a training step needs before its first real kernel: the zero-fill of the accumulator arena and the
 // gradient buffers (dg_zero_multi) and every parameter draw of the step - latents (with their bfloat16 copy), Gumbel
 // logistic noise, DiffAugment parameters - as extra blocks.  Four dependent launches of 4-8 us each otherwise.
@@ -151,7 +185,7 @@ struct PrologueDraws { DgDraw d[6]; int first_block[7]; int n; };
 // order.  No accumulator that this very launch would have to zero first, no atomics.
 struct PrologueFetch { DgFetch f; int first_block; int blocks; long chunk; };
 // one fetch block's sweep of `chunk` pixels; kDerived: `mask` is not read, the validity is pol > 0.  (Not the stand-alone
-// kernel's sweep - pointwise.hip, single floats into an accumulator - on purpose: this one was tuned for the launch it rides on.)
+// kernel's sweep above - single floats into an accumulator - on purpose: this one was tuned for the launch it rides on.)
 template <bool kDerived>
 __device__ __forceinline__ float prologue_fetch_sweep(const float* pol, const float* mask, float* out, long chunk,
                                                       const DgFetch& f) {
@@ -231,8 +265,6 @@ __global__ __launch_bounds__(256) void step_prologue_kernel(PrologueZero z, Prol
     aug_draw_body(d.seed, d.stream_id, offset, d.B, g.sh, g.sw, g.nx, g.ny, d.uf, d.qi, (int)i);
   }
 }
-
-static inline unsigned nblk(long n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
 
 extern "C" {
 
@@ -328,6 +360,53 @@ int dg_resident_gather(const float* store, long nslab, int B, long HW, long slab
     resident_gather_kernel<1><<<nblk((long)B * HW), 256, 0, s>>>(store, nslab, B, HW, slab, flip, depth, mask);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
+}
+
+// the four stand-alone forms of fetch_reals: each names its source in a DgFetch (include/dusty_gan_hip.h) for one launcher.
+// xsum != nullptr: xsum[b] += sum of out[b] over its HW pixels (xsum zeroed by the caller; HW % 256 == 0 or DG_EUNSUPPORTED)
+static int fetch_reals_launch(DgFetch f, float min_depth, float max_depth, float drop_const, float* out, float* xsum, void* s_) {
+  f.min_depth = min_depth; f.max_depth = max_depth; f.drop_const = drop_const; f.out = out;
+  const int rc = fetch_check(f);
+  if (rc != DG_OK) return rc;
+  if (xsum && f.HW % 256 != 0) return DG_EUNSUPPORTED;
+  const int chunk = xsum ? sum_chunk(f.HW) : 256;
+  const unsigned grid = nblk((long)f.B * f.HW, chunk);
+  const DgDet det = dg_det_current();
+  if (f.nslab > 0) fetch_reals_kernel<true><<<grid, 256, 0, (hipStream_t)s_>>>(f, xsum, chunk, det);
+  else fetch_reals_kernel<false><<<grid, 256, 0, (hipStream_t)s_>>>(f, xsum, chunk, det);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
+int dg_fetch_reals(const float* pol, const float* mask, float min_depth, float max_depth, float drop_const, long n,
+                   float* out, void* s_) {
+  DgFetch f{};
+  f.pol = pol; f.mask = mask; f.B = 1; f.HW = n;
+  return fetch_reals_launch(f, min_depth, max_depth, drop_const, out, nullptr, s_);
+}
+int dg_fetch_reals_sum(const float* pol, const float* mask, float min_depth, float max_depth, float drop_const, int B,
+                       long HW, float* out, float* xsum, void* s_) {
+  if (!xsum) return DG_EINVAL;
+  DgFetch f{};
+  f.pol = pol; f.mask = mask; f.B = B; f.HW = HW;
+  return fetch_reals_launch(f, min_depth, max_depth, drop_const, out, xsum, s_);
+}
+// ... from a device-resident pool of `npool` batches: batch index = *pool_ctr % npool, read on the device
+int dg_fetch_reals_pool_sum(const float* pol_pool, const float* mask_pool, const unsigned long long* pool_ctr, int npool,
+                            float min_depth, float max_depth, float drop_const, int B, long HW, float* out, float* xsum,
+                            void* s_) {
+  if (!xsum || !pool_ctr) return DG_EINVAL;
+  DgFetch f{};
+  f.pol = pol_pool; f.mask = mask_pool; f.pool_ctr = pool_ctr; f.npool = npool; f.B = B; f.HW = HW;
+  return fetch_reals_launch(f, min_depth, max_depth, drop_const, out, xsum, s_);
+}
+// ... from a resident scan store: the batch and each sample's stored variant picked on the device
+int dg_fetch_reals_resident_sum(const float* store, const unsigned long long* pool_ctr, long nslab,
+                                const unsigned char* flip_tab, float min_depth, float max_depth, float drop_const, int B,
+                                long HW, float* out, float* xsum, void* s_) {
+  if (!xsum || nslab < 1) return DG_EINVAL;
+  DgFetch f{};
+  f.pol = store; f.pool_ctr = pool_ctr; f.nslab = nslab; f.flip_tab = flip_tab; f.B = B; f.HW = HW;
+  return fetch_reals_launch(f, min_depth, max_depth, drop_const, out, xsum, s_);
 }
 
 // zero-fill of k <= 4 fp32 buffers (as dg_zero_multi; k may be 0) + ndraw <= 6 draws (DgDraw) + optionally fetch_reals of one

@@ -1450,7 +1450,7 @@ class DEngine:
 
     def r1_fused_ok(self):
         """whether dg_blur_bwd_r1 (BlurVH adjoint + R1 tangent + |g|^2 in one pass) takes this image shape
-        (pointwise.hip: four pixels per thread, 1024-pixel blocks)"""
+        (blur_aug.hip: four pixels per thread, 1024-pixel blocks)"""
         c = self.cfg
         return c.W % 4 == 0 and (c.H * c.W) % 1024 == 0
 

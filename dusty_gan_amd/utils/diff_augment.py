@@ -1,6 +1,6 @@
 """DiffAugment on [B,1,H,W] range images -- reference: utils/diff_augment.py:114-132 (p = 1.0).
 
-One fused gather kernel per call (csrc/pointwise.hip) instead of the reference's ~40 small ops, plus the hand-derived
+One fused gather kernel per call (csrc/blur_aug.hip, csrc/diffaug.h) instead of the reference's ~40 small ops, plus the hand-derived
 backward (the G phase differentiates through A(fake), trainers/dcgan_amp.py:256).  Every random draw of one call is
 an explicit parameter set `rp` so parity tests can inject the reference's draws:
     u_b,u_s,u_c float [B] (the uniform_(-1,1) draws; the applied factor is u*u),

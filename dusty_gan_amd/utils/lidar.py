@@ -4,7 +4,7 @@ On the training path it provides `fetch_reals` (Coordinate.invert_depth :31-36 f
 drop-constant fill of Trainer.fetch_reals, trainers/dcgan_amp.py:154-160).  On the output side it turns generated
 inverse depth into the unit-space point map (`inv_to_xyz` :58-65 with revert_depth / pol_to_xyz) on the sensor's
 angle grid (`angles.pt`, resized like LiDAR.init_coordmap :127-130).  All arithmetic is in csrc/ (step_inputs.h,
-pointwise.hip, step_inputs.hip, lidar_io.hip, incl. the surface-normal image of utils/geometry.py); `points_to_depth` (:67-108, used by the reconstruction demo only) is not built.
+step_inputs.hip, lidar_io.hip, incl. the surface-normal image of utils/geometry.py); `points_to_depth` (:67-108, used by the reconstruction demo only) is not built.
 """
 import math
 import os

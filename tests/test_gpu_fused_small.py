@@ -24,7 +24,8 @@ def L():
     return _lib
 
 
-@pytest.mark.parametrize("H,W", [(32, 64), (64, 1024), (8, 48)])   # 8 x 48: H W % 1024 != 0 -> refused
+# 8 x 48: H W % 1024 != 0 -> refused; 6 x 512, 3 x 1024: bands of 2 rows and of 1 row
+@pytest.mark.parametrize("H,W", [(32, 64), (64, 1024), (8, 48), (6, 512), (3, 1024)])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_blur_adjoint_r1_form(L, H, W, dtype):
     """dg_blur_bwd_r1 == dg_blur_bwd, then |g_b|^2 per sample and the scaled copy (the three launches it replaces)"""
@@ -261,10 +262,20 @@ def test_diffaug_blurvh_one_pass(L, H, W, ring, dtype, nsets):
     """dg_diffaug_blur_fwd (DiffAugment + BlurVH, the augmented image never written; one or two source sets per launch)
     == dg_diffaug_fwd_pre into a buffer, then dg_blur_fwd - the launches it replaces in D(A(x)); and the augmented
     image itself against the oracle's DiffAugment (utils/diff_augment.py:114-132)"""
-    from dusty_gan_amd.utils.diff_augment import DiffAugment
+    _diffaug_blurvh_one_pass(L, H, W, ring, dtype, nsets, None)
+
+
+def test_diffaug_blurvh_one_pass_without_translation(L):
+    """... for a policy without translation: no stage wraps the columns then (the last column is its own source, not
+    column 0 as under the translation's `% (W - 1)`)"""
+    _diffaug_blurvh_one_pass(L, 8, 16, 1, torch.float32, 1, ["brightness", "contrast", "cutout"])
+
+
+def _diffaug_blurvh_one_pass(L, H, W, ring, dtype, nsets, policy):
+    from dusty_gan_amd.utils.diff_augment import DEFAULT_POLICY, DiffAugment
     lib = L.lib()
     B = 3
-    A = DiffAugment()
+    A = DiffAugment() if policy is None else DiffAugment(policy=policy)
     g = torch.Generator().manual_seed(H * 3 + W + nsets)
     xs = [torch.randn(B, 1, H, W, generator=g) for _ in range(nsets)]
     rps = [_aug_params(B, H, W, 11 + k, extreme=True) for k in range(nsets)]
@@ -277,7 +288,7 @@ def test_diffaug_blurvh_one_pass(L, H, W, ring, dtype, nsets):
         args, kp = A._args(rp, B, xd.device)
         aug = torch.empty_like(xd)
         L.check(lib.dg_diffaug_fwd_pre(xd.data_ptr(), *args, A.mask, B, H, W, sums.data_ptr(), aug.data_ptr(), None))
-        assert rel_l2(aug.cpu(), O.diff_augment(xs[k], rps[k])) < 1e-6
+        assert rel_l2(aug.cpu(), O.diff_augment(xs[k], rps[k], tuple(DEFAULT_POLICY if policy is None else policy))) < 1e-6
         L.check(lib.dg_blur_fwd(aug.data_ptr(), ref[k * B:].data_ptr(), L.dtype_code(dtype), B, H, W, ring, None))
         q = L.DgAugSet()
         q.x, q.xsum = xd.data_ptr(), sums.data_ptr()
@@ -293,7 +304,7 @@ def test_diffaug_blurvh_one_pass(L, H, W, ring, dtype, nsets):
     assert rel_l2(out.float().cpu(), ref.float().cpu()) < (1e-6 if dtype == torch.float32 else 2e-3)
 
 
-@pytest.mark.parametrize("H,W", [(32, 64), (64, 1024)])
+@pytest.mark.parametrize("H,W", [(32, 64), (64, 1024), (6, 64), (5, 64)])   # 6, 5 rows: bands of 2 rows and of 1 row
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_blurvh_adjoint_with_augment_sum(L, H, W, dtype):
     """dg_blur_bwd_augsum + dg_diffaug_bwd_pre == dg_blur_bwd + dg_diffaug_bwd (adjoint, masked sum, gather: the three
@@ -318,6 +329,46 @@ def test_blurvh_adjoint_with_augment_sum(L, H, W, dtype):
     assert torch.equal(dx2, dx)
     assert rel_l2(gsum.cpu(), ws.cpu()) < 1e-5
     assert rel_l2(got.cpu(), ref.cpu()) < 1e-5
+
+
+# Bound of the inner-product identity below, relative to |A(x) - A(0)| |g|: four times what the library measured at these very
+# inputs before the geometry was consolidated into csrc/diffaug.h (1.365e-8, the worst of the nine cases: fp32 roundings of
+# the forward pixel, of cc g2 + gm and of the two sums), to cover compiler contraction differences.
+ADJOINT_TOL = 4 * 1.365e-8
+
+
+@pytest.mark.parametrize("policy", [None, ["translation"], ["brightness", "contrast", "cutout"]],
+                         ids=["default", "translation", "no-translation"])
+def test_diffaug_adjoint_is_the_transpose_of_the_forward(L, policy):
+    """<A(x) - A(0), g> == <x, A^T(g)> per sample (dg_diffaug_fwd / dg_diffaug_bwd; brightness makes A affine, so the
+    identity is tested on its linear part), both sides accumulated in float64 on the host, for the extreme draws of
+    test_head_post_bwd_aug_equals_gather_then_head_post_bwd (clamped boxes, maximal shifts, the column read twice) and two
+    random ones; and A(x) against the oracle's DiffAugment (utils/diff_augment.py:114-132)."""
+    from dusty_gan_amd.utils.diff_augment import DEFAULT_POLICY, DiffAugment
+    B, H, W = 4, 6, 12
+    A = DiffAugment() if policy is None else DiffAugment(policy=policy)
+    gen = torch.Generator().manual_seed(41)
+    for trial in range(3):
+        rp = O.draw_augment_params(B, H, W, gen)
+        if trial == 0:
+            sh, sw = O.translation_shift(H, W)
+            rp["o_x"][:] = torch.tensor([0, H, 0, H])
+            rp["o_y"][:] = torch.tensor([0, W, W, 0])
+            rp["t_h"][:] = torch.tensor([-sh, sh, 0, 1])
+            rp["t_w"][:] = torch.tensor([-sw, sw, 1, 0])
+        rpd = DiffAugment.params_to_device(rp, DEV)
+        x, g = torch.randn(B, 1, H, W, generator=gen), torch.randn(B, 1, H, W, generator=gen)
+        y = A.apply(x.to(DEV), rpd).cpu()
+        y0 = A.apply(torch.zeros(B, 1, H, W, device=DEV), rpd).cpu()
+        gx = A.backward(g.to(DEV), rpd).cpu()
+        assert rel_l2(y, O.diff_augment(x, rp, tuple(DEFAULT_POLICY if policy is None else policy))) < 1e-6
+        ylin = y.double() - y0.double()
+        lhs = (ylin * g.double()).sum(dim=[1, 2, 3])
+        rhs = (x.double() * gx.double()).sum(dim=[1, 2, 3])
+        scale = ylin.flatten(1).norm(dim=1) * g.double().flatten(1).norm(dim=1)
+        err = float(((lhs - rhs).abs() / scale).max())
+        print("diffaug adjoint identity: policy %s trial %d relative error %.3e" % (policy, trial, err))
+        assert err < ADJOINT_TOL, (trial, err)
 
 
 @pytest.mark.parametrize("H,W,ring", [(32, 64, 1), (64, 1024, 1), (16, 48, 0), (8, 2048, 1), (6, 64, 1)])
