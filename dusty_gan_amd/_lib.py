@@ -188,6 +188,11 @@ PROTOTYPES = {
     "dg_scan_project": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
     "dg_angle_accum": [_P, _I, _I, _I, _I, _D, _D, _P, _P, _P],
     "dg_angle_finish": [_P, _P, _I, _I, _P, _P],
+    "dg_splat_accum": [_P, _P, _I, _L, _I, _I, _I, _P, _P],
+    "dg_render_points": [_P, _P, _I, _L, _I, _P, _I, _P, _I, _D, _P, _P],
+    "dg_splat_finish": [_P, _I, _I, _I, _I, _I, _P, _P],
+    "dg_image_grid": [_P, _L, _I, _I, _I, _I, _F, _I, _P, _P],
+    "dg_turbo_lut": [_P],
     "dg_fps": [_P, _I, _I, _I, _P, _P, _P, _P],
     "dg_chamfer_dir": [_P, _I, _I, _P, _I, _I, _P, _P],
     "dg_chamfer_paired": [_P, _I, _P, _I, _I, _P, _P],

@@ -235,6 +235,21 @@ __device__ __forceinline__ float dg_fix2_value(long long hi, long long lo) {
   return (float)((double)hi * (1.0 / 1048576.0) + (double)lo * (1.0 / 1152921504606846976.0));
 }
 
+// ---- one-word 24.40 fixed point for the splatted images (render.hip): q = rint(v 2^40), from a double.  Ranges: a splat term is
+// corner weight (<= 1) x value; the renderer's values are weight x normal <= 1, so |term| <= 1, and a pixel receives at most 4 N
+// terms with N <= 2^18 points per cloud (the entry points refuse more): |total| <= 2^20.  Scale 2^40 puts that at 2^60, a factor 8
+// below the word's 2^63 - the margin is what a caller of the bare rasterizer may spend on values above 1 (|value| <= 8).  Per term
+// the window is |v| < 2^22 (q < 2^62); larger or non-finite: false, and the term is left out.  Resolution 2^-40, ABSOLUTE: the
+// smallest term that survives the rasterizer's 1e-3 weight cut times exp(-3 depth) (>= 5e-3 inside the unit cube) keeps 22 bits.
+// The total is not range-checked on the device: utils/render.py refuses |value| > 8 before it launches (ValueError), which with the
+// entry points' N <= 2^18 keeps every total inside the word.
+__device__ __forceinline__ bool dg_fix40(double v, long long& q) {
+  if (!(fabs(v) < 4194304.0)) return false;
+  q = __double2ll_rn(v * 1099511627776.0);
+  return true;
+}
+__device__ __forceinline__ double dg_fix40_value(long long q) { return (double)q * (1.0 / 1099511627776.0); }
+
 // ---- dg_acc_add: accumulators inside the registered arena (dg_det_arena: the step's AccArena, plus a shadow of DG_DET_STRIDE
 // bytes per float, zero at rest) are summed in 32.32 in the slot's 64-bit shadow word, the ticket in the word after it.  Anything
 // outside the arena, or with no arena registered, falls back to the float atomic.

@@ -457,6 +457,36 @@ int dg_angle_accum(const float* scans, int S, int H, int W, int C, double min_de
                    int* count, void* stream);
 int dg_angle_finish(const long long* sums, const int* count, int H, int W, float* angles, void* stream);
 
+/* ---- the picture log of a training run (utils/render.py:18-127, train.py:28-34; csrc/render.hip) ---------------
+ * acc: caller-owned u64 words [B,H,W,C] (24.40 fixed point, dg_fix40 of csrc/common.h), ZERO AT REST: all zeros before the
+ * first accumulate, zeroed again by dg_splat_finish.  Integer atomics: the image is bit-identical whatever the order of the
+ * points.  N <= 2^18 points per cloud (DG_EUNSUPPORTED above: the codec's range), |value| <= 8.
+ * dg_splat_accum: bilinear_rasterizer  render.py:67-127 without the final layout.  coords [B,N,2] fp32 (coordinate 0 = row),
+ * values [B,N,C] fp32, C <= 4: per point the four neighbouring cells at the clamped indices; a weight is zero where the clamp
+ * moved the index, a corner weight below 1e-3 is zero.  A point with a non-finite coordinate is skipped (the reference's
+ * .long() of NaN is undefined), and so is a non-finite term.
+ * dg_render_points: render_point_clouds  render.py:26-62 up to the splat, per point, inputs untouched.  xyz, normals [B,N,3]
+ * fp32; z flipped; @ R ([3,3], or [B,3,3] with R_batched; nullable); + t ([3], or [B,3] with t_batched; nullable); uv = (x/z,
+ * y/z) focal + 0.5, times L; the in-image mask 0 < uv < L-1 on the normals only; uv = L - uv; weight = exp(-3 |xyz|) (|xyz| >
+ * 1e-8); (weight normals, weight) splatted as C = 4 into acc [B,L,L,4].  Per-point arithmetic in double.
+ * dg_splat_finish: out [B,C,H,W] fp32 = the words' values; normalize = 1: channels 0..C-2 divided by (channel C-1 + 1e-8)
+ * (render.py:62-63, utils/lidar.py:101-102), channel C-1 as is.  Zeroes acc.
+ * dg_image_grid: x [B,C,H,W] fp32 (C = 1 or 3; sample_stride floats between samples, >= C H W: a channel slice of a larger
+ * tensor is read in place) times scale -> out uint8 [Hg,Wg,3] laid out as torchvision's make_grid(nrow=4, padding=2,
+ * pad_value=0): xmaps = min(4,B), ymaps = ceil(B/xmaps), Hg = ymaps (H+2) + 2, Wg = xmaps (W+2) + 2, tile k at row (k / xmaps)
+ * (H+2) + 2, column (k % xmaps) (W+2) + 2.  color = 1: channel 0 through matplotlib's Normalize(0,1) and the 256-entry turbo
+ * table (index floor(v 256) clipped to 0..255, NaN -> (0,0,0)), the padding too (turbo(0)); color = 0: the channel
+ * replicated (C = 1) or the three channels.  Float -> byte = clip(v 255, 0, 255) truncated (TensorBoard's), NaN -> 0.
+ * dg_turbo_lut: the table csrc/turbo_lut.h, 768 floats, into HOST memory (no device needed). */
+int dg_splat_accum(const float* coords, const float* values, int B, long N, int C, int H, int W, unsigned long long* acc,
+                   void* stream);
+int dg_render_points(const float* xyz, const float* normals, int B, long N, int L, const float* R, int R_batched, const float* t,
+                     int t_batched, double focal, unsigned long long* acc, void* stream);
+int dg_splat_finish(unsigned long long* acc, int B, int C, int H, int W, int normalize, float* out, void* stream);
+int dg_image_grid(const float* x, long sample_stride, int B, int C, int H, int W, float scale, int color, unsigned char* out,
+                  void* stream);
+int dg_turbo_lut(float* host_out);
+
 /* ---- validation metrics (the reference's CUDA extensions and their torch drivers) -------
  * dg_fps: furthest point sampling  utils/sampling/fps/furthest_point_sampling.cu:97-207 (+ gather_points :38-60 when
  * `out` is given).  xyz [B,n,3] fp32, m <= n samples per cloud, temp [B,n] fp32 workspace, idx [B,m] int32, out
