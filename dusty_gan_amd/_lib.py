@@ -168,10 +168,6 @@ PROTOTYPES = {
     "dg_fetch_reals_pool_sum": [_P, _P, _P, _I, _F, _F, _F, _I, _L, _P, _P, _P],
     "dg_fetch_reals_resident_sum": [_P, _P, _L, _P, _F, _F, _F, _I, _L, _P, _P, _P],
     "dg_resident_gather": [_P, _L, _I, _L, _L, _P, _P, _P, _P],
-    "dg_nsgan_d": [_P, _P, _I, _F, _P, _P, _P, _P],
-    "dg_nsgan_g": [_P, _I, _F, _P, _P, _P],
-    "dg_nsgan_d_step": [_P, _P, _I, _F, _P, _P, _P, _P, _P, _P],
-    "dg_nsgan_g_step": [_P, _I, _F, _P, _P, _P],
     "dg_gan_d_step": [_I, _F, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P],
     "dg_gan_g_step": [_I, _P, _P, _I, _F, _P, _P, _P],
     "dg_final_gan_bwd": [_I, _I, _F, _P, _P, _I, _F, _I, _P, _P, _P, _P, _P, _P, _I, _P, _F, _L, _I, _P, _P, _P, _P, _P],

@@ -293,7 +293,7 @@ __device__ __forceinline__ void dg_acc_add(float* dst, float v, unsigned contrib
 //   conv_direct, conv_mfma   u64 pair (2i, 2i+1) = channel i in dg_fix2 form; the ticket in the LAST u64
 //   thin_smallk_kernel       u64 word i < 64 = channel n_base + i in 32.32; the ticket in u64 word 64
 //   thin_s2_mfma_kernel      per slot of DG_DBIAS_SLOT_FLOATS floats: floats 0..63 = float channel sums, the ticket at float 64
-// head_post_bwd4_kernel's bias_ws (DG_BIAS_WS_SAMPLE_FLOATS per sample): u64 word h < 3 = head h in 32.32, the ticket in u64
+// head_post_bwd_kernel<.., PX = 4>'s bias_ws (DG_BIAS_WS_SAMPLE_FLOATS per sample): u64 word h < 3 = head h in 32.32, the ticket in u64
 // word 3; the launch's accumulators, in the same form, at float DG_BIAS_WS_ACC (the upper half of sample 0's slot).
 #define DG_DBIAS_WS_WORDS (DG_DBIAS_SLOTS * DG_DBIAS_SLOT_FLOATS / 2)
 #define DG_BIAS_WS_SAMPLE_FLOATS 1024
@@ -325,7 +325,7 @@ __device__ __forceinline__ void dg_dbias_ws_finish(float* ws, int bias_mod, floa
 }
 
 // tanh for the depth head (Generator.forward, models/gans/dcgan_eqlr.py:71) in ~17 VALU instructions: libm's tanhf made
-// head_post_fwd4_kernel VALU-bound (8.4 M pixels x ~45 instructions = the whole 11 us of the launch, round 6).
+// head_post_fwd_kernel<.., PX = 4> VALU-bound (8.4 M pixels x ~45 instructions = the whole 11 us of the launch, round 6).
 //   |x| >= 0.25: (1 - e) / (1 + e) with e = exp(-2 |x|) in (0, 0.61]: no cancellation, ~2 ulp
 //   |x| <  0.25: the odd Taylor polynomial through x^9 (next term < 9e-9 relative at 0.25)
 __device__ __forceinline__ float dg_tanh(float x) {

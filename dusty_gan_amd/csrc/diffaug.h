@@ -1,6 +1,6 @@
 // DiffAugment's geometry and arithmetic, written ONCE (utils/diff_augment.py:114-132, p = 1) for every kernel that evaluates it:
 // the forward gathers and the adjoint's sum and gather (blur_aug.hip), the BlurVH adjoint's window sum (blur_aug.hip) and the
-// head post-processing's backward, which applies the adjoint gather on the fly (pointwise.hip, HeadGradAug).  Every one of the
+// head post-processing's backward, which applies the adjoint gather on the fly (head_post.hip, HeadGradAug).  Every one of the
 // reference's quirks lives here and nowhere else: the applied factor is u * u, the translation wraps columns
 // modulo W - 1, so that output columns 0 and W - 1 read the same source column, and shifted-out rows read zero.
 // policy bits: 1 brightness, 2 saturation (identity for one channel), 4 contrast, 8 translation, 16 cutout.
@@ -115,14 +115,16 @@ __device__ __forceinline__ float aug_adj_px(const AugP& a, const AugSample& s, c
   return (a.policy & 4) ? s.cc * g2 + gm : g2;
 }
 
-// Where head_post_bwd4_kernel (pointwise.hip) gets d loss / d depth of a pixel quad from when DiffAugment's adjoint gather is
+// Where head_post_bwd_kernel (head_post.hip) gets d loss / d depth of a pixel quad from when DiffAugment's adjoint gather is
 // applied on the fly to the BlurVH adjoint's output gy (W % 4 == 0, so a quad lies in one row): the generator's upstream
 // gradient is then never written.
 struct HeadGradAug {
   AugP a;
   const float* gy;
   const float* gsum;
-  __device__ __forceinline__ float4 operator()(int b, long p, long HW) const {
+  template <int PX>
+  __device__ __forceinline__ void operator()(int b, long p, long HW, float (&o)[PX]) const {
+    static_assert(PX == 4, "the adjoint gather serves the four-pixel backward only");
     const int W = a.W;
     const int row = (int)(p / W), q0 = (int)(p - (long)row * W);
     const AugSample s = aug_sample(a, b);
@@ -130,9 +132,7 @@ struct HeadGradAug {
     const float gm = aug_adj_gm(a, s, (a.policy & 4) ? gsum[b] : 0.f);
     const float* grow = gy + (long)b * HW + (long)(r.ok ? r.y : 0) * W;
     const float gb = grow[W - 1];
-    float o[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) o[k] = aug_adj_px(a, s, r, grow, gb, gm, q0 + k);
-    return make_float4(o[0], o[1], o[2], o[3]);
   }
 };

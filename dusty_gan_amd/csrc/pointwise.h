@@ -1,4 +1,4 @@
-// What the pointwise translation units (pointwise.hip, blur_aug.hip, step_inputs.hip) share: 16-byte accesses of feature-map
+// What the pointwise translation units (pointwise.hip, head_post.hip, blur_aug.hip, step_inputs.hip) share: 16-byte accesses of feature-map
 // elements and the launchers' block arithmetic.
 #pragma once
 #include "common.h"

@@ -1,8 +1,7 @@
-// HBM-bound kernels of the step's network end: the final (4 x w0) dot, head post-processing (tanh + Gumbel point-drop), the GAN
-// losses, the path-length penalty, small reductions and zero-fills; and the registration of the accumulator arena.  (BlurVH,
-// DiffAugment and sample_sum: blur_aug.hip; fetch_reals: step_inputs.hip.)  Images are fp32 [B,1,H,W]; feature maps are T.
+// HBM-bound kernels of the step's network end: the final (4 x w0) dot, the GAN losses, the path-length penalty, small reductions
+// and zero-fills; and the registration of the accumulator arena.  (Head post-processing: head_post.hip; BlurVH, DiffAugment and
+// sample_sum: blur_aug.hip; fetch_reals: step_inputs.hip.)  Images are fp32 [B,1,H,W]; feature maps are T.
 #include "pointwise.h"
-#include "diffaug.h"   // (HeadGradAug: DiffAugment's adjoint gather inside the head post-processing's backward)
 
 // ----------------------------------------------------------------------------------------------------------
 // Final EqualLR(Conv2d(C,1,(h0,w0))) (models/gans/dcgan_eqlr.py:95): y[b] = scale * <d4[b], wf> + bias.
@@ -155,420 +154,8 @@ __global__ void batch_wsum_scalar_kernel(const T* __restrict__ src, const float*
 }
 
 // ----------------------------------------------------------------------------------------------------------
-// Head post-processing: Generator.forward's tanh (models/gans/dcgan_eqlr.py:71) + DUSty maskout
-// (models/dusty.py:77-91, 107-127).  gout [B,1+k,H,W] planar fp32: ch0 raw depth -> tanh in place (depth_orig),
-// ch1.. confidence logits (kept).  arch: 0 none, 1 dusty1, 2 dusty2.  noise_pixel [B,H,W], noise_image [B].
-// dsum != nullptr: dsum[b] += sum of depth[b] - the per-sample sum DiffAugment's contrast needs of its input, produced where
-// the image is produced.  A block then owns `chunk` consecutive pixels of ONE sample (HW % chunk == 0) and issues one atomic:
-// with one block per 256 pixels the 8192 atomics on 32 addresses cost 80 us (round 1 met the same in head_post_bwd).
-template <int arch>
-__device__ __forceinline__ float head_post_px(float* __restrict__ gout, const float* __restrict__ noise_pixel,
-                                              const float* __restrict__ noise_image, int training,
-                                              float inv_tau, float drop_const, long HW, float* __restrict__ mask,
-                                              int b, long p) {
-  const long idx = (long)b * HW + p;
-  const int nch = 1 + (arch == 0 ? 0 : arch);
-  float* g = gout + (long)b * nch * HW + p;
-  const float t = dg_tanh(g[0]);
-  g[0] = t;
-  if (arch == 0) return t;
-  const float sp = 1.f / (1.f + __expf(-(g[HW] + noise_pixel[idx]) * inv_tau));
-  const float mp = sp > 0.5f ? 1.f : 0.f;
-  float m = mp;
-  if (arch == 1) {
-    mask[idx] = mp;
-  } else {
-    float mi;
-    if (training) {
-      const float si = 1.f / (1.f + __expf(-(g[2 * HW] + noise_image[b]) * inv_tau));
-      mi = si > 0.5f ? 1.f : 0.f;
-    } else {
-      mi = g[2 * HW] > 0.f ? 1.f : 0.f;
-    }
-    mask[(long)b * 2 * HW + p] = mp;
-    mask[(long)b * 2 * HW + HW + p] = mi;
-    m = mp * mi;
-  }
-  return m * t + (1.f - m) * drop_const;
-}
-// Four consecutive pixels per thread (HW % 1024 == 0, sums wanted): 16-byte loads / stores of every plane; same arithmetic
-// as head_post_px (which remains for other sizes).
-template <int arch>
-__global__ __launch_bounds__(256) void head_post_fwd4_kernel(float* __restrict__ gout, const float* __restrict__ noise_pixel,
-                                      const float* __restrict__ noise_image, int training, float inv_tau,
-                                      float drop_const, int B, long HW, float* __restrict__ mask,
-                                      float* __restrict__ depth, float* __restrict__ dsum, int chunk, const DgDet det) {
-  __shared__ float red[16];
-  const long i0 = (long)blockIdx.x * chunk;
-  const int b = (int)(i0 / HW);
-  const long p0 = i0 - (long)b * HW;
-  constexpr int nch = 1 + (arch == 0 ? 0 : arch);
-  float* g = gout + (long)b * nch * HW + p0;
-  const float ni = (arch == 2 && training) ? noise_image[b] : 0.f;
-  float acc = 0.f;
-  // the loads of four trips issued before the first store (gout is rewritten in place: the compiler cannot hoist a later
-  // trip's loads over an earlier trip's stores, and one load in flight per wave left the launch at a third of the HBM rate)
-  constexpr int U = 4;
-  for (int k0 = threadIdx.x * 4; k0 < chunk; k0 += U * 1024) {
-    float4 g0u[U], g1u[U], npu[U], g2u[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int k = k0 + u * 1024;
-      if (k < chunk) {
-        g0u[u] = *(const float4*)(g + k);
-        if (arch >= 1) { g1u[u] = *(const float4*)(g + HW + k); npu[u] = *(const float4*)(noise_pixel + (long)b * HW + p0 + k); }
-        if (arch == 2) g2u[u] = *(const float4*)(g + 2 * HW + k);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-    const int k = k0 + u * 1024;
-    if (k >= chunk) break;
-    const float4 g0 = g0u[u];
-    float t[4] = {dg_tanh(g0.x), dg_tanh(g0.y), dg_tanh(g0.z), dg_tanh(g0.w)};
-    *(float4*)(g + k) = make_float4(t[0], t[1], t[2], t[3]);
-    float dv[4] = {t[0], t[1], t[2], t[3]};
-    if (arch >= 1) {
-      const float4 g1 = g1u[u], np = npu[u];
-      const float l1[4] = {g1.x + np.x, g1.y + np.y, g1.z + np.z, g1.w + np.w};
-      float mp[4], m[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float sp = 1.f / (1.f + __expf(-l1[q] * inv_tau));
-        mp[q] = sp > 0.5f ? 1.f : 0.f;
-        m[q] = mp[q];
-      }
-      if (arch == 1) {
-        *(float4*)(mask + (long)b * HW + p0 + k) = make_float4(mp[0], mp[1], mp[2], mp[3]);
-      } else {
-        const float4 g2 = g2u[u];
-        const float l2[4] = {g2.x, g2.y, g2.z, g2.w};
-        float mi[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (training) {
-            const float si = 1.f / (1.f + __expf(-(l2[q] + ni) * inv_tau));
-            mi[q] = si > 0.5f ? 1.f : 0.f;
-          } else {
-            mi[q] = l2[q] > 0.f ? 1.f : 0.f;
-          }
-          m[q] = mp[q] * mi[q];
-        }
-        *(float4*)(mask + (long)b * 2 * HW + p0 + k) = make_float4(mp[0], mp[1], mp[2], mp[3]);
-        *(float4*)(mask + (long)b * 2 * HW + HW + p0 + k) = make_float4(mi[0], mi[1], mi[2], mi[3]);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) dv[q] = m[q] * t[q] + (1.f - m[q]) * drop_const;
-    }
-    *(float4*)(depth + i0 + k) = make_float4(dv[0], dv[1], dv[2], dv[3]);
-    acc += (dv[0] + dv[1]) + (dv[2] + dv[3]);
-    }
-  }
-  const float sblk = dg_block_sum(acc, red);
-  if (threadIdx.x == 0) dg_acc_add(&dsum[b], sblk, (unsigned)(HW / chunk), det);
-}
-
-template <int arch>   // compile-time: the pixel function is then straight-line code and the unrolled trips batch their loads
-__global__ __launch_bounds__(256) void head_post_fwd_kernel(float* __restrict__ gout, const float* __restrict__ noise_pixel,
-                                     const float* __restrict__ noise_image, int training, float inv_tau,
-                                     float drop_const, int B, long HW, float* __restrict__ mask,
-                                     float* __restrict__ depth, float* __restrict__ dsum, int chunk, const DgDet det) {
-  __shared__ float red[16];
-  if (!dsum) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < (long)B * HW) {
-      const int b = (int)(idx / HW);
-      depth[idx] = head_post_px<arch>(gout, noise_pixel, noise_image, training, inv_tau, drop_const, HW, mask, b, idx - (long)b * HW);
-    }
-    return;
-  }
-  // the block's pixels belong to ONE sample (HW % chunk == 0): the sample index is block-uniform, and the four pixels a
-  // thread handles per trip are independent - unrolled so that their loads are in flight together (a 64-bit division per
-  // pixel and one round trip per pixel made this 15 us for 25 MB)
-  const long i0 = (long)blockIdx.x * chunk;
-  const int b = (int)(i0 / HW);
-  const long p0 = i0 - (long)b * HW;
-  float acc = 0.f;
-#pragma unroll 4
-  for (int k = threadIdx.x; k < chunk; k += 256) {
-    const float dv = head_post_px<arch>(gout, noise_pixel, noise_image, training, inv_tau, drop_const, HW, mask, b, p0 + k);
-    depth[i0 + k] = dv;
-    acc += dv;
-  }
-  const float sblk = dg_block_sum(acc, red);
-  if (threadIdx.x == 0) dg_acc_add(&dsum[b], sblk, (unsigned)(HW / chunk), det);
-}
-
-// Backward of the above: ddepth [B,H,W] -> draw [B,1+k,H,W] planar (gradient w.r.t. the head conv outputs).
-template <int arch, int CP>   // CP: 0 no pixel-major copy, 2 / 4 that padded channel count, 1 any other (`cp`)
-__global__ __launch_bounds__(256) void head_post_bwd_kernel(const float* __restrict__ gout, const float* __restrict__ noise_pixel,
-                                     const float* __restrict__ noise_image, const float* __restrict__ mask,
-                                     const float* __restrict__ ddepth, float inv_tau, float drop_const,
-                                     int B, long HW, float s_depth, float s_conf, float* __restrict__ draw,
-                                     float* __restrict__ dbias, bf16* __restrict__ draw_pm, int cp) {
-  __shared__ float red[16];
-  // grid-stride: a block covers many pixels so that the bias-gradient sums cost one atomic per block per head (one
-  // pixel per thread meant 8192 atomics on the same address: 100 us of the 108 us this kernel took at B = 32)
-  // blockIdx.y = sample (no 64-bit division per pixel); straight-line body (arch and the copy's layout are compile-time),
-  // four independent pixels per trip in flight together
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-  const int b = blockIdx.y;
-#pragma unroll 4
-  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += (long)gridDim.x * blockDim.x) {
-  const long idx = (long)b * HW + p;
-  float d0 = 0.f, d1 = 0.f, d2 = 0.f;  // unscaled gradients w.r.t. the head outputs (= the head bias gradients)
-  {
-  const int nch = 1 + (arch == 0 ? 0 : arch);
-  const float* g = gout + (long)b * nch * HW + p;
-  float* d = draw + (long)b * nch * HW + p;
-  const float t = g[0];
-  const float dt = 1.f - t * t;
-  const float go = ddepth[idx];
-  if (arch == 0) {
-    d0 = go * dt;
-  } else {
-    const float sp = 1.f / (1.f + __expf(-(g[HW] + noise_pixel[idx]) * inv_tau));
-    const float dmask = go * (t - drop_const);
-    if (arch == 1) {
-      const float mp = mask[idx];
-      d0 = mp * go * dt;
-      d1 = dmask * sp * (1.f - sp) * inv_tau;
-    } else {
-      const float mp = mask[(long)b * 2 * HW + p], mi = mask[(long)b * 2 * HW + HW + p];
-      const float si = 1.f / (1.f + __expf(-(g[2 * HW] + noise_image[b]) * inv_tau));
-      d0 = mp * mi * go * dt;
-      d1 = dmask * mi * sp * (1.f - sp) * inv_tau;
-      d2 = dmask * mp * si * (1.f - si) * inv_tau;
-      d[2 * HW] = d2 * s_conf;
-    }
-    d[HW] = d1 * s_conf;
-  }
-  d[0] = d0 * s_depth;
-  if (CP != 0) {  // second copy, pixel-major / channel-minor bf16 [B,H,W,cp], channels zero-padded: the operand layout
-                  // of the MFMA backward-data kernel (thin_s2_mfma); one store per pixel for cp = 2 / 4
-    const unsigned short h0 = __builtin_bit_cast(unsigned short, (bf16)(d0 * s_depth));
-    const unsigned short h1 = __builtin_bit_cast(unsigned short, (bf16)(arch >= 1 ? d1 * s_conf : 0.f));
-    const unsigned short h2 = __builtin_bit_cast(unsigned short, (bf16)(arch >= 2 ? d2 * s_conf : 0.f));
-    if (CP == 2) {
-      *(unsigned*)(draw_pm + idx * 2) = (unsigned)h0 | ((unsigned)h1 << 16);
-    } else if (CP == 4) {
-      *(uint2*)(draw_pm + idx * 4) = make_uint2((unsigned)h0 | ((unsigned)h1 << 16), (unsigned)h2);
-    } else {      // any other padded channel count
-      bf16* q = draw_pm + idx * cp;
-      q[0] = __builtin_bit_cast(bf16, h0);
-      if (cp > 1) q[1] = __builtin_bit_cast(bf16, h1);
-      if (cp > 2) q[2] = __builtin_bit_cast(bf16, h2);
-      for (int c = 3; c < cp; ++c) q[c] = (bf16)0.f;
-    }
-  }
-  }
-  a0 += d0; a1 += d1; a2 += d2;
-  }
-  if (dbias) {  // head biases are outside EqualLR's input scaling: their gradient is the unscaled sum
-    const float s0 = dg_block_sum(a0, red);
-    if (threadIdx.x == 0) atomicAdd(&dbias[0], s0);
-    if (arch >= 1) { const float s1 = dg_block_sum(a1, red); if (threadIdx.x == 0) atomicAdd(&dbias[1], s1); }
-    if (arch >= 2) { const float s2 = dg_block_sum(a2, red); if (threadIdx.x == 0) atomicAdd(&dbias[2], s2); }
-  }
-}
-
-// Where head_post_bwd4_kernel gets d loss / d depth of a pixel quad from: the tensor itself, or - HeadGradAug, diffaug.h -
-// DiffAugment's adjoint gather applied on the fly to the BlurVH adjoint's output.
-struct HeadGradPlain {
-  const float* ddepth;
-  __device__ __forceinline__ float4 operator()(int b, long p, long HW) const { return *(const float4*)(ddepth + (long)b * HW + p); }
-};
-
-// Four consecutive pixels per thread (HW % 4 == 0): 16-byte loads of every plane, 16-byte stores; `draw` (the planar fp32
-// copy) may be null - the bf16 path consumes only the pixel-major copy, and three 8 MB planes were written for nobody.
-template <int arch, int CP, typename DD>   // CP: 2 / 4 padded channel count of the pixel-major copy, 0 none
-__global__ __launch_bounds__(256) void head_post_bwd4_kernel(const float* __restrict__ gout, const float* __restrict__ noise_pixel,
-                                      const float* __restrict__ noise_image, const float* __restrict__ mask,
-                                      DD ddepth, float inv_tau, float drop_const, int B, long HW,
-                                      float s_depth, float s_conf, float* __restrict__ draw, float* __restrict__ dbias,
-                                      bf16* __restrict__ draw_pm, float* __restrict__ bias_ws) {
-  __shared__ float red[16];
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-  const int b = blockIdx.y;
-  constexpr int nch = 1 + (arch == 0 ? 0 : arch);
-  const float* g = gout + (long)b * nch * HW;
-  const float ni = arch == 2 ? noise_image[b] : 0.f;
-  auto ld = [](const float* q) { const float4 v = *(const float4*)q; return v; };
-  for (long p = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4; p < HW; p += (long)gridDim.x * blockDim.x * 4) {
-    const long idx = (long)b * HW + p;
-    const float4 t4 = ld(g + p), go4 = ddepth(b, p, HW);
-    const float t[4] = {t4.x, t4.y, t4.z, t4.w}, go[4] = {go4.x, go4.y, go4.z, go4.w};
-    float d0[4], d1[4] = {0.f, 0.f, 0.f, 0.f}, d2[4] = {0.f, 0.f, 0.f, 0.f};
-    if (arch == 0) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) d0[q] = go[q] * (1.f - t[q] * t[q]);
-    } else {
-      const float4 g14 = ld(g + HW + p), np4 = ld(noise_pixel + idx);
-      const float l1[4] = {g14.x + np4.x, g14.y + np4.y, g14.z + np4.z, g14.w + np4.w};
-      float mp[4], mi[4] = {1.f, 1.f, 1.f, 1.f}, l2[4] = {0.f, 0.f, 0.f, 0.f};
-      if (arch == 1) {
-        const float4 m4 = ld(mask + idx);
-        mp[0] = m4.x; mp[1] = m4.y; mp[2] = m4.z; mp[3] = m4.w;
-      } else {
-        const float4 m4 = ld(mask + (long)b * 2 * HW + p), i4 = ld(mask + (long)b * 2 * HW + HW + p), g24 = ld(g + 2 * HW + p);
-        mp[0] = m4.x; mp[1] = m4.y; mp[2] = m4.z; mp[3] = m4.w;
-        mi[0] = i4.x; mi[1] = i4.y; mi[2] = i4.z; mi[3] = i4.w;
-        l2[0] = g24.x; l2[1] = g24.y; l2[2] = g24.z; l2[3] = g24.w;
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float dt = 1.f - t[q] * t[q];
-        const float sp = 1.f / (1.f + __expf(-l1[q] * inv_tau));
-        const float dmask = go[q] * (t[q] - drop_const);
-        if (arch == 1) {
-          d0[q] = mp[q] * go[q] * dt;
-          d1[q] = dmask * sp * (1.f - sp) * inv_tau;
-        } else {
-          const float si = 1.f / (1.f + __expf(-(l2[q] + ni) * inv_tau));
-          d0[q] = mp[q] * mi[q] * go[q] * dt;
-          d1[q] = dmask * mi[q] * sp * (1.f - sp) * inv_tau;
-          d2[q] = dmask * mp[q] * si * (1.f - si) * inv_tau;
-        }
-      }
-    }
-    if (draw) {
-      float* d = draw + (long)b * nch * HW + p;
-      *(float4*)d = make_float4(d0[0] * s_depth, d0[1] * s_depth, d0[2] * s_depth, d0[3] * s_depth);
-      if (arch >= 1) *(float4*)(d + HW) = make_float4(d1[0] * s_conf, d1[1] * s_conf, d1[2] * s_conf, d1[3] * s_conf);
-      if (arch >= 2) *(float4*)(d + 2 * HW) = make_float4(d2[0] * s_conf, d2[1] * s_conf, d2[2] * s_conf, d2[3] * s_conf);
-    }
-    if (CP != 0) {
-      unsigned w01[4], w2[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const unsigned short h0 = __builtin_bit_cast(unsigned short, (bf16)(d0[q] * s_depth));
-        const unsigned short h1 = __builtin_bit_cast(unsigned short, (bf16)(arch >= 1 ? d1[q] * s_conf : 0.f));
-        const unsigned short h2 = __builtin_bit_cast(unsigned short, (bf16)(arch >= 2 ? d2[q] * s_conf : 0.f));
-        w01[q] = (unsigned)h0 | ((unsigned)h1 << 16);
-        w2[q] = (unsigned)h2;
-      }
-      if (CP == 2) {
-        *(uint4*)(draw_pm + idx * 2) = make_uint4(w01[0], w01[1], w01[2], w01[3]);
-      } else {
-        *(uint4*)(draw_pm + idx * 4) = make_uint4(w01[0], w2[0], w01[1], w2[1]);
-        *(uint4*)(draw_pm + idx * 4 + 8) = make_uint4(w01[2], w2[2], w01[3], w2[3]);
-      }
-    }
-    a0 += (d0[0] + d0[1]) + (d0[2] + d0[3]);
-    a1 += (d1[0] + d1[1]) + (d1[2] + d1[3]);
-    a2 += (d2[0] + d2[1]) + (d2[2] + d2[3]);
-  }
-  if (dbias) {
-    // Atomics on ONE address retire at ~10 ns each (they execute memory-side): a thousand blocks adding straight into
-    // dbias[n] cost 10 us per head - more than the pass over the data.  With `bias_ws` (4 KB per sample, zero on entry and
-    // left zero) the blocks of a sample add into that sample's slot - B independent addresses - and the last one to
-    // arrive (a ticket in the slot) folds the slot into dbias: gridDim.x adds per slot, B per dbias[n].
-    const float s0 = dg_block_sum(a0, red);
-    const float s1 = arch >= 1 ? dg_block_sum(a1, red) : 0.f;
-    const float s2 = arch >= 2 ? dg_block_sum(a2, red) : 0.f;
-    if (threadIdx.x == 0) {
-      if (bias_ws && gridDim.x > 1) {
-        // Round 5: the staged sums are 32.32 FIXED POINT (integer adds commute: the total no longer depends on the order in
-        // which blocks and samples arrive - common.h has the protocol and its argument).  Two levels, as before: the blocks of a
-        // sample add into that sample's slot; the last block of a sample (ticket) moves the slot's totals, still integers,
-        // into the launch's accumulators (upper half of slot 0) and takes a second ticket; the last SAMPLE converts and adds
-        // each head's total to dbias once.  Everything is left zero.
-        unsigned long long* w = (unsigned long long*)(bias_ws + (long)b * DG_BIAS_WS_SAMPLE_FLOATS);
-        unsigned long long* gacc = (unsigned long long*)(bias_ws + DG_BIAS_WS_ACC);
-        const float sv[3] = {s0, s1, s2};
-#pragma unroll
-        for (int h = 0; h <= arch; ++h) {
-          long long q;
-          if (dg_fix1(sv[h], q)) atomicAdd(&w[h], (unsigned long long)q);
-          else atomicAdd(&dbias[h], sv[h]);
-        }
-        if (dg_ticket_last(dg_bias_ws_ticket(w), gridDim.x)) {
-#pragma unroll
-          for (int h = 0; h <= arch; ++h) atomicAdd(&gacc[h], atomicExch(&w[h], 0ull));
-          if (dg_ticket_last(dg_bias_ws_ticket(gacc), gridDim.y)) {
-#pragma unroll
-            for (int h = 0; h <= arch; ++h) atomicAdd(&dbias[h], dg_fix1_value((long long)atomicExch(&gacc[h], 0ull)));
-          }
-        }
-      } else {
-        atomicAdd(&dbias[0], s0);
-        if (arch >= 1) atomicAdd(&dbias[1], s1);
-        if (arch >= 2) atomicAdd(&dbias[2], s2);
-      }
-    }
-  }
-}
-
-// ----------------------------------------------------------------------------------------------------------
-// Path-length regularisation (trainers/dcgan_amp.py:268-306), the pieces that are not convolutions.
-//
-// head_post_bwd2_kernel: the SECOND-order part of the head post-processing.  With x = depth output, h = the head conv
-// outputs (h0 raw depth, h1 / h2 confidence logits), y the upstream of x and th the forward-mode tangent of h along
-// the latent direction v, the tangent of the first-order backward d x / d h_i * y is  y * sum_j H_ij th_j  with H the
-// Hessian of x in h as autograd sees it (hard masks carry the straight-through derivative sp' = sp (1 - sp) / tau,
-// which is itself differentiable: sp'' = sp' (1 - 2 sp) / tau):
-//   H00 = m (-2 t)(1 - t^2)   H01 = mi sp' (1 - t^2)   H02 = mp si' (1 - t^2)
-//   H11 = (t - c) mi sp''     H12 = (t - c) sp' si'    H22 = (t - c) mp si''        (t = tanh h0, c = drop_const)
-// Outputs as head_post_bwd_kernel: draw2 (scaled by the head's EqualLR scale), the pixel-major bf16 copy, and the
-// head-bias gradient sums.
-__global__ void head_post_bwd2_kernel(const float* __restrict__ gout, const float* __restrict__ noise_pixel,
-                                      const float* __restrict__ noise_image, const float* __restrict__ mask,
-                                      const float* __restrict__ ddepth, const float* __restrict__ thead, int arch,
-                                      float inv_tau, float drop_const, int B, long HW, float s_depth, float s_conf,
-                                      float* __restrict__ draw, float* __restrict__ dbias, bf16* __restrict__ draw_pm,
-                                      int cp) {
-  __shared__ float red[16];
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < (long)B * HW; idx += (long)gridDim.x * blockDim.x) {
-    const int b = (int)(idx / HW);
-    const long p = idx - (long)b * HW;
-    const int nch = 1 + (arch == 0 ? 0 : arch);
-    const float* g = gout + (long)b * nch * HW + p;
-    const float* th = thead + (long)b * nch * HW + p;
-    float* d = draw + (long)b * nch * HW + p;
-    const float t = g[0], dt = 1.f - t * t, y = ddepth[idx];
-    const float t0 = th[0];
-    float d0, d1 = 0.f, d2 = 0.f;
-    if (arch == 0) {
-      d0 = y * (-2.f * t * dt) * t0;
-    } else {
-      const float sp = 1.f / (1.f + __expf(-(g[HW] + noise_pixel[idx]) * inv_tau));
-      const float sp1 = sp * (1.f - sp) * inv_tau, sp2 = sp1 * (1.f - 2.f * sp) * inv_tau;
-      const float t1 = th[HW], tc = t - drop_const;
-      if (arch == 1) {
-        const float mp = mask[idx];
-        d0 = y * (mp * (-2.f * t * dt) * t0 + sp1 * dt * t1);
-        d1 = y * (sp1 * dt * t0 + tc * sp2 * t1);
-      } else {
-        const float mp = mask[(long)b * 2 * HW + p], mi = mask[(long)b * 2 * HW + HW + p];
-        const float si = 1.f / (1.f + __expf(-(g[2 * HW] + noise_image[b]) * inv_tau));
-        const float si1 = si * (1.f - si) * inv_tau, si2 = si1 * (1.f - 2.f * si) * inv_tau;
-        const float t2 = th[2 * HW];
-        d0 = y * (mp * mi * (-2.f * t * dt) * t0 + mi * sp1 * dt * t1 + mp * si1 * dt * t2);
-        d1 = y * (mi * sp1 * dt * t0 + tc * mi * sp2 * t1 + tc * sp1 * si1 * t2);
-        d2 = y * (mp * si1 * dt * t0 + tc * sp1 * si1 * t1 + tc * mp * si2 * t2);
-        d[2 * HW] = d2 * s_conf;
-      }
-      d[HW] = d1 * s_conf;
-    }
-    d[0] = d0 * s_depth;
-    if (draw_pm) {
-      bf16* q = draw_pm + idx * cp;
-      q[0] = (bf16)(d0 * s_depth);
-      if (cp > 1) q[1] = (bf16)(arch >= 1 ? d1 * s_conf : 0.f);
-      if (cp > 2) q[2] = (bf16)(arch >= 2 ? d2 * s_conf : 0.f);
-      if (cp > 3) q[3] = (bf16)0.f;
-    }
-    a0 += d0; a1 += d1; a2 += d2;
-  }
-  if (dbias) {
-    const float s0 = dg_block_sum(a0, red);
-    if (threadIdx.x == 0) atomicAdd(&dbias[0], s0);
-    if (arch >= 1) { const float s1 = dg_block_sum(a1, red); if (threadIdx.x == 0) atomicAdd(&dbias[1], s1); }
-    if (arch >= 2) { const float s2 = dg_block_sum(a2, red); if (threadIdx.x == 0) atomicAdd(&dbias[2], s2); }
-  }
-}
-
+// Path-length regularisation (trainers/dcgan_amp.py:268-306), the pieces that are not convolutions (its second-order
+// head post-processing: head_post.hip).
 // |J^T y| per sample, the running baseline and the penalty (:294-300), and v = w * d penalty / d dz, the direction of
 // the forward-over-reverse pass.  pl_ema (device scalar) is updated in place; acc[0] += baseline, acc[1] += penalty.
 // The baseline a = ema + 0.01 (mean l - ema) stays in the graph in the reference (lerp of a live mean), hence the
@@ -611,87 +198,9 @@ __global__ __launch_bounds__(256) void pl_penalty_kernel(const float* __restrict
 }
 
 // ----------------------------------------------------------------------------------------------------------
-// NSGAN losses (models/loss.py:39-41, 68-69) + their gradients w.r.t. the logits; one block.
-// scal[0]=mean(y_real) scal[1]=mean(y_fake) scal[2]=loss_D ; dy_* = d(w_gan*loss_D)/dy
+// The GAN losses' scalar functions.
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(__expf(x)); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + __expf(-x)); }
-
-__global__ __launch_bounds__(256) void nsgan_d_kernel(const float* __restrict__ y_real,
-                                                      const float* __restrict__ y_fake, int B, float w_gan,
-                                                      float* __restrict__ dy_real, float* __restrict__ dy_fake,
-                                                      float* __restrict__ scal) {
-  __shared__ float red[16];
-  float sr = 0.f, sf = 0.f, lr = 0.f, lf = 0.f;
-  for (int i = threadIdx.x; i < B; i += blockDim.x) {
-    const float r = y_real[i], f = y_fake[i];
-    sr += r; sf += f;
-    lr += softplus_f(-r); lf += softplus_f(f);
-    dy_real[i] = -w_gan * sigmoid_f(-r) / (float)B;
-    dy_fake[i] = w_gan * sigmoid_f(f) / (float)B;
-  }
-  const float a = dg_block_sum(sr, red), b = dg_block_sum(sf, red);
-  const float c = dg_block_sum(lr, red), d = dg_block_sum(lf, red);
-  if (threadIdx.x == 0) {
-    scal[0] = a / B; scal[1] = b / B; scal[2] = c / B + d / B;
-  }
-}
-
-// scal[0] = loss_G ; dy = d(w_gan*loss_G)/dy_fake
-__global__ __launch_bounds__(256) void nsgan_g_kernel(const float* __restrict__ y_fake, int B, float w_gan,
-                                                      float* __restrict__ dy, float* __restrict__ scal) {
-  __shared__ float red[16];
-  float l = 0.f;
-  for (int i = threadIdx.x; i < B; i += blockDim.x) {
-    const float f = y_fake[i];
-    l += softplus_f(-f);
-    dy[i] = -w_gan * sigmoid_f(-f) / (float)B;
-  }
-  const float s = dg_block_sum(l, red);
-  if (threadIdx.x == 0) scal[0] = s / B;
-}
-
-// The D-phase bookkeeping around the loss in one launch (trainers/dcgan_amp.py:203-238): loss + dLoss/dy as
-// nsgan_d_kernel, plus the two per-sample vectors the R1 schedule feeds the backward with (up = [1 .. 1 | dy_fake],
-// rs = [dy_real | 1 .. 1]; either may be null), the running sums of the logged scalars (acc[0..2] +=) and the
-// final bias gradient (dfinal_b += sum dy).  Replaces eight tiny torch kernels per step.
-__global__ __launch_bounds__(256) void nsgan_d_step_kernel(const float* __restrict__ y_real,
-                                                           const float* __restrict__ y_fake, int B, float w_gan,
-                                                           float* __restrict__ dy, float* __restrict__ up,
-                                                           float* __restrict__ rs, float* __restrict__ acc,
-                                                           float* __restrict__ dfinal_b) {
-  __shared__ float red[16];
-  float sr = 0.f, sf = 0.f, lr = 0.f, lf = 0.f, sd = 0.f;
-  for (int i = threadIdx.x; i < B; i += blockDim.x) {
-    const float r = y_real[i], f = y_fake[i];
-    sr += r; sf += f;
-    lr += softplus_f(-r); lf += softplus_f(f);
-    const float dr = -w_gan * sigmoid_f(-r) / (float)B, df = w_gan * sigmoid_f(f) / (float)B;
-    dy[i] = dr; dy[B + i] = df;
-    if (up) { up[i] = 1.f; up[B + i] = df; }
-    if (rs) { rs[i] = dr; rs[B + i] = 1.f; }
-    sd += dr + df;
-  }
-  const float a = dg_block_sum(sr, red), b = dg_block_sum(sf, red);
-  const float c = dg_block_sum(lr, red), d = dg_block_sum(lf, red), e = dg_block_sum(sd, red);
-  if (threadIdx.x == 0) {
-    acc[0] += a / B; acc[1] += b / B; acc[2] += c / B + d / B;
-    if (dfinal_b) dfinal_b[0] += e;
-  }
-}
-
-// acc[0] += loss_G ; dy = d(w_gan*loss_G)/dy_fake
-__global__ __launch_bounds__(256) void nsgan_g_step_kernel(const float* __restrict__ y_fake, int B, float w_gan,
-                                                           float* __restrict__ dy, float* __restrict__ acc) {
-  __shared__ float red[16];
-  float l = 0.f;
-  for (int i = threadIdx.x; i < B; i += blockDim.x) {
-    const float f = y_fake[i];
-    l += softplus_f(-f);
-    dy[i] = -w_gan * sigmoid_f(-f) / (float)B;
-  }
-  const float s = dg_block_sum(l, red);
-  if (threadIdx.x == 0) acc[0] += s / B;
-}
 
 // ----------------------------------------------------------------------------------------------------------
 // All seven GANLoss metrics (models/loss.py:39-61 loss_D, :66-85 loss_G) as one kernel.  Every metric is
@@ -740,8 +249,9 @@ static int gan_form(int metric, int mode_g, float smoothing, GanForm* f) {
   return DG_OK;
 }
 
-// One block.  D mode (mode_g = 0): dy = [d/dy_real | d/dy_fake] of w_gan * loss, up / rs / dfinal_b / acc[0..2] as in
-// nsgan_d_step_kernel.  G mode: only the fake half carries a gradient (D(real) is data, trainers/dcgan_amp.py:259);
+// One block.  D mode (mode_g = 0): dy = [d/dy_real | d/dy_fake] of w_gan * loss; the two per-sample vectors the R1 schedule
+// feeds the backward with (up = [1 .. 1 | dy_fake], rs = [dy_real | 1 .. 1]; either may be null); acc[0..2] += (mean y_real,
+// mean y_fake, loss); dfinal_b += sum dy (the final conv's bias gradient; may be null).  G mode: only the fake half carries a gradient (D(real) is data, trainers/dcgan_amp.py:259);
 // dy = d(w_gan * loss)/dy_fake, acc[0] += loss; y_real may be null unless the metric is relativistic.
 // `red` >= 17 floats of LDS.  dy / up / rs may be LDS (the fused final-layer kernel: every block evaluates the step for
 // itself) or global memory; `write_acc`: add the scalars / the final bias gradient (one block only).
@@ -967,26 +477,6 @@ int dg_zero_f32(float* p, long n, hipStream_t s) {
   return DG_OK;
 }
 
-template <typename DD>
-static int head_post_bwd4_launch(DD dd, const float* gout, const float* noise_pixel, const float* noise_image,
-                                 const float* mask, int arch, float tau, float drop_const, int B, long HW, float s_depth,
-                                 float s_conf, float* draw, float* dbias, void* draw_pm, int cpk, float* bias_ws,
-                                 hipStream_t s) {
-  const unsigned per = B >= 1024 ? 1u : (unsigned)(1024 / B);
-  unsigned hb4 = nblk(HW / 4);
-  if (hb4 > per) hb4 = per;
-  const dim3 grid4(hb4, B);
-#define DG_HPB4(A, C)                                                                                                    \
-  head_post_bwd4_kernel<A, C, DD><<<grid4, 256, 0, s>>>(gout, noise_pixel, noise_image, mask, dd, 1.f / tau, drop_const,   \
-                                                        B, HW, s_depth, s_conf, draw, dbias, (bf16*)draw_pm, bias_ws)
-#define DG_HPB4_A(A) do { if (cpk == 0) DG_HPB4(A, 0); else if (cpk == 2) DG_HPB4(A, 2); else DG_HPB4(A, 4); } while (0)
-  if (arch == 0) DG_HPB4_A(0); else if (arch == 1) DG_HPB4_A(1); else DG_HPB4_A(2);
-#undef DG_HPB4_A
-#undef DG_HPB4
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
 extern "C" {
 
 // k <= 4 fp32 buffers (16-byte aligned, counts multiples of 4) zero-filled by one launch
@@ -1077,130 +567,9 @@ int dg_batch_wsum(const void* src, int dtype, const float* coef, float scale, in
   return DG_OK;
 }
 
-static int head_post_fwd_impl(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
-                              float tau, float drop_const, int B, long HW, float* mask, float* depth, float* dsum, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  if (arch < 0 || arch > 2) return DG_EINVAL;
-  if (dsum && HW % 256 != 0) return DG_EUNSUPPORTED;
-  const int chunk = dsum ? sum_chunk(HW) : 256;
-  const DgDet det = dg_det_current();
-  const unsigned nb = nblk((long)B * HW, chunk);
-  if (dsum && chunk % 1024 == 0 && ((size_t)gout & 15) == 0 && ((size_t)depth & 15) == 0 && ((size_t)mask & 15) == 0 &&
-      ((size_t)noise_pixel & 15) == 0) {
-    if (arch == 0)
-      head_post_fwd4_kernel<0><<<nb, 256, 0, s>>>(gout, noise_pixel, noise_image, training, 1.f / tau, drop_const, B, HW, mask, depth, dsum, chunk, det);
-    else if (arch == 1)
-      head_post_fwd4_kernel<1><<<nb, 256, 0, s>>>(gout, noise_pixel, noise_image, training, 1.f / tau, drop_const, B, HW, mask, depth, dsum, chunk, det);
-    else
-      head_post_fwd4_kernel<2><<<nb, 256, 0, s>>>(gout, noise_pixel, noise_image, training, 1.f / tau, drop_const, B, HW, mask, depth, dsum, chunk, det);
-    HIP_CHECK_RET(hipGetLastError());
-    return DG_OK;
-  }
-  if (arch == 0)
-    head_post_fwd_kernel<0><<<nb, 256, 0, s>>>(gout, noise_pixel, noise_image, training, 1.f / tau, drop_const, B, HW, mask, depth, dsum, chunk, det);
-  else if (arch == 1)
-    head_post_fwd_kernel<1><<<nb, 256, 0, s>>>(gout, noise_pixel, noise_image, training, 1.f / tau, drop_const, B, HW, mask, depth, dsum, chunk, det);
-  else
-    head_post_fwd_kernel<2><<<nb, 256, 0, s>>>(gout, noise_pixel, noise_image, training, 1.f / tau, drop_const, B, HW, mask, depth, dsum, chunk, det);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-int dg_head_post_fwd(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
-                     float tau, float drop_const, int B, long HW, float* mask, float* depth, void* s_) {
-  return head_post_fwd_impl(gout, noise_pixel, noise_image, arch, training, tau, drop_const, B, HW, mask, depth, nullptr, s_);
-}
-// ... + dsum[b] += sum of depth[b] (dsum zeroed by the caller; HW % 256 == 0 or DG_EUNSUPPORTED): the per-sample sums
-// that dg_diffaug_fwd_pre takes instead of making its own pass over the image
-int dg_head_post_fwd_sum(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
-                         float tau, float drop_const, int B, long HW, float* mask, float* depth, float* dsum, void* s_) {
-  if (!dsum) return DG_EINVAL;
-  return head_post_fwd_impl(gout, noise_pixel, noise_image, arch, training, tau, drop_const, B, HW, mask, depth, dsum, s_);
-}
-
-int dg_head_post_bwd(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
-                     const float* ddepth, int arch, float tau, float drop_const, int B, long HW, float s_depth,
-                     float s_conf, float* draw, float* dbias, void* draw_pm, int cp, float* bias_ws,
-                     void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  if (arch < 0 || arch > 2) return DG_EINVAL;
-  unsigned hb = nblk(HW);                        // blocks per sample: ~1024 blocks in all, each one atomic per head
-  const unsigned per = B >= 1024 ? 1u : (unsigned)(1024 / B);
-  if (hb > per) hb = per;
-  const dim3 grid(hb, B);
-  const int cpk = !draw_pm ? 0 : (cp == 2 ? 2 : (cp == 4 ? 4 : 1));
-  if (!draw && !draw_pm) return DG_EINVAL;
-  auto al = [](const void* q) { return ((size_t)q & 15) == 0; };
-  if (HW % 4 == 0 && cpk != 1 && al(gout) && al(ddepth) && al(draw) && al(draw_pm) && al(noise_pixel) && al(mask))
-    return head_post_bwd4_launch(HeadGradPlain{ddepth}, gout, noise_pixel, noise_image, mask, arch, tau, drop_const, B, HW,
-                                 s_depth, s_conf, draw, dbias, draw_pm, cpk, bias_ws, s);
-  if (!draw) return DG_EUNSUPPORTED;   // (the scalar kernel always writes the planar copy)
-#define DG_HPB(A, C)                                                                                                   \
-  head_post_bwd_kernel<A, C><<<grid, 256, 0, s>>>(gout, noise_pixel, noise_image, mask, ddepth, 1.f / tau, drop_const, \
-                                                  B, HW, s_depth, s_conf, draw, dbias, (bf16*)draw_pm, cp)
-#define DG_HPB_A(A)                                                                                  \
-  do {                                                                                               \
-    if (cpk == 0) DG_HPB(A, 0); else if (cpk == 2) DG_HPB(A, 2); else if (cpk == 4) DG_HPB(A, 4); else DG_HPB(A, 1); \
-  } while (0)
-  if (arch == 0) DG_HPB_A(0); else if (arch == 1) DG_HPB_A(1); else DG_HPB_A(2);
-#undef DG_HPB_A
-#undef DG_HPB
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-// dg_diffaug_bwd_pre + dg_head_post_bwd in one launch: d loss / d depth is DiffAugment's adjoint gather of gy (the BlurVH
-// adjoint's output; gsum from dg_blur_bwd_augsum), evaluated per pixel quad where the head post-processing's backward
-// needs it - the generator's upstream gradient [B,1,H,W] is never written.  DG_EUNSUPPORTED (nothing launched) unless the
-// four-pixel form applies (W % 4 == 0, 16-byte aligned planes, cp 2 / 4 or no pixel-major copy).
-int dg_head_post_bwd_aug(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
-                         const float* gy, const float* u_b, const float* u_c, const int* t_h, const int* t_w,
-                         const int* o_x, const int* o_y, int policy, const float* gsum, int arch, float tau,
-                         float drop_const, int B, int H, int W, float s_depth, float s_conf, float* draw, float* dbias,
-                         void* draw_pm, int cp, float* bias_ws, void* s_) {
-  if (arch < 0 || arch > 2 || !gy || B <= 0 || H <= 0 || W <= 1) return DG_EINVAL;
-  if (!draw && !draw_pm) return DG_EINVAL;
-  if ((policy & 4) && !gsum) return DG_EINVAL;
-  const int cpk = !draw_pm ? 0 : (cp == 2 ? 2 : (cp == 4 ? 4 : 1));
-  auto al = [](const void* q) { return ((size_t)q & 15) == 0; };
-  if (!(W % 4 == 0 && cpk != 1 && al(gout) && al(draw) && al(draw_pm) && al(noise_pixel) && al(mask))) return DG_EUNSUPPORTED;
-  HeadGradAug dd{make_aug(u_b, u_c, t_h, t_w, o_x, o_y, policy, B, H, W), gy, gsum};
-  return head_post_bwd4_launch(dd, gout, noise_pixel, noise_image, mask, arch, tau, drop_const, B, (long)H * W, s_depth,
-                               s_conf, draw, dbias, draw_pm, cpk, bias_ws, (hipStream_t)s_);
-}
-
-int dg_nsgan_d(const float* y_real, const float* y_fake, int B, float w_gan, float* dy_real, float* dy_fake,
-               float* scal, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  nsgan_d_kernel<<<1, 256, 0, s>>>(y_real, y_fake, B, w_gan, dy_real, dy_fake, scal);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_nsgan_g(const float* y_fake, int B, float w_gan, float* dy, float* scal, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  nsgan_g_kernel<<<1, 256, 0, s>>>(y_fake, B, w_gan, dy, scal);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
 int dg_scale(const float* x, float a, long n, float* y, void* s_) {
   hipStream_t s = (hipStream_t)s_;
   scale_kernel<<<nblk(n), 256, 0, s>>>(x, a, n, y);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_nsgan_d_step(const float* y_real, const float* y_fake, int B, float w_gan, float* dy, float* up, float* rs,
-                    float* acc, float* dfinal_b, void* s_) {
-  if (!y_real || !y_fake || !dy || !acc || B <= 0) return DG_EINVAL;
-  nsgan_d_step_kernel<<<1, 256, 0, (hipStream_t)s_>>>(y_real, y_fake, B, w_gan, dy, up, rs, acc, dfinal_b);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_nsgan_g_step(const float* y_fake, int B, float w_gan, float* dy, float* acc, void* s_) {
-  if (!y_fake || !dy || !acc || B <= 0) return DG_EINVAL;
-  nsgan_g_step_kernel<<<1, 256, 0, (hipStream_t)s_>>>(y_fake, B, w_gan, dy, acc);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }
@@ -1257,21 +626,6 @@ int dg_final_gan_bwd(int metric, int mode_g, float smoothing, const float* y_rea
   else
     final_gan_bwd_kernel<float><<<grid, 512, 0, s>>>(fm, mode_g ? 1 : 0, y_real, y_fake, B, w_gan, r1, dy, up, rs, acc, dfinal_b,
                                                      (const float*)d4, wf, scale, n, C, (float*)dd4, dbias, dwf, dbias_part);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_head_post_bwd2(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
-                      const float* ddepth, const float* thead, int arch, float tau, float drop_const, int B, long HW,
-                      float s_depth, float s_conf, float* draw, float* dbias, void* draw_pm, int cp, void* s_) {
-  if (!gout || !ddepth || !thead || !draw || B <= 0 || HW <= 0 || arch < 0 || arch > 2) return DG_EINVAL;
-  if (arch >= 1 && (!noise_pixel || !mask)) return DG_EINVAL;
-  if (arch == 2 && !noise_image) return DG_EINVAL;
-  const long n = (long)B * HW;
-  const int hb = (int)min((long)1024, (n + 255) / 256);
-  head_post_bwd2_kernel<<<hb, 256, 0, (hipStream_t)s_>>>(gout, noise_pixel, noise_image, mask, ddepth, thead, arch,
-                                                         1.f / tau, drop_const, B, HW, s_depth, s_conf, draw, dbias,
-                                                         (bf16*)draw_pm, cp);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }

@@ -1,7 +1,7 @@
 """DUSty measurability wrappers -- reference: models/dusty.py.
 
 The Gumbel-sigmoid sampling and the mask-out are fused into the generator's head kernels
-(csrc/pointwise.hip head_post_fwd/bwd); these classes keep the reference's module names, buffers and the
+(csrc/head_post.hip head_post_fwd/bwd); these classes keep the reference's module names, buffers and the
 `GumbelSigmoid.fixed_noise` / `logistic_noise` hooks that utils.setup relies on (utils/__init__.py:141-149).
 """
 import torch

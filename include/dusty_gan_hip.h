@@ -336,24 +336,12 @@ int dg_head_post_bwd_aug(const float* gout, const float* noise_pixel, const floa
                          float drop_const, int B, int H, int W, float s_depth, float s_conf, float* draw, float* dbias,
                          void* draw_pm, int cp, float* bias_ws, void* stream);
 
-/* ---- GANLoss(nsgan)  models/loss.py:39-41,68-69 + gradient w.r.t. the logits ----------------------------- */
-/* scal[0]=mean(y_real) scal[1]=mean(y_fake) scal[2]=loss_D */
-int dg_nsgan_d(const float* y_real, const float* y_fake, int B, float w_gan, float* dy_real, float* dy_fake,
-               float* scal, void* stream);
-int dg_nsgan_g(const float* y_fake, int B, float w_gan, float* dy, float* scal, void* stream);
-/* The same losses with the step's bookkeeping folded in (trainers/dcgan_amp.py:203-238,305-309): dy [2B] = dLoss/dy
- * (real | fake); up [2B] = [1..1 | dy_fake] and rs [2B] = [dy_real | 1..1] (the R1 schedule's per-sample vectors, either
- * may be NULL); acc[0..2] += (mean y_real, mean y_fake, loss_D); *dfinal_b += sum dy (the final conv's bias gradient).
- * dg_nsgan_g_step: acc[0] += loss_G.  dg_mean_acc: acc[0] += mean(x[0..n)). */
-int dg_nsgan_d_step(const float* y_real, const float* y_fake, int B, float w_gan, float* dy, float* up, float* rs,
-                    float* acc, float* dfinal_b, void* stream);
-int dg_nsgan_g_step(const float* y_fake, int B, float w_gan, float* dy, float* acc, void* stream);
-
 /* ---- GANLoss, all metrics  models/loss.py:39-61 (loss_D), :66-85 (loss_G) ------------------------------------
- * metric: DG_GAN_* below (the reference's `solver.gan_mode` strings in models/loss.py order).  Same outputs as the
- * nsgan entries above: D step writes dy = [d/dy_real | d/dy_fake] of w_gan * loss_D, the R1 schedule's `up` / `rs`
- * vectors (nullable), acc[0..2] += (mean y_real, mean y_fake, loss_D), dfinal_b += sum(dy) (nullable).  G step writes
- * dy = d(w_gan * loss_G)/dy_fake and acc[0] += loss_G; y_real = D(real) logits, required by the relativistic
+ * metric: DG_GAN_* below (the reference's `solver.gan_mode` strings in models/loss.py order).  The loss with the step's
+ * bookkeeping folded in (trainers/dcgan_amp.py:203-238,305-309).  D step: dy [2B] = [d/dy_real | d/dy_fake] of
+ * w_gan * loss_D; up [2B] = [1..1 | dy_fake] and rs [2B] = [dy_real | 1..1] (the R1 schedule's per-sample vectors, either
+ * may be NULL); acc[0..2] += (mean y_real, mean y_fake, loss_D); *dfinal_b += sum dy (the final conv's bias gradient,
+ * nullable).  G step writes dy = d(w_gan * loss_G)/dy_fake and acc[0] += loss_G; y_real = D(real) logits, required by the relativistic
  * metrics (ragan / rahinge / ralsgan, average_diff models/loss.py:11-18) and ignored (may be NULL) otherwise.
  * `smoothing` = GANLoss.smoothing (lsgan's real label, models/loss.py:46).  DG_EUNSUPPORTED for an unknown metric. */
 enum { DG_GAN_NSGAN = 0, DG_GAN_WGAN = 1, DG_GAN_LSGAN = 2, DG_GAN_HINGE = 3, DG_GAN_RAGAN = 4, DG_GAN_RAHINGE = 5,

@@ -47,7 +47,8 @@ def test_blur_adjoint_r1_form(L, H, W, dtype):
     assert rel_l2(ssq.cpu(), ref.pow(2).sum(dim=[1, 2, 3]).cpu()) < 1e-6
 
 
-@pytest.mark.parametrize("H,W", [(8, 32), (64, 1024), (5, 7)])   # 5 x 7: H W % 256 != 0 -> refused
+# 5 x 7: H W % 256 != 0 -> refused; 8 x 128: the smallest image on the four-pixel forward (HW = 1024, one block per sample)
+@pytest.mark.parametrize("H,W", [(8, 32), (64, 1024), (5, 7), (8, 128)])
 def test_fetch_reals_and_head_emit_per_sample_sums(L, H, W):
     lib = L.lib()
     g = torch.Generator().manual_seed(7 * H + W)
@@ -64,18 +65,19 @@ def test_fetch_reals_and_head_emit_per_sample_sums(L, H, W):
         L.check(rc)
         assert torch.equal(out, ref)
         assert rel_l2(sums.cpu(), ref.sum(dim=[1, 2, 3]).cpu()) < 1e-6
-    for k in (0, 1, 2):  # none / dusty1 / dusty2 heads
+    # none / dusty1 / dusty2 heads; training = 0: dusty2's image mask is the sign of its logit (models/dusty.py:118-119)
+    for k, training in ((k, tr) for k in (0, 1, 2) for tr in (1, 0)):
         raw = torch.randn(B, 1 + k, H, W, generator=g).to(DEV)
         npx = torch.randn(B, H, W, generator=g).to(DEV)
         nim = torch.randn(B, generator=g).to(DEV)
         g1, g2 = raw.clone(), raw.clone()
         m1, m2 = torch.zeros(B, max(k, 1), H, W, device=DEV), torch.zeros(B, max(k, 1), H, W, device=DEV)
         d1, d2 = torch.empty(B, 1, H, W, device=DEV), torch.empty(B, 1, H, W, device=DEV)
-        L.check(lib.dg_head_post_fwd(g1.data_ptr(), npx.data_ptr(), nim.data_ptr(), k, 1, 1.0, -1.0, B, HW, m1.data_ptr(),
-                                     d1.data_ptr(), None))
+        L.check(lib.dg_head_post_fwd(g1.data_ptr(), npx.data_ptr(), nim.data_ptr(), k, training, 1.0, -1.0, B, HW,
+                                     m1.data_ptr(), d1.data_ptr(), None))
         ds = torch.zeros(B, device=DEV)
-        rc = lib.dg_head_post_fwd_sum(g2.data_ptr(), npx.data_ptr(), nim.data_ptr(), k, 1, 1.0, -1.0, B, HW, m2.data_ptr(),
-                                      d2.data_ptr(), ds.data_ptr(), None)
+        rc = lib.dg_head_post_fwd_sum(g2.data_ptr(), npx.data_ptr(), nim.data_ptr(), k, training, 1.0, -1.0, B, HW,
+                                      m2.data_ptr(), d2.data_ptr(), ds.data_ptr(), None)
         if HW % 256 != 0:
             assert rc == L.DG_EUNSUPPORTED
             continue
