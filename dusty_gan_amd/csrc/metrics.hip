@@ -20,7 +20,10 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 // t + w into slot t for w = T/2 .. 1 keeping the lower SLOT on ties, so two threads meet at the lowest bit in which
 // their ids differ and the one with that bit clear wins.  Among equal maxima the winner therefore minimises
 // (bit-reversed (k mod T), k); `tie_mod` carries T.
-// Points with |p|^2 <= 1e-3 (dropped returns at the origin) never become candidates (:132-134).
+// Points with |p|^2 <= 1e-3 (dropped returns at the origin) never become candidates (:132-134).  The reference compares
+// the float `mag` with the DOUBLE literal 1e-3; float(1e-3) = 0.0010000000475 lies above it and its lower neighbour
+// below, so in float terms the skip is `mag < 1e-3f`: a point of squared norm exactly 1e-3f IS a candidate
+// (tests/golden/fps_emd.npz thresh_*, recorded from the reference's kernel).
 struct Cand {
   float v;
   int k;
@@ -55,7 +58,7 @@ __global__ __launch_bounds__(1024) void fps_kernel(const float* __restrict__ xyz
     for (int k = tid; k < n; k += blockDim.x) {
       const float x2 = xyz[k * 3 + 0], y2 = xyz[k * 3 + 1], z2 = xyz[k * 3 + 2];
       const float mag = (x2 * x2) + (y2 * y2) + (z2 * z2);
-      if (mag <= 1e-3f) continue;
+      if (mag < 1e-3f) continue;  // == the reference's `mag <= 1e-3` (double literal): see above
       const float d = (x2 - x1) * (x2 - x1) + (y2 - y1) * (y2 - y1) + (z2 - z1) * (z2 - z1);
       const float d2 = fminf(d, temp[k]);
       temp[k] = d2;

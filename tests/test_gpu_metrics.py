@@ -28,7 +28,8 @@ def lidar_like_clouds(B, n, seed, drop=0.15):
 @pytest.mark.parametrize("n,m", [(70, 20), (512, 64), (1000, 128), (4096, 512), (8192, 100),
                                  (65536, 512)])  # last: a full 64x1024 scan to the validation size
 def test_fps_matches_oracle_indices(n, m):
-    """index-exact furthest point sampling incl. the reference launcher's tie order and the origin-skip rule"""
+    """index-exact furthest point sampling incl. the reference launcher's tie order and the origin-skip rule, at the
+    validation sizes, against the restatement that tests/golden/fps_emd.npz pins to the reference's own kernel"""
     from dusty_gan_amd.utils.sampling import downsample_point_clouds, furthest_point_sampling
     B = 3 if n < 60000 else 1
     pts = lidar_like_clouds(B, n, seed=n + m)
@@ -90,8 +91,9 @@ def test_cov_mmd_1nna_matches_oracle():
 def test_cov_mmd_1nna_matches_the_reference_functions():
     """`utils.metrics.compute_cov_mmd_1nna`, `_compute_cov_mmd`, `_compute_nna` (device tensors, the all-pairs Chamfer
     kernel) against tests/golden/covmmd.npz: the outputs of the reference's own functions (cov_mmd_1nna.py:55-148) with its
-    own CPU Chamfer search underneath.  Parity-unpinned and staying so: furthest point sampling and the EMD, which the
-    reference holds only as CUDA sources (their tests compare against restatements of those sources)."""
+    own CPU Chamfer search underneath.  Furthest point sampling and the EMD, which the reference holds only as CUDA
+    sources, are pinned by tests/golden/fps_emd.npz: the outputs of those kernels built for gfx950 (the two tests named
+    `..._the_reference_kernel(s)`)."""
     from tests.golden_util import load, sub
     from dusty_gan_amd.utils.metrics import compute_cov_mmd_1nna
     from dusty_gan_amd.utils.metrics.cov_mmd_1nna import _compute_cov_mmd, _compute_nna
@@ -123,7 +125,8 @@ def test_cov_mmd_1nna_matches_the_reference_functions():
 @pytest.mark.parametrize("n,m", [(64, 64), (200, 200), (96, 32), (50, 150)])
 def test_emd_matches_oracle(n, m):
     """approxmatch + matchcost (earth_mover_distance.cu) fused: paired costs and the all-pairs matrix against the numpy
-    restatement; __expf against np.exp and fp32 sums in a different order -> 1e-3 relative"""
+    restatement (itself held to the reference's kernels by tests/golden/fps_emd.npz, whose order of operations it follows;
+    the kernel sums the cost per level instead of over a stored match matrix) -> 1e-3 relative"""
     from dusty_gan_amd.utils.metrics import earth_mover_distance
     from dusty_gan_amd.utils.metrics.distance import emd_distance_matrix
     a = lidar_like_clouds(4, n, seed=n, drop=0.05)
@@ -136,6 +139,72 @@ def test_emd_matches_oracle(n, m):
         assert M.shape == (3, 4) and rel_l2(M, MO.pairwise_emd(a[:3], b)) < 1e-3
         self_cost = earth_mover_distance(torch.from_numpy(a).to(DEV), torch.from_numpy(a).to(DEV)).cpu()
         assert float(self_cost.max()) < 1e-2 * float(want.min())  # a cloud matches itself at (almost) no cost
+
+
+@pytest.mark.parametrize("family", ["lattice", "thresh", "scan"])
+def test_fps_matches_the_reference_kernel(family):
+    """`furthest_point_sampling` / `downsample_point_clouds` against what the reference's OWN kernel and launcher returned on
+    an MI355X (tests/golden/fps_emd.npz): index-exact on every rung of the launcher's block-size ladder (n = 1 .. 2048,
+    B = 3, m = min(n, 48)); lattice: exact arithmetic and ties everywhere (the tie order); thresh: points exactly at, just
+    below and just above the origin-skip threshold; scan: dropped returns and a duplicate, selections that do not depend
+    on multiply-add fusion.  Where oracle/_ref/libref_fps_emd.so has been built the reference's kernel is also run live,
+    in this process, and must return the fixture bit for bit."""
+    from dusty_gan_amd.utils.sampling import downsample_point_clouds, furthest_point_sampling
+    from tests.ref_fps_emd_util import RefFpsEmd
+    from tests.test_oracle_golden import FPS_RUNGS
+    g = load("fps_emd")
+    ref = RefFpsEmd.open()
+    for n in FPS_RUNGS:
+        name = f"{family}_n{n}"
+        xyz, want = g[f"fps/{name}/xyz"], g[f"fps/{name}/idx"]
+        m = want.shape[1]
+        if ref is not None:
+            assert np.array_equal(ref.fps(xyz, m), want), name
+        x = torch.from_numpy(xyz).to(DEV)
+        idx = furthest_point_sampling(x, m).cpu().numpy()
+        sub = downsample_point_clouds(x, m).cpu().numpy()
+        for b in range(3):
+            assert idx[b].tolist() == want[b].tolist(), (name, b)
+            assert np.array_equal(sub[b], xyz[b][want[b]]), (name, b)
+
+
+def test_emd_matches_the_reference_kernels():
+    """`earth_mover_distance` / `emd_distance_matrix` against the reference's OWN approxmatch + matchcost kernels as run on an
+    MI355X (tests/golden/fps_emd.npz): integer and truncated n/m factors both ways, the 512-thread and 1024-point chunk
+    edges, b = 35 (the 32-block grid stride), far-apart clouds (the 1e-9 guards decide), a cloud with itself.  Per pair
+    the cost must lie within 2 * e_ref + 1e-6 * |cost| of the same algorithm in float64, e_ref being the reference's own
+    distance from it.  Where oracle/_ref/libref_fps_emd.so has been built the reference's kernels are also run live and
+    must return the recorded costs."""
+    from dusty_gan_amd.utils.metrics import earth_mover_distance
+    from dusty_gan_amd.utils.metrics.distance import emd_distance_matrix
+    from tests.ref_fps_emd_util import RefFpsEmd
+    from tests.test_oracle_golden import EMD_CASES
+    g = load("fps_emd")
+    ref = RefFpsEmd.open()
+    bad = []
+    for name in EMD_CASES:
+        a, b = g[f"emd/{name}/a"], g[f"emd/{name}/b"]
+        f64, e_ref = g[f"emd/{name}/f64"], g[f"emd/{name}/e_ref"]
+        if ref is not None:
+            assert np.array_equal(ref.emd(a, b), g[f"emd/{name}/ref"]), name
+        got = earth_mover_distance(torch.from_numpy(a).to(DEV), torch.from_numpy(b).to(DEV)).cpu().numpy().astype(np.float64)
+        for i in range(a.shape[0]):
+            print(name, i, "f64", f64[i], "e_ref", e_ref[i], "|ours - f64|", abs(got[i] - f64[i]))
+            if not abs(got[i] - f64[i]) <= 2.0 * e_ref[i] + 1e-6 * abs(f64[i]):
+                bad.append((name, i, got[i], f64[i], e_ref[i]))
+    A, B = g["emd/mat64/a"], g["emd/mat64/b"]
+    f64, e_ref = g["emd/mat64/f64"], g["emd/mat64/e_ref"]
+    if ref is not None:
+        live = ref.emd(np.repeat(A, 4, axis=0), np.tile(B, (3, 1, 1))).reshape(3, 4)
+        assert np.array_equal(live, g["emd/mat64/ref"])
+    M = emd_distance_matrix(torch.from_numpy(A).to(DEV), torch.from_numpy(B).to(DEV)).cpu().numpy().astype(np.float64)
+    assert M.shape == (3, 4)
+    for i in range(3):
+        for j in range(4):   # the matrix holds compute_emd = cost / N
+            print("mat64", i, j, "f64", f64[i, j], "e_ref", e_ref[i, j], "|ours - f64|", abs(M[i, j] * 64.0 - f64[i, j]))
+            if not abs(M[i, j] * 64.0 - f64[i, j]) <= 2.0 * e_ref[i, j] + 1e-6 * abs(f64[i, j]):
+                bad.append(("mat64", i, j, M[i, j] * 64.0, f64[i, j], e_ref[i, j]))
+    assert not bad, bad
 
 
 def test_cov_mmd_1nna_emd_matches_oracle():

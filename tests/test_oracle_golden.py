@@ -245,8 +245,8 @@ def test_jsd_oracle_matches_reference():
 
 
 def test_fps_and_chamfer_restatements():
-    """parity-unpinned restatements (the reference's CUDA extensions cannot run here): literal loops of the cited
-    sources on tiny inputs against the vectorised oracle"""
+    """restatements of the reference's CUDA extensions (pinned to its own code by tests/golden/chamfer.npz and
+    fps_emd.npz): literal loops of the cited sources on tiny inputs against the vectorised oracle"""
     from oracle import metrics_oracle as MO
     rng = np.random.default_rng(3)
     xyz = rng.normal(0, 0.3, (70, 3)).astype(np.float32)
@@ -381,6 +381,71 @@ def test_chamfer_oracle_pinned_by_the_reference_nnsearch():
                 assert abs(M[i, i] - (dl.mean() + dr.mean())) <= 1e-6 * max(1.0, abs(M[i, i]))
 
 
+FPS_RUNGS = [1, 2, 3, 5, 8, 17, 33, 70, 130, 300, 513, 1000, 1025, 2048]
+FPS_FAMILIES = ["lattice", "thresh", "scan"]
+EMD_CASES = ["p1_1", "p2_3", "p4_4", "p64_64", "p96_32", "p50_150", "p100_30", "p520_1030", "p1030_520", "b35_8_8",
+             "far_96_32", "self_64"]
+
+
+def test_fps_oracle_pinned_by_the_reference_kernel():
+    """oracle/metrics_oracle.py `fps` against the reference's OWN furthest_point_sampling kernel and launcher, hipified and
+    run on an MI355X (tests/golden/fps_emd.npz, made by tests/golden/make_fps_emd_golden.py): index-exact on every rung of
+    the launcher's 1..512 block-size ladder, on lattice clouds (exact arithmetic, ties everywhere: the tie order), on
+    clouds with points exactly at, just below and just above the origin-skip threshold, and on scan-like clouds whose
+    selection does not depend on multiply-add fusion.  No case is left out."""
+    from oracle import metrics_oracle as MO
+    g = load("fps_emd")
+    assert list(g["meta/fps_cases"]) == [f"{fam}_n{n}" for n in FPS_RUNGS for fam in FPS_FAMILIES]
+    for name in g["meta/fps_cases"]:
+        xyz, idx = g[f"fps/{name}/xyz"], g[f"fps/{name}/idx"]
+        assert xyz.shape[0] == 3 and idx.shape == (3, min(xyz.shape[1], 48))
+        for b in range(3):
+            assert MO.fps(xyz[b], idx.shape[1]).tolist() == idx[b].tolist(), (name, b)
+    # the threshold clouds do hold what they are for: squared norms exactly float32(1e-3), its neighbours and 0, and the
+    # reference picks points AT float32(1e-3) (it lies above the double 1e-3) but none below
+    t0 = np.float32(1e-3)
+    lo, hi = np.nextafter(t0, np.float32(0)), np.nextafter(t0, np.float32(1))
+    picked = {float(v): 0 for v in (lo, t0, hi, np.float32(0))}
+    for n in FPS_RUNGS[4:]:
+        xyz, idx = g[f"fps/thresh_n{n}/xyz"], g[f"fps/thresh_n{n}/idx"]
+        for b in range(3):
+            mag = (xyz[b, :, 0] * xyz[b, :, 0] + xyz[b, :, 1] * xyz[b, :, 1]) + xyz[b, :, 2] * xyz[b, :, 2]
+            assert all((mag == v).any() for v in (lo, t0, hi, np.float32(0))), (n, b)
+            for k in idx[b][1:]:
+                if float(mag[k]) in picked:
+                    picked[float(mag[k])] += 1
+    assert picked[float(t0)] > 0 and picked[float(hi)] > 0 and picked[float(lo)] == 0 and picked[0.0] == 0, picked
+
+
+def test_emd_oracle_pinned_by_the_reference_kernels():
+    """oracle/metrics_oracle.py `emd_cost` against the reference's OWN approxmatch + matchcost kernels, hipified and run on an
+    MI355X at their <<<32, 512>>> launch (tests/golden/fps_emd.npz).  Per pair the fixture holds the reference's cost, the
+    same algorithm in float64 and e_ref = |reference - float64|; the float32 restatement must lie within
+    2 * e_ref + 1e-6 * |cost| of the float64 value (the 2x: its own float32 rounding, in another order, beside the
+    reference's), and in float64 it must reproduce the recorded float64 value to 1e-12 relative.
+    The float32 restatement follows the kernels' order of operations and fused multiply-adds (oracle/metrics_oracle.py
+    `emd_costs`): the approximation is ill-conditioned on isolated points, and a float32 evaluation in any other order
+    lies further from the kernels than they lie from float64 (unfused, BLAS-ordered sums and np.exp: p64_64[1] at
+    3.0e-6 against its bound of 2.2e-6, e_ref 3.65e-7 on a cost of 1.4651).  As it stands it is within 3 ulp of the
+    recorded reference cost on every pair, and the largest |oracle32 - f64| / bound is 0.48."""
+    from oracle import metrics_oracle as MO
+    g = load("fps_emd")
+    assert list(g["meta/emd_cases"]) == EMD_CASES
+    pairs = [(name, g[f"emd/{name}/a"][i], g[f"emd/{name}/b"][i], g[f"emd/{name}/f64"][i], g[f"emd/{name}/e_ref"][i])
+             for name in EMD_CASES for i in range(g[f"emd/{name}/a"].shape[0])]
+    A, B = g["emd/mat64/a"], g["emd/mat64/b"]
+    pairs += [("mat64", A[i], B[j], g["emd/mat64/f64"][i, j], g["emd/mat64/e_ref"][i, j]) for i in range(3) for j in range(4)]
+    bad = []
+    for name, a, b, f64, e_ref in pairs:
+        got64 = MO.emd_cost(a, b, dtype=np.float64)
+        assert abs(got64 - f64) <= 1e-12 * abs(f64), (name, got64, f64)
+        got32 = MO.emd_cost(a, b)
+        print(name, "f64", f64, "e_ref", e_ref, "|oracle32 - f64|", abs(got32 - f64))
+        if not abs(got32 - f64) <= 2.0 * e_ref + 1e-6 * abs(f64):
+            bad.append((name, got32, f64, e_ref))
+    assert not bad, bad
+
+
 def test_oracle_matches_reference_at_full_width():
     """The benchmark's width - 64x1024, 512 latent, channels 64..512 (BASELINE configs 2-4), dusty2, B = 2, one step -
     as the REFERENCE's modules computed it (tests/golden/make_golden.py full): parameters and inputs are regenerated
@@ -473,7 +538,7 @@ def test_cov_mmd_1nna_oracle_pinned_by_the_reference_functions():
     Chamfer distance = its own CPU `nnsearch`) returned: tests/golden/covmmd.npz, made by make_golden.py covmmd.  Crafted
     matrices with ties, k = 1 and 3, sqrt on and off; then clouds end to end incl. the three pairwise matrices.
     (FPS and EMD exist in the reference only as CUDA sources - furthest_point_sampling.cu, earth_mover_distance.cu - and
-    stay parity-unpinned: their oracles are restatements of those sources with no reference-made vector.)"""
+    are pinned by tests/golden/fps_emd.npz, recorded from those kernels built for gfx950.)"""
     from oracle import metrics_oracle as MO
     g = load("covmmd")
     for tag in ("rand", "ties", "wide"):
