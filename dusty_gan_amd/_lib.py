@@ -192,6 +192,7 @@ PROTOTYPES = {
     "dg_fps": [_P, _I, _I, _I, _P, _P, _P, _P],
     "dg_chamfer_dir": [_P, _I, _I, _P, _I, _I, _P, _P],
     "dg_chamfer_paired": [_P, _I, _P, _I, _I, _P, _P],
+    "dg_chamfer_nn": [_P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _P, _P, _P],
     "dg_emd": [_P, _I, _I, _P, _I, _I, _I, _P, _P],
     "dg_grid_vote": [_P, _L, _P, _I, _P, _P],
     "dg_jsd": [_P, _P, _I, _P, _P],
@@ -226,6 +227,10 @@ PROTOTYPES = {
     "dg_adam_fused": [_P, _P, _P, _P, _P, _I, C.POINTER(DgOptSeg), _I, _F, _F, _F, _F, _P, _F, _P],
     "dg_adam_proj_fused": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _L, _I, _F, _F, _F, _F, _F, _P, _F, _P],
     "dg_inv_loss_grad": [_P, _L, _I, _P, _P, _P, _I, _I, _L, _F, _P, _I, _P, _I, _P, _P, _I, _P, _P],
+    "dg_inv_loss_grad_add": [_P, _L, _I, _P, _P, _P, _I, _I, _L, _F, _P, _I, _P, _I, _P, _P, _I, _P, _P],
+    "dg_inv_chamfer_scatter": [_P, _P, _I, _L, _P, _P],
+    "dg_inv_chamfer_grad": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _L, _F, _F, _I, _P, _I, _P,
+                            _I, _P, _P, _I, _P, _P],
     "dg_sphere_adam": [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _I, _U64, _U64, _I, _P],
     "dg_depth_metrics": [_P, _P, _P, _P, _I, _I, _F, _I, _L, _F, _F, _P, _P],
 }

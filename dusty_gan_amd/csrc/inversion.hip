@@ -9,9 +9,13 @@
 //                            perturbed latent written straight into the generator's compute-dtype latent buffer.
 //   * depth_metrics_kernel : compute_depth_error / compute_depth_accuracy (utils/metrics/depth.py) on revert_depth of both
 //                            inverse-depth maps, and the drop ratios of the evaluation CSV.
+//   * inv_chamfer_scatter_kernel / inv_chamfer_grad_kernel : the Chamfer term of the reference's inversion loop (demo.py:508-519
+//                            with chamfer_distance.cpp:82-140): the target-to-generated matches of dg_chamfer_nn scattered
+//                            onto the generated pixels in 24.40 fixed point, then per sample the loss and, chained through
+//                            inv_to_xyz and the EVAL-mode head post-processing, the head gradient.
 // Every per-sample sum is a fixed-order reduction (block sums, then the partials of a sample in chunk order): an inversion
 // is bit-reproducible run to run.
-#include "common.h"
+#include "head_post.h"
 
 namespace {
 
@@ -20,6 +24,8 @@ constexpr int IL_THREADS = 256;
 // gen = tanh_to_sigmoid(t) (from_tanh) or x; l1: |ref - gen|, l2: (ref - gen)^2, both times the mask.
 // d loss_b / d gen = sign(gen - ref) (sign(0) = 0, torch's l1_loss gradient) or 2 (gen - ref), times mask / msum_b;
 // through tanh_to_sigmoid (1/2) and tanh (1 - t^2), times the head's EqualLR scale.
+// ADD: a further term of the loss (its own instantiation: the single-term kernel is the code it was)
+template <bool ADD>
 __global__ __launch_bounds__(IL_THREADS) void inv_loss_grad_kernel(const float* __restrict__ gen, int gen_sb, int from_tanh,
                                                                    const float* __restrict__ ref, const float* __restrict__ mask,
                                                                    const float* __restrict__ msum, int l2, long HW,
@@ -46,6 +52,17 @@ __global__ __launch_bounds__(IL_THREADS) void inv_loss_grad_kernel(const float* 
       const float e = x - r[p];
       const float dl = (l2 ? 2.f * e : (float)((e > 0.f) - (e < 0.f))) * (m * inv_m);
       const float d0 = dl * 0.5f * (1.f - t * t) * s_depth;
+      if constexpr (ADD) {   // a further term of the loss: the planar fp32 gradient is the running sum, the bf16 copy its rounding
+        float* q = draw + (long)b * nheads * HW + p;
+        const float v0 = q[0] + d0;
+        q[0] = v0;
+        if (draw_pm) {
+          bf16* o = draw_pm + ((long)b * HW + p) * cp;
+          o[0] = (bf16)v0;
+          for (int c = 1; c < cp; ++c) o[c] = (bf16)(c < nheads ? q[c * HW] : 0.f);
+        }
+        continue;
+      }
       if (draw) {
         float* q = draw + (long)b * nheads * HW + p;
         q[0] = d0;
@@ -61,7 +78,7 @@ __global__ __launch_bounds__(IL_THREADS) void inv_loss_grad_kernel(const float* 
   const float s = dg_block_sum(acc, red);
   if (threadIdx.x != 0) return;
   if (nch == 1) {
-    loss[b] = s / msum[b];
+    loss[b] = ADD ? loss[b] + s / msum[b] : s / msum[b];
     return;
   }
   // the partial goes to memory-side (atomic exchange); the last block of the sample adds the partials in chunk order
@@ -69,7 +86,121 @@ __global__ __launch_bounds__(IL_THREADS) void inv_loss_grad_kernel(const float* 
   if (!dg_ticket_last(&tickets[b], nch)) return;
   float tot = 0.f;
   for (int c = 0; c < nch; ++c) tot += atomicExch(&parts[(long)b * nch + c], 0.f);
-  loss[b] = tot / msum[b];
+  loss[b] = ADD ? loss[b] + tot / msum[b] : tot / msum[b];
+}
+
+// ---- the Chamfer term.  R [B,3,HW]: the target's points, P [B,3,HW]: postprocess(out)["points"], both planar.
+// Scatter of the target-to-generated matches: acc [B,HW,4] u64 words (dg_fix40: |R| <= 1 and at most 2^18 matches per pixel keep a
+// total below 2^59), word 3 the match count.  Integer atomics: the sums do not depend on the arrival order.  ZERO AT REST:
+// inv_chamfer_grad_kernel zeroes what it reads.
+__global__ __launch_bounds__(256) void inv_chamfer_scatter_kernel(const float* __restrict__ R, const int* __restrict__ idx1,
+                                                                  int B, long HW, unsigned long long* __restrict__ acc) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * HW) return;
+  const long b = i / HW, j = i - b * HW;
+  const int k = idx1[i];
+  if (k < 0 || k >= HW) return;
+  unsigned long long* cell = acc + (b * HW + k) * 4;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    long long q;
+    if (dg_fix40((double)R[(b * 3 + c) * HW + j], q) && q != 0) atomicAdd(cell + c, (unsigned long long)q);
+  }
+  atomicAdd(cell + 3, 1ull);
+}
+
+struct ChamferGradArgs {
+  const float *P, *R, *d1, *d2;
+  const int* idx2;
+  unsigned long long* acc;
+  const float *depth, *angle, *gout, *noise_pixel, *mask;
+  int arch, nheads, cp, add;
+  float inv_tau, drop_const, min_d, max_d, tol, s_depth, s_conf;
+  long HW;
+  float* draw;
+  bf16* draw_pm;
+  float* parts;
+  unsigned* tickets;
+  float* loss;
+};
+
+// loss[b] (+)= mean_j d1 + mean_k d2 (N = M = HW points either side) and, per generated pixel k,
+//   gP = (2/M)(P_k - R_idx2[k]) + (2/N)(c_k P_k - S_k)                       chamfer_distance.cpp:105-139
+//   g  = <gP, direction> d(depth/max)/d inv * valid * 1/2                     utils/lidar.py:61-68, utils/__init__.py:168
+// = d loss_b / d (masked depth); then the head gradient of the eval-mode graph (models/dusty.py:45-59,77-91,107-127): the depth
+// channel through mask and tanh, the pixel confidence through the straight-through Gumbel sigmoid, dusty2's image channel 0
+// (eval: a plain threshold).  add: the gradient is added to what `draw` holds (an L1 / L2 term written before).
+__global__ __launch_bounds__(IL_THREADS) void inv_chamfer_grad_kernel(const ChamferGradArgs a) {
+  __shared__ float red[16];
+  const int b = blockIdx.y, nch = gridDim.x;
+  const long HW = a.HW;
+  const long chunk = (HW + nch - 1) / nch;
+  const long p0 = blockIdx.x * chunk, p1 = min(HW, p0 + chunk);
+  const float* Pb = a.P + (long)b * 3 * HW;
+  const float* Rb = a.R + (long)b * 3 * HW;
+  const float span = 1.f / a.min_d - 1.f / a.max_d;
+  const float w = 2.f / (float)HW;
+  float acc = 0.f;
+  for (long p = p0 + threadIdx.x; p < p1; p += IL_THREADS) {
+    const long bp = (long)b * HW + p;
+    acc += a.d1[bp] + a.d2[bp];
+    const float x = Pb[p], y = Pb[HW + p], z = Pb[2 * HW + p];
+    int k2 = a.idx2[bp];
+    k2 = k2 < 0 ? 0 : (k2 >= HW ? (int)(HW - 1) : k2);
+    unsigned long long* cell = a.acc + bp * 4;
+    const float sx = (float)dg_fix40_value((long long)cell[0]), sy = (float)dg_fix40_value((long long)cell[1]),
+                sz = (float)dg_fix40_value((long long)cell[2]), cnt = (float)cell[3];
+    cell[0] = 0ull; cell[1] = 0ull; cell[2] = 0ull; cell[3] = 0ull;
+    const float gx = w * (x - Rb[k2]) + w * (cnt * x - sx);
+    const float gy = w * (y - Rb[HW + k2]) + w * (cnt * y - sy);
+    const float gz = w * (z - Rb[2 * HW + k2]) + w * (cnt * z - sz);
+    const float pitch = a.angle[p], yaw = a.angle[HW + p];
+    const float cpt = cosf(pitch), spt = sinf(pitch), cy = cosf(yaw), sy_ = sinf(yaw);
+    const float dot = gx * (cpt * cy) + gy * (cpt * sy_) + gz * spt;
+    const float tm = a.depth[bp];                       // the masked depth, tanh domain
+    const float raw01 = (tm + 1.f) / 2.f;
+    const float inv = fminf(fmaxf(raw01, 0.f), 1.f);
+    const bool pass = raw01 >= 0.f && raw01 <= 1.f;     // clamp(0, 1) passes the gradient on the closed interval
+    const bool valid = fabsf(inv - 0.f) > a.tol;        // the LiDAR's drop_const is 0 (utils/lidar.py:12)
+    const float dep = 1.f / (inv * span + 1.f / a.max_d);
+    const float g = (valid && pass) ? 0.5f * (-(span * dep * dep) / a.max_d) * dot : 0.f;
+    const float* go = a.gout + (long)b * a.nheads * HW + p;
+    const float t = go[0];
+    float d0, d1, d2;
+    if (a.arch == 0) {
+      head_px_bwd<0>(t, g, 0.f, 0.f, 1.f, 1.f, a.inv_tau, a.drop_const, d0, d1, d2);
+    } else if (a.arch == 1) {
+      head_px_bwd<1>(t, g, go[HW] + a.noise_pixel[bp], 0.f, a.mask[bp], 1.f, a.inv_tau, a.drop_const, d0, d1, d2);
+    } else {
+      const float* mk = a.mask + (long)b * 2 * HW + p;
+      head_px_bwd<2>(t, g, go[HW] + a.noise_pixel[bp], 0.f, mk[0], mk[HW], a.inv_tau, a.drop_const, d0, d1, d2);
+      d2 = 0.f;
+    }
+    float v[3] = {d0 * a.s_depth, d1 * a.s_conf, d2 * a.s_conf};
+    if (a.add) {
+      const float* q = a.draw + (long)b * a.nheads * HW + p;
+      for (int c = 0; c < a.nheads && c < 3; ++c) v[c] += q[c * HW];
+    }
+    if (a.draw) {
+      float* q = a.draw + (long)b * a.nheads * HW + p;
+      for (int c = 0; c < a.nheads; ++c) q[c * HW] = c < 3 ? v[c] : 0.f;
+    }
+    if (a.draw_pm) {
+      bf16* q = a.draw_pm + bp * a.cp;
+      for (int c = 0; c < a.cp; ++c) q[c] = (bf16)((c < 3 && c < a.nheads) ? v[c] : 0.f);
+    }
+  }
+  const float s = dg_block_sum(acc, red);
+  if (threadIdx.x != 0) return;
+  float tot = s;
+  if (nch > 1) {
+    atomicExch(&a.parts[(long)b * nch + blockIdx.x], s);
+    if (!dg_ticket_last(&a.tickets[b], nch)) return;
+    tot = 0.f;
+    for (int c = 0; c < nch; ++c) tot += atomicExch(&a.parts[(long)b * nch + c], 0.f);
+  }
+  const float val = tot / (float)HW;
+  a.loss[b] = a.add ? a.loss[b] + val : val;
 }
 
 constexpr int SA_THREADS = 256;
@@ -239,9 +370,10 @@ __global__ __launch_bounds__(DM_THREADS) void depth_metrics_kernel(const float* 
 
 extern "C" {
 
-int dg_inv_loss_grad(const float* gen, long gen_sb, int from_tanh, const float* ref, const float* mask, const float* msum,
-                     int distance, int B, long HW, float s_depth, float* draw, int nheads, void* draw_pm, int cp,
-                     float* parts, unsigned* tickets, int nchunk, float* loss, void* s_) {
+static int inv_loss_grad_launch(const float* gen, long gen_sb, int from_tanh, const float* ref, const float* mask,
+                                const float* msum, int distance, int B, long HW, float s_depth, float* draw, int nheads,
+                                void* draw_pm, int cp, float* parts, unsigned* tickets, int nchunk, float* loss, int add,
+                                void* s_) {
   if (!gen || !ref || !mask || !msum || !loss || B <= 0 || HW <= 0 || (distance != 0 && distance != 1)) return DG_EINVAL;
   if (draw && nheads < 1) return DG_EINVAL;
   if (draw_pm && cp < 1) return DG_EINVAL;
@@ -249,9 +381,64 @@ int dg_inv_loss_grad(const float* gen, long gen_sb, int from_tanh, const float* 
   if (nchunk > 1 && (!parts || !tickets)) return DG_EINVAL;
   if (gen_sb > 0x7fffffffL) return DG_EUNSUPPORTED;
   const dim3 grid(nchunk, B);
-  inv_loss_grad_kernel<<<grid, IL_THREADS, 0, (hipStream_t)s_>>>(gen, (int)gen_sb, from_tanh, ref, mask, msum, distance,
-                                                                 HW, s_depth, draw, nheads, (bf16*)draw_pm, cp, parts,
-                                                                 tickets, loss);
+  if (add)
+    inv_loss_grad_kernel<true><<<grid, IL_THREADS, 0, (hipStream_t)s_>>>(gen, (int)gen_sb, from_tanh, ref, mask, msum, distance,
+                                                                         HW, s_depth, draw, nheads, (bf16*)draw_pm, cp, parts,
+                                                                         tickets, loss);
+  else
+    inv_loss_grad_kernel<false><<<grid, IL_THREADS, 0, (hipStream_t)s_>>>(gen, (int)gen_sb, from_tanh, ref, mask, msum, distance,
+                                                                          HW, s_depth, draw, nheads, (bf16*)draw_pm, cp, parts,
+                                                                          tickets, loss);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
+
+int dg_inv_loss_grad(const float* gen, long gen_sb, int from_tanh, const float* ref, const float* mask, const float* msum,
+                     int distance, int B, long HW, float s_depth, float* draw, int nheads, void* draw_pm, int cp,
+                     float* parts, unsigned* tickets, int nchunk, float* loss, void* s_) {
+  return inv_loss_grad_launch(gen, gen_sb, from_tanh, ref, mask, msum, distance, B, HW, s_depth, draw, nheads, draw_pm, cp,
+                              parts, tickets, nchunk, loss, 0, s_);
+}
+
+int dg_inv_loss_grad_add(const float* gen, long gen_sb, int from_tanh, const float* ref, const float* mask, const float* msum,
+                         int distance, int B, long HW, float s_depth, float* draw, int nheads, void* draw_pm, int cp,
+                         float* parts, unsigned* tickets, int nchunk, float* loss, void* s_) {
+  if (!draw) return DG_EINVAL;   // the running sum lives in the planar gradient
+  return inv_loss_grad_launch(gen, gen_sb, from_tanh, ref, mask, msum, distance, B, HW, s_depth, draw, nheads, draw_pm, cp,
+                              parts, tickets, nchunk, loss, 1, s_);
+}
+
+int dg_inv_chamfer_scatter(const float* R, const int* idx1, int B, long HW, unsigned long long* acc, void* s_) {
+  if (!R || !idx1 || !acc || B <= 0 || HW <= 0) return DG_EINVAL;
+  if (HW > (1l << 18)) return DG_EUNSUPPORTED;
+  const long n = (long)B * HW;
+  inv_chamfer_scatter_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)s_>>>(R, idx1, B, HW, acc);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
+
+int dg_inv_chamfer_grad(const float* P, const float* R, const float* d1, const float* d2, const int* idx2,
+                        unsigned long long* acc, const float* depth, const float* angle, const float* gout,
+                        const float* noise_pixel, const float* mask, int arch, float tau, float drop_const, float min_depth,
+                        float max_depth, float tol, int B, long HW, float s_depth, float s_conf, int add, float* draw,
+                        int nheads, void* draw_pm, int cp, float* parts, unsigned* tickets, int nchunk, float* loss,
+                        void* s_) {
+  if (!P || !R || !d1 || !d2 || !idx2 || !acc || !depth || !angle || !gout || !loss || B <= 0 || HW <= 0) return DG_EINVAL;
+  if (arch < 0 || arch > 2 || nheads != arch + 1 || (arch && (!noise_pixel || !mask)) || !(tau > 0.f)) return DG_EINVAL;
+  if (!(min_depth > 0.f && min_depth < max_depth)) return DG_EINVAL;
+  if (!draw && !draw_pm) return DG_EINVAL;
+  if (add && !draw) return DG_EINVAL;
+  if (draw_pm && cp < nheads) return DG_EINVAL;
+  if (nchunk < 1 || nchunk > 65535 || B > 65535) return DG_EINVAL;
+  if (nchunk > 1 && (!parts || !tickets)) return DG_EINVAL;
+  if (HW > (1l << 18)) return DG_EUNSUPPORTED;
+  ChamferGradArgs a;
+  a.P = P; a.R = R; a.d1 = d1; a.d2 = d2; a.idx2 = idx2; a.acc = acc; a.depth = depth; a.angle = angle; a.gout = gout;
+  a.noise_pixel = noise_pixel; a.mask = mask; a.arch = arch; a.nheads = nheads; a.cp = cp; a.add = add;
+  a.inv_tau = 1.f / tau; a.drop_const = drop_const; a.min_d = min_depth; a.max_d = max_depth; a.tol = tol;
+  a.s_depth = s_depth; a.s_conf = s_conf; a.HW = HW; a.draw = draw; a.draw_pm = (bf16*)draw_pm; a.parts = parts;
+  a.tickets = tickets; a.loss = loss;
+  inv_chamfer_grad_kernel<<<dim3(nchunk, B), IL_THREADS, 0, (hipStream_t)s_>>>(a);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }

@@ -189,6 +189,115 @@ __global__ __launch_bounds__(CH_THREADS) void chamfer_dir_kernel(const float* __
 }
 
 // --------------------------------------------------------------------------------------------------------------
+// Paired nearest-neighbour search WITH indices (chamfer_distance.cu:9-127 / nnsearch chamfer_distance.cpp:39-62):
+// dist[i][p] = min_q |A_i[p] - B_i[q]|^2, idx[i][p] = the LOWEST q attaining it.  The work split and the inner loop are
+// chamfer_dir_kernel<true>'s (a wave owns 512 points of A in registers, B_i streamed through the double-buffered LDS chunks,
+// the same three packed operations per distance: a distance here is the one dg_chamfer_paired sums, bit for bit).  The loop
+// tracks the minimum only; per point and chunk ONE strict compare notes the chunk in which the running minimum last fell,
+// i.e. the first chunk that attains the final minimum.  After the stream every lane rescans the winning chunk of each of its
+// points (from global memory: the chunks differ lane to lane) for the first minimum, strict `<` - the reference's rule.
+// Clouds come with a point stride and a channel stride (planar [B,3,HW] point maps and [B,n,3] clouds alike).  Every dist /
+// idx element has one writer; no atomics.
+__global__ __launch_bounds__(CH_THREADS) void chamfer_nn_kernel(const float* __restrict__ A, long a_sb, int a_sp, int a_sc,
+                                                                int n, const float* __restrict__ Bc, long b_sb, int b_sp,
+                                                                int b_sc, int m, float* __restrict__ dist,
+                                                                int* __restrict__ idx) {
+  __shared__ float4 qbuf[2][CH_MC];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = blockIdx.y, slice = blockIdx.z * 4 + wave;
+  const int p0 = slice * CH_WPTS + lane * CH_PT;
+  f2 px[CH_PT / 2], py[CH_PT / 2], pz[CH_PT / 2];
+  const float* a = A + (long)i * a_sb;
+  const float* q = Bc + (long)i * b_sb;
+#pragma unroll
+  for (int h = 0; h < CH_PT / 2; ++h) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int p = p0 + 2 * h + e;
+      const long pp = (long)(p < n ? p : 0) * a_sp;  // out-of-range slots replicate point 0 and store nothing
+      px[h][e] = a[pp];
+      py[h][e] = a[pp + a_sc];
+      pz[h][e] = a[pp + 2l * a_sc];
+    }
+  }
+  const int nchunk = (m + CH_MC - 1) / CH_MC;
+  float r[CH_LD][3];
+  auto fetch = [&](int c) {
+#pragma unroll
+    for (int u = 0; u < CH_LD; ++u) {
+      const int k = c * CH_MC + u * CH_THREADS + tid;
+      const long kk = (long)(k < m ? k : 0) * b_sp;  // the last chunk's tail repeats point 0: chunk 0 holds it first
+      r[u][0] = q[kk]; r[u][1] = q[kk + b_sc]; r[u][2] = q[kk + 2l * b_sc];
+    }
+  };
+  auto commit = [&](int buf) {
+#pragma unroll
+    for (int u = 0; u < CH_LD; ++u) qbuf[buf][u * CH_THREADS + tid] = make_float4(r[u][0], r[u][1], r[u][2], 0.f);
+  };
+  f2 rmin[CH_PT / 2];
+  int wch[CH_PT];
+#pragma unroll
+  for (int h = 0; h < CH_PT / 2; ++h) {
+    rmin[h] = (f2){3.0e38f, 3.0e38f};
+    wch[2 * h] = 0; wch[2 * h + 1] = 0;
+  }
+  fetch(0);
+  commit(0);
+  __syncthreads();
+  for (int c = 0; c < nchunk; ++c) {
+    const int buf = c & 1;
+    if (c + 1 < nchunk) fetch(c + 1);
+    f2 was[CH_PT / 2];
+#pragma unroll
+    for (int h = 0; h < CH_PT / 2; ++h) was[h] = rmin[h];
+#pragma unroll 2
+    for (int t = 0; t < CH_MC; ++t) {
+      const float4 v = qbuf[buf][t];
+      const f2 qx = (f2){v.x, v.x}, qy = (f2){v.y, v.y}, qz = (f2){v.z, v.z};
+#pragma unroll
+      for (int h = 0; h < CH_PT / 2; ++h) {
+        const f2 dx = qx - px[h], dy = qy - py[h], dz = qz - pz[h];
+        f2 d = dx * dx;
+        d = __builtin_elementwise_fma(dy, dy, d);
+        d = __builtin_elementwise_fma(dz, dz, d);
+        rmin[h][0] = __builtin_fminf(rmin[h][0], d[0]);
+        rmin[h][1] = __builtin_fminf(rmin[h][1], d[1]);
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < CH_PT / 2; ++h) {
+      if (rmin[h][0] < was[h][0]) wch[2 * h] = c;
+      if (rmin[h][1] < was[h][1]) wch[2 * h + 1] = c;
+    }
+    if (c + 1 < nchunk) commit(buf ^ 1);
+    __syncthreads();
+  }
+  // the first minimum inside the winning chunk; the distance stored is the streamed one
+#pragma unroll
+  for (int h = 0; h < CH_PT / 2; ++h) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      const int p = p0 + 2 * h + e;
+      if (p >= n) continue;
+      const int k0 = wch[2 * h + e] * CH_MC, k1 = min(m, k0 + CH_MC);
+      const float x = px[h][e], y = py[h][e], z = pz[h][e];
+      float best = 3.0e38f;
+      int bi = k0;
+      for (int k = k0; k < k1; ++k) {
+        const long kk = (long)k * b_sp;
+        const float dx = q[kk] - x, dy = q[kk + b_sc] - y, dz = q[kk + 2l * b_sc] - z;
+        float d = dx * dx;
+        d = __builtin_fmaf(dy, dy, d);
+        d = __builtin_fmaf(dz, dz, d);
+        if (d < best) { best = d; bi = k; }
+      }
+      dist[(long)i * n + p] = rmin[h][e];
+      idx[(long)i * n + p] = bi;
+    }
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------
 // JSD occupancy histogram (utils/metrics/jsd.py:24-79): every point votes for its nearest node of the in-sphere unit
 // grid -- brute force like the reference (argmin over all nodes, first index on ties), nodes streamed through LDS.
 constexpr int GV_CHUNK = 2048;
@@ -432,6 +541,21 @@ int dg_chamfer_paired(const float* A, int n, const float* Bc, int m, int B, floa
   const int zrc = dg_zero_f32(L, B, s);
   if (zrc) return zrc;
   chamfer_dir_kernel<true><<<dim3(1, B, wpc / 4), CH_THREADS, 0, s>>>(A, B, n, wpc, Bc, B, m, 1, L);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
+
+int dg_chamfer_nn(const float* A, long a_sb, long a_sp, long a_sc, int n, const float* Bc, long b_sb, long b_sp, long b_sc,
+                  int m, int B, float* dist, int* idx, void* s_) {
+  if (!A || !Bc || !dist || !idx || B <= 0 || n <= 0 || m <= 0) return DG_EINVAL;
+  if (a_sp <= 0 || a_sc <= 0 || b_sp <= 0 || b_sc <= 0 || a_sb < 0 || b_sb < 0) return DG_EINVAL;
+  // 2^18 points per cloud: what the fixed-point sums behind the search (dg_inv_chamfer_grad) are sized for
+  if (n > (1 << 18) || m > (1 << 18)) return DG_EUNSUPPORTED;
+  if (a_sp > 0x7fffffffL || a_sc > 0x3fffffffL || b_sp > 0x7fffffffL || b_sc > 0x3fffffffL) return DG_EUNSUPPORTED;
+  const int wgs = (n + 4 * CH_WPTS - 1) / (4 * CH_WPTS);   // whole workgroups per cloud, as dg_chamfer_paired
+  if (B > 65535 || wgs > 65535) return DG_EUNSUPPORTED;
+  chamfer_nn_kernel<<<dim3(1, B, wgs), CH_THREADS, 0, (hipStream_t)s_>>>(A, a_sb, (int)a_sp, (int)a_sc, n, Bc, b_sb,
+                                                                        (int)b_sp, (int)b_sc, m, dist, idx);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }

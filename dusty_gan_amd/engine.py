@@ -1233,17 +1233,41 @@ class GEngine:
         """One step of the latent optimiser on the frozen generator `st` (S: dusty_gan_amd.inversion.InvState, every buffer
         allocated before the loop): forward in eval mode on self.zT (latent + this step's perturbation, written by the previous
         step's optimizer launch) -> dg_inv_loss_grad (per-sample masked loss and the head gradient, in place of
-        dg_head_post_bwd) -> the data-only backward-data chain -> grad_z into its fixed buffer -> dg_sphere_adam (Adam,
+        dg_head_post_bwd) and / or the Chamfer term (dg_inv_to_xyz, two dg_chamfer_nn searches, dg_inv_chamfer_scatter,
+        dg_inv_chamfer_grad: demo.py:508-515) -> the data-only backward-data chain -> grad_z into its fixed buffer -> dg_sphere_adam (Adam,
         renormalisation, the next step's perturbed latent into self.zT).  No parameter, gradient or counter of the model is
         touched: the step's only state is S's.  Returns the forward's output dict (views of engine workspaces)."""
         c, lib = self.cfg, L.lib()
         B, sp = S.B, L.stream_ptr()
         out = self.forward(st, S.latent, S.gumbel, training=False, z_ready=True, want_sums=False)
         pm = self.draw_pm is not None   # bf16: the chain reads the pixel-major copy only
-        L.check(lib.dg_inv_loss_grad(L.ptr(self.gout), c.nheads * self.HW, 1, L.ptr(S.ref), L.ptr(S.mask), L.ptr(S.msum),
-                                     S.l2, B, self.HW, self.head_scales[0], None if pm else L.ptr(self.draw), c.nheads,
-                                     L.ptr(self.draw_pm), self.cp, L.ptr(S.parts), L.ptr(S.tickets), S.nchunk,
-                                     L.ptr(S.loss), sp), "dg_inv_loss_grad")
+        C = S.chamfer
+        nterm = len(S.terms) + (C is not None)
+        # one term: it writes the head gradient where the chain reads it.  Several (demo.py:509-519): summed in a fixed order
+        # (l1, l2, chamfer) in the planar fp32 gradient; the last one also writes the sum's bf16 pixel-major copy
+        for i, code in enumerate(S.terms):
+            fn, what = (lib.dg_inv_loss_grad, "dg_inv_loss_grad") if i == 0 else (lib.dg_inv_loss_grad_add, "dg_inv_loss_grad_add")
+            draw = L.ptr(self.draw) if (nterm > 1 or not pm) else None
+            draw_pm = L.ptr(self.draw_pm) if i == nterm - 1 else None
+            L.check(fn(L.ptr(self.gout), c.nheads * self.HW, 1, L.ptr(S.ref), L.ptr(S.mask), L.ptr(S.msum), code, B, self.HW,
+                       self.head_scales[0], draw, c.nheads, draw_pm, self.cp, L.ptr(S.parts), L.ptr(S.tickets), S.nchunk,
+                       L.ptr(S.loss), sp), what)
+        if C is not None:
+            HW, arch = self.HW, ARCH_ID[c.arch]
+            depth = out["depth"]   # the MASKED depth: this term's gradient reaches the confidence head through it
+            L.check(lib.dg_inv_to_xyz(L.ptr(depth), L.ptr(C.angle), B, c.H, c.W, 1, C.min_depth, C.max_depth, 0.0, C.tol, None,
+                                      L.ptr(C.P), sp), "dg_inv_to_xyz")
+            cloud = (3 * HW, 1, HW, HW)   # planar point maps: sample, point and channel strides, points
+            L.check(lib.dg_chamfer_nn(L.ptr(C.R), *cloud, L.ptr(C.P), *cloud, B, L.ptr(C.d1), L.ptr(C.idx1), sp), "dg_chamfer_nn")
+            L.check(lib.dg_chamfer_nn(L.ptr(C.P), *cloud, L.ptr(C.R), *cloud, B, L.ptr(C.d2), L.ptr(C.idx2), sp), "dg_chamfer_nn")
+            L.check(lib.dg_inv_chamfer_scatter(L.ptr(C.R), L.ptr(C.idx1), B, HW, L.ptr(C.acc), sp), "dg_inv_chamfer_scatter")
+            add = int(nterm > 1)
+            L.check(lib.dg_inv_chamfer_grad(L.ptr(C.P), L.ptr(C.R), L.ptr(C.d1), L.ptr(C.d2), L.ptr(C.idx2), L.ptr(C.acc),
+                                            L.ptr(depth), L.ptr(C.angle), L.ptr(self.gout),
+                                            L.ptr(self.noise_pixel) if arch else None, L.ptr(self.mask) if arch else None, arch,
+                                            c.tau, c.drop_const, C.min_depth, C.max_depth, C.tol, B, HW, *self.head_scales, add,
+                                            L.ptr(self.draw) if (add or not pm) else None, c.nheads, L.ptr(self.draw_pm), self.cp,
+                                            L.ptr(S.parts), L.ptr(S.tickets), S.nchunk, L.ptr(S.loss), sp), "dg_inv_chamfer_grad")
         self._backward_chain(st, None, self.draw, self.draw_pm, self.dp, acts=None, chain=None, second_of=None,
                              head_ready=True)
         dzT = self.grad_z_T(st)

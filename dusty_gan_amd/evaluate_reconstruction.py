@@ -1,7 +1,7 @@
 """Reconstruction evaluation by GAN inversion -- reference: evaluate_reconstruction.py (same flags, same CSV).
 
     python -m dusty_gan_amd.evaluate_reconstruction --model-path <ckpt.pth> --config-path <config.yaml>
-        [--save-dir-path .] [--tol 0] [--batch-size 512] [--distance l1|l2] [--num-step 1000]
+        [--save-dir-path .] [--tol 0] [--batch-size 512] [--distance l1|l2|chamfer|l1+chamfer|...] [--num-step 1000]
 
 Every test scan is reconstructed by optimising the latent of the EMA generator (dusty_gan_amd.inversion.invert), then
 scored per scan: Chamfer distance of the point clouds, depth accuracy / error, and the drop ratios."""
@@ -15,6 +15,21 @@ COLUMNS = ["cd", "accuracy_1", "accuracy_2", "accuracy_3", "rmse", "rmse_log", "
            "drop_ref"]
 
 
+TERMS = ("l1", "l2", "chamfer")
+
+
+def split_distance(text):
+    """"l1+chamfer" -> ("l1", "chamfer"): the terms of the inversion loss, summed (demo.py:509-519)"""
+    return tuple(text.split("+"))
+
+
+def _distance_arg(text):
+    names = split_distance(text)
+    if any(n not in TERMS for n in names):
+        raise argparse.ArgumentTypeError(f"{text!r}: '+'-joined terms out of {', '.join(TERMS)}")
+    return text
+
+
 def parse_args(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument("--model-path", type=str, required=True)
@@ -22,7 +37,10 @@ def parse_args(argv=None):
     parser.add_argument("--save-dir-path", type=str, default=".")
     parser.add_argument("--tol", type=float, default=0)
     parser.add_argument("--batch-size", type=int, default=512)
-    parser.add_argument("--distance", default="l1", choices=["l1", "l2"])
+    parser.add_argument("--distance", default="l1", type=_distance_arg,
+                        help="the inversion loss: l1 or l2 (the reference's command), or - beyond the reference's command, "
+                             "which offers those two only - chamfer (the third loss of the reference's demo, demo.py:508-519) "
+                             "and '+'-joined sums such as l1+chamfer")
     parser.add_argument("--num-step", type=int, default=1000)
     return parser.parse_args(argv)
 
@@ -41,7 +59,9 @@ def evaluate_batch(G, lidar, arch, item, args):
     xyz, depth, mask = item["xyz"], item["depth"], item["mask"].float()
     inv = lidar.invert_depth(depth)
     inv_ref = mask * inv + (1 - mask) * 0.0   # preprocess_reals (:63-69)
-    res = invert(G, inv_ref, mask, num_step=args.num_step, distance=args.distance)
+    names = split_distance(args.distance)
+    res = invert(G, inv_ref, mask, num_step=args.num_step, distance=names[0] if len(names) == 1 else names,
+                 lidar=lidar if "chamfer" in names else None)
     out = postprocess(res["out"], lidar, tol=args.tol)
     cd = compute_cd(flatten(xyz.float()), flatten(out["points"]))
     if "dusty" in arch:

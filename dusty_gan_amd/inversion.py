@@ -2,7 +2,9 @@
 evaluate_reconstruction.py:32-164 (the loop) with utils/__init__.py:224-246 (SphericalOptimizer, masked_loss).
 
 Every step is forward (eval mode) -> dg_inv_loss_grad -> the generator's backward-data chain -> grad_z ->
-dg_sphere_adam (GEngine.inversion_step).  The step index, the Adam moments and the latent live on the device, so one
+dg_sphere_adam (GEngine.inversion_step).  The reference's demo adds a third loss, "chamfer" (demo.py:508-519): the symmetric
+Chamfer distance between the target's points and postprocess(out)["points"], the one term whose gradient reaches the
+measurability head - dg_inv_to_xyz -> two dg_chamfer_nn searches -> dg_inv_chamfer_scatter -> dg_inv_chamfer_grad.  The step index, the Adam moments and the latent live on the device, so one
 step is captured in a hipGraph and replayed; the scalars are read back once, after the loop."""
 import gc
 import math
@@ -56,6 +58,54 @@ def _draw_logistic(seed, stream_id, n, eps, device):
     return out
 
 
+DISTANCES = ("l1", "l2", "chamfer")   # the order the terms are evaluated and summed in
+
+
+def check_distance(distance, lidar=None):
+    """`distance` of invert - one of DISTANCES or a sequence of them (demo.py:509-519: the loss is their sum) - as a tuple
+    in DISTANCES' order.  ValueError for an empty selection or "chamfer" without a LiDAR; needs no device."""
+    names = (distance,) if isinstance(distance, str) else tuple(distance)
+    if len(names) == 0:
+        raise ValueError("no distance selected: give at least one of " + ", ".join(DISTANCES))
+    for n in names:
+        if n not in DISTANCES:
+            raise NotImplementedError(n)
+    if "chamfer" in names:
+        if lidar is None:
+            raise ValueError('distance "chamfer" needs lidar= (dusty_gan_amd.utils.lidar.LiDAR with its angle grid)')
+        if getattr(lidar, "angle", None) is None:
+            raise ValueError('distance "chamfer" needs a LiDAR with an angle grid (angles.pt or use_nominal_angles)')
+        if float(lidar.drop_const) != 0.0:
+            raise ValueError("the Chamfer term is built for the LiDAR's own drop_const of 0 (utils/lidar.py:12)")
+    return tuple(n for n in DISTANCES if n in names)
+
+
+class ChamferState:
+    """The Chamfer term's buffers: the target's points R (made once), the generated points, both searches' results and the
+    scatter words (zero at rest)."""
+
+    def __init__(self, inv_ref, lidar, tol):
+        dev = inv_ref.device
+        B, _, H, W = inv_ref.shape
+        HW = H * W
+        if HW > (1 << 18):
+            raise ValueError("the Chamfer term holds at most 2^18 points per scan")
+        assert (H, W) == (lidar.H, lidar.W)
+        self.tol = float(tol)
+        self.min_depth, self.max_depth = lidar.min_depth, lidar.max_depth
+        self.angle = lidar.angle.detach().to(dev).float().reshape(2, HW).contiguous()   # (a copy: the caller's LiDAR stays as it is)
+        self.R = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
+        ref = inv_ref.detach().float().contiguous()
+        L.check(L.lib().dg_inv_to_xyz(L.ptr(ref), L.ptr(self.angle), B, H, W, 0, self.min_depth, self.max_depth, 0.0, self.tol,
+                                      None, L.ptr(self.R), L.stream_ptr()), "dg_inv_to_xyz")
+        self.P = torch.empty_like(self.R)
+        self.d1 = torch.empty(B, HW, dtype=torch.float32, device=dev)
+        self.d2 = torch.empty_like(self.d1)
+        self.idx1 = torch.empty(B, HW, dtype=torch.int32, device=dev)
+        self.idx2 = torch.empty_like(self.idx1)
+        self.acc = torch.zeros(B, HW, 4, dtype=torch.int64, device=dev)
+
+
 def _backbone(G):
     return G.backbone if hasattr(G, "backbone") else G
 
@@ -79,14 +129,16 @@ class InvState:
     NCHUNK = 16   # workgroups per sample of dg_inv_loss_grad
 
     def __init__(self, inv_ref, mask_ref, latent, gumbel, *, num_step, distance, lr, perturb_latent, noise_ratio,
-                 noise_sigma, lr_rampup_ratio, lr_rampdown_ratio, seed):
+                 noise_sigma, lr_rampup_ratio, lr_rampdown_ratio, seed, lidar=None, tol=1e-8):
         dev = inv_ref.device
         B, _, H, W = inv_ref.shape
         self.B, self.HW = B, H * W
         self.ref = inv_ref.detach().float().contiguous()
         self.mask = mask_ref.detach().float().contiguous()
         self.msum = self.mask.sum(dim=(1, 2, 3)).contiguous()   # integers: exact in any order
-        self.l2 = {"l1": 0, "l2": 1}[distance]
+        names = check_distance(distance, lidar)
+        self.terms = tuple({"l1": 0, "l2": 1}[n] for n in names if n != "chamfer")   # dg_inv_loss_grad's distance codes
+        self.chamfer = ChamferState(inv_ref, lidar, tol) if "chamfer" in names else None
         self.latent = latent
         self.m = torch.zeros_like(latent)
         self.v = torch.zeros_like(latent)
@@ -122,10 +174,12 @@ class InvState:
 
 def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, perturb_latent=True, noise_ratio=0.75,
            noise_sigma=1.0, lr_rampup_ratio=0.05, lr_rampdown_ratio=0.25, seed=0, latent=None, graph=True,
-           noise_fn=None, gumbel_noise=None, on_step=None):
+           noise_fn=None, gumbel_noise=None, on_step=None, lidar=None, tol=1e-8):
     """Reconstruct inv_ref [B,1,H,W] (inverse depth in [0,1]) under mask_ref [B,1,H,W] by optimising G's latent
     (evaluate_reconstruction.py:84-118).  G: what utils.setup returns (the bare 'none' generator or a DUSty1 / DUSty2
     wrapper), run in eval mode at its own precision; nothing of G is modified.
+    distance: "l1", "l2", "chamfer" or a sequence of them; the per-sample loss is their sum (demo.py:509-519).  "chamfer"
+    needs lidar= (utils.lidar.LiDAR with its angle grid) and takes tol, postprocess's validity threshold.
     latent: the initial latent [B,nz] (default: Philox normal draws of `seed`, rows normalised as the reference does).
     Test hooks: noise_fn(k) -> the perturbation [B,nz] added to the latent at step k (replaces the Philox draws; eager
     loop), gumbel_noise [1,1,H,W] the fixed pixel-level logistic noise of the dusty archs, on_step(k, loss [B],
@@ -134,11 +188,10 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
     Returns {"latent", "out", "inv_gen", "loss"}: the reference's loop variables after the loop - the optimised latent, the
     last step's generator output and tanh_to_sigmoid of its unmasked depth, and the last step's per-sample loss."""
     from .utils.lidar import unit_map
+    check_distance(distance, lidar)
     bb = _backbone(G)
     if not inv_ref.is_cuda:
         raise RuntimeError("invert runs on the GPU only (no CPU fallback)")
-    if distance not in ("l1", "l2"):
-        raise NotImplementedError(distance)
     if num_step < 1:
         raise ValueError("num_step must be >= 1")
     dev = inv_ref.device
@@ -153,7 +206,8 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
     latent = latent.detach().to(dev).float().clone().contiguous()
     S = InvState(inv_ref, mask_ref, latent, _fixed_gumbel(G, B, H, W, seed, dev, gumbel_noise), num_step=num_step,
                  distance=distance, lr=lr, perturb_latent=perturb_latent, noise_ratio=noise_ratio, noise_sigma=noise_sigma,
-                 lr_rampup_ratio=lr_rampup_ratio, lr_rampdown_ratio=lr_rampdown_ratio, seed=seed)
+                 lr_rampup_ratio=lr_rampup_ratio, lr_rampdown_ratio=lr_rampdown_ratio, seed=seed,
+                 lidar=lidar, tol=tol)
     # every buffer of the loop exists before it, allocated on the caller's stream
     eng.alloc(B, dev)
     eng.grad_z_buffers()

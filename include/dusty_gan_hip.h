@@ -495,6 +495,14 @@ int dg_chamfer_dir(const float* A, int Na, int n, const float* Bc, int Nb, int m
  * bit-reproducible run to run there); compute_cd of
  * utils/metrics/cov_mmd_1nna.py:19-21 on paired sets = L_AB + L_BA (evaluate_reconstruction.py:126). */
 int dg_chamfer_paired(const float* A, int n, const float* Bc, int m, int B, float* L, void* stream);
+/* dg_chamfer_nn: the paired nearest-neighbour search WITH indices (chamfer_distance.cu:9-127, nnsearch
+ * chamfer_distance.cpp:39-62), the differentiable form: for B pairs A_i (n points), B_i (m points)
+ * dist[i][p] = min_q |A_i[p] - B_i[q]|^2 and idx[i][p] = the LOWEST q that attains it (the reference's strict `<`,
+ * chamfer_distance.cu:33,123 / .cpp:53).  Coordinate c of point p of cloud i is X[i x_sb + p x_sp + c x_sc]: a planar
+ * point map [B,3,HW] is (3 HW, 1, HW), a cloud [B,n,3] is (3 n, 3, 1).  dist [B,n] fp32, idx [B,n] int32, one writer per
+ * element, no atomics; a distance is the one dg_chamfer_paired sums, bit for bit.  n or m above 2^18: DG_EUNSUPPORTED. */
+int dg_chamfer_nn(const float* A, long a_sb, long a_sp, long a_sc, int n, const float* Bc, long b_sb, long b_sp, long b_sc,
+                  int m, int B, float* dist, int* idx, void* stream);
 /* dg_emd: approximate earth mover's distance  utils/metrics/distance/emd/earth_mover_distance.cu (approxmatch :28-190
  * + matchcost :218-262 fused; the [m,n] match matrix is never stored).  paired = 1: out[i] = emd(A_i, B_i) (Na == Nb,
  * the extension's semantics); paired = 0: out [Na,Nb] for all pairs.  The value is the raw cost (compute_emd of
@@ -716,6 +724,33 @@ int dg_adam_proj_fused(float* p, float* v, float* ema, void* shadow, int shadow_
 int dg_inv_loss_grad(const float* gen, long gen_sb, int from_tanh, const float* ref, const float* mask, const float* msum,
                      int distance, int B, long HW, float s_depth, float* draw, int nheads, void* draw_pm, int cp,
                      float* parts, unsigned* tickets, int nchunk, float* loss, void* stream);
+/* dg_inv_loss_grad_add: the same, as a FURTHER term of the loss (demo.py:516-519 adds l1 and l2): loss[b] += the term, the
+ * depth channel of draw (required) += its gradient, and draw_pm, when given, = the planar sums rounded to bf16. */
+int dg_inv_loss_grad_add(const float* gen, long gen_sb, int from_tanh, const float* ref, const float* mask, const float* msum,
+                         int distance, int B, long HW, float s_depth, float* draw, int nheads, void* draw_pm, int cp,
+                         float* parts, unsigned* tickets, int nchunk, float* loss, void* stream);
+/* The Chamfer term of the inversion loss  demo.py:508-515 with chamfer_distance.cpp:82-140: loss_b = mean_j d1 + mean_k d2
+ * between the target's points R and P = postprocess(out)["points"] (utils/__init__.py:163-178), both planar [B,3,HW] as
+ * dg_inv_to_xyz writes them (HW <= 2^18), with (d1, idx1) = dg_chamfer_nn(R, P) and (d2, idx2) = dg_chamfer_nn(P, R).
+ * dg_inv_chamfer_scatter: for every target point j adds R_j and a count of 1 to generated pixel idx1[j] in acc [B,HW,4]
+ * u64 words (24.40 fixed point, dg_fix40 of csrc/common.h, word 3 the count; integer atomics: order-independent), ZERO AT
+ * REST: dg_inv_chamfer_grad zeroes what it reads.
+ * dg_inv_chamfer_grad: loss[b] = (or += with add) the term, per-sample sums in the fixed order of dg_inv_loss_grad (parts
+ * [B*nchunk], tickets [B]), and per generated pixel k  gP = (2/HW)(P_k - R_idx2[k]) + (2/HW)(c_k P_k - S_k), chained through
+ * Coordinate.inv_to_xyz (utils/lidar.py:61-68; angle [2,HW], the LiDAR's drop_const 0, `tol`), the closed-interval clamp
+ * and tanh_to_sigmoid to g = d loss_b / d depth (depth [B,HW]: the generator's MASKED depth), then the head gradient of
+ * the EVAL-mode graph (models/dusty.py:45-59,77-91,107-127) where dg_head_post_bwd writes its: depth channel g mask
+ * (1 - t^2) s_depth, pixel confidence g (t - drop_const) mask_image sp (1 - sp) / tau s_conf (the straight-through Gumbel
+ * sigmoid under the fixed noise_pixel [B,HW]), dusty2's image channel 0 (eval: a plain threshold, :120).  gout [B,nheads,HW]
+ * (tanh'd depth, logits) and mask [B,arch,HW] as dg_head_post_fwd left them; nheads = arch + 1.  draw planar fp32 and / or
+ * draw_pm [B,HW,cp] bf16 (the planar value rounded); add = 1: the gradient is added to what draw (required) holds. */
+int dg_inv_chamfer_scatter(const float* R, const int* idx1, int B, long HW, unsigned long long* acc, void* stream);
+int dg_inv_chamfer_grad(const float* P, const float* R, const float* d1, const float* d2, const int* idx2,
+                        unsigned long long* acc, const float* depth, const float* angle, const float* gout,
+                        const float* noise_pixel, const float* mask, int arch, float tau, float drop_const, float min_depth,
+                        float max_depth, float tol, int B, long HW, float s_depth, float s_conf, int add, float* draw,
+                        int nheads, void* draw_pm, int cp, float* parts, unsigned* tickets, int nchunk, float* loss,
+                        void* stream);
 int dg_sphere_adam(const float* grad, long g_sb, long g_sk, float* latent, float* m, float* v, unsigned long long* step_dev,
                    unsigned* ticket, const float* noise_in, void* zT, int z_dtype, int B, int nz, const float* sched,
                    int num_step, float beta1, float beta2, float eps, int perturb, uint64_t seed, uint64_t stream_id, int prime,
