@@ -1,6 +1,7 @@
 // extern "C" dispatchers of the conv-like passes (include/dusty_gan_hip.h): one selector per pass (select_conv,
 // select_wgrad) turns a `force` request into the kernel that runs; every entry point selects, then launches or describes.
 #include "common.h"
+#include "thin.h"
 
 int dg_conv_direct_launch(const ConvP* p, hipStream_t stream);
 int dg_lrelu_bits_launch(const ConvP* p, hipStream_t stream);
@@ -8,21 +9,12 @@ int dg_conv_mfma_launch(const ConvP* p, hipStream_t stream, int force, int fp32x
 int dg_wgrad_mfma_dma_supported(const WgradP* p);
 int dg_wgrad_mfma_dma_launch(const WgradP* p, int accumulate, int pairs, hipStream_t stream, DgWgradPlan* plan);
 int dg_wgrad_mfma_dma_group_launch(const WgradP* items, int n, int pairs, int rounds, hipStream_t stream, DgWgradPlan* plans);
-int dg_conv_thin_launch(const ConvP* p, hipStream_t stream);
-int dg_conv_thin_supported(const ConvP* p);
 int dg_proj_stream_supported(const ConvP* p);
 int dg_proj_stream_launch(const ConvP* p, hipStream_t stream, DgConvPlan* plan);
-int dg_conv_thin_mfma_variant(const ConvP* p);
-int dg_conv_up_mfma_sum_parts(const ConvP* p);
-int dg_conv_s2_mfma_blocks(const ConvP* p);
-int dg_wgrad_thin_mfma_variant(const WgradP* p);
-int dg_wgrad_thin_ws_splits(const WgradP* p);
 int dg_wgrad_mfma_ws_splits(const WgradP* p, int accumulate);
 int dg_wgrad_direct_ws_splits(const WgradP* p);
 int dg_wgrad_direct_launch(const WgradP* p, hipStream_t stream);
 int dg_wgrad_mfma_launch(const WgradP* p, int accumulate, hipStream_t stream, int x3);
-int dg_wgrad_thin_launch(const WgradP* p, hipStream_t stream);
-int dg_wgrad_thin_supported(const WgradP* p);
 
 // `force` carries one flag bit beside the request code: DG_FORCE_FP32X3 (include/dusty_gan_hip.h) - fp32 operands through
 // split-bf16 matrix instructions (mfma_common.h).  Per CALL, so two engines of different precision in one process do not
@@ -36,7 +28,7 @@ enum ConvKernel { CONV_DIRECT, CONV_THIN, CONV_MFMA, CONV_PROJ_STREAM };
 // The saved-mask fields: mask_out is honoured behind EVERY kernel (natively by the ping-pong conv and the thin matrix-core
 // MODE_S2 kernel - DgConvPlan.mask_bits & 1 - otherwise by one packing launch over the output, conv_dispatch), mask_in only
 // by kernels that take bits (the others read aux, which stays mandatory).
-int select_conv(const DgConv* p, int force_flags, ConvKernel* k, DgConvPlan* plan) {
+int select_conv(const DgConv* p, int force_flags, ConvKernel* k, ThinConvPick* thin, DgConvPlan* plan) {
   if (p && (p->mask_out || p->mask_in)) {
     if (p->mask_out && p->epi != EPI_LRELU) return DG_EINVAL;
     if (p->mask_in && p->epi != EPI_MASK) return DG_EINVAL;
@@ -50,7 +42,7 @@ int select_conv(const DgConv* p, int force_flags, ConvKernel* k, DgConvPlan* pla
   if (p->dbias && p->bias_mod <= 0) return DG_EINVAL;
   if (plan) *plan = DgConvPlan{};
   const int force = force_flags & ~DG_FORCE_FP32X3;
-  const bool mfma_ok = !p->nscale && dg_conv_mfma_supported(p), thin_ok = dg_conv_thin_supported(p);
+  const bool mfma_ok = !p->nscale && dg_conv_mfma_supported(p), thin_ok = thin_conv_pick(p, thin) == DG_OK;
   const bool proj_ok = dg_proj_stream_supported(p);   // Proj forward (bf16, K = 512, B <= 32): replaces the general MFMA kernel
   bool ok = true;
   if (force == DG_FORCE_AUTO) *k = proj_ok ? CONV_PROJ_STREAM : (mfma_ok ? CONV_MFMA : (thin_ok ? CONV_THIN : CONV_DIRECT));
@@ -63,28 +55,25 @@ int select_conv(const DgConv* p, int force_flags, ConvKernel* k, DgConvPlan* pla
 }
 
 // launch kernel k, or (plan != NULL) describe the launch
-int conv_run(const DgConv* p, ConvKernel k, int force_flags, int wg_cap, hipStream_t s, DgConvPlan* plan) {
+int conv_run(const DgConv* p, ConvKernel k, const ThinConvPick& thin, int force_flags, int wg_cap, hipStream_t s, DgConvPlan* plan) {
   if (k == CONV_PROJ_STREAM) return dg_proj_stream_launch(p, s, plan);
   if (k == CONV_MFMA)
     return dg_conv_mfma_launch(p, s, force_flags & ~DG_FORCE_FP32X3, (force_flags & DG_FORCE_FP32X3) ? 1 : 0, wg_cap, plan);
-  if (!plan) return k == CONV_THIN ? dg_conv_thin_launch(p, s) : dg_conv_direct_launch(p, s);
+  if (!plan) return k == CONV_THIN ? thin_conv_launch(p, thin, s) : dg_conv_direct_launch(p, s);
   plan->family = k == CONV_THIN ? DG_CONV_FAMILY_THIN : DG_CONV_FAMILY_DIRECT;
-  if (k == CONV_THIN) {
-    plan->thin_mfma = dg_conv_thin_mfma_variant(p);
-    plan->mask_bits = plan->thin_mfma == 1 ? 3 : 0;
-    plan->dbias_rows = plan->thin_mfma == 1 ? dg_conv_s2_mfma_blocks(p) : 0;
-    plan->sum_parts = plan->thin_mfma == 2 ? dg_conv_up_mfma_sum_parts(p) : 0;
-  }
+  if (k == CONV_THIN)
+    plan->thin_mfma = thin.thin_mfma, plan->mask_bits = thin.mask_bits, plan->dbias_rows = thin.dbias_rows, plan->sum_parts = thin.sum_parts;
   return DG_OK;
 }
 
 int conv_dispatch(const DgConv* p, int force_flags, int wg_cap, hipStream_t s, DgConvPlan* plan) {
   ConvKernel k;
-  int rc = select_conv(p, force_flags, &k, plan);
-  if (rc || plan || !p->mask_out) return rc ? rc : conv_run(p, k, force_flags, wg_cap, s, plan);
+  ThinConvPick thin;
+  int rc = select_conv(p, force_flags, &k, &thin, plan);
+  if (rc || plan || !p->mask_out) return rc ? rc : conv_run(p, k, thin, force_flags, wg_cap, s, plan);
   DgConvPlan pl{};
-  rc = conv_run(p, k, force_flags, wg_cap, nullptr, &pl);
-  if (rc == DG_OK) rc = conv_run(p, k, force_flags, wg_cap, s, nullptr);
+  rc = conv_run(p, k, thin, force_flags, wg_cap, nullptr, &pl);
+  if (rc == DG_OK) rc = conv_run(p, k, thin, force_flags, wg_cap, s, nullptr);
   if (rc == DG_OK && !(pl.mask_bits & 1)) rc = dg_lrelu_bits_launch(p, s);
   return rc;
 }
@@ -96,6 +85,7 @@ struct WgradKernel {
   long ws_floats;
   bool takes_gmod;  // the kernel honours DgWgrad.g_mod
   bool zero_dw;     // dg_wgrad zero-fills dw in front of it (overwrite without a workspace: the kernel only adds)
+  ThinWgradPick thin;   // DG_WGRAD_VARIANT_THIN / _THIN_MFMA: the kernel and its launch
 };
 
 // The kernel dg_wgrad(p, accumulate, force) runs, or the refusal.  Whether it takes this call's `ws` / `g_mod` is for the
@@ -104,7 +94,8 @@ int select_wgrad(const DgWgrad* p, int accumulate, int force_flags, WgradKernel*
   if (!p || !p->a || !p->g || !p->dw) return DG_EINVAL;
   if (p->B <= 0 || p->Ci <= 0 || p->Co <= 0 || p->Hc <= 0 || p->Wc <= 0) return DG_EINVAL;
   const int force = force_flags & ~DG_FORCE_FP32X3;
-  const bool mfma_ok = dg_wgrad_mfma_supported(p), thin_ok = dg_wgrad_thin_supported(p);
+  ThinWgradPick thin;
+  const bool mfma_ok = dg_wgrad_mfma_supported(p), thin_ok = thin_wgrad_pick(p, &thin) == DG_OK;
   const bool pairs = force == DG_FORCE_WG_DMA_PAIRS || force == DG_FORCE_WG_DMA_NOPAIRS;
   *k = WgradKernel{};
   // bf16 Down / Up layers: the LDS-DMA ring version (wgrad_mfma_dma.hip), with the workspace form and the sample map of its
@@ -124,11 +115,10 @@ int select_wgrad(const DgWgrad* p, int accumulate, int force_flags, WgradKernel*
   // block of the thin kernels (Down1, Head), per K split of the register-staged MFMA kernel (the fp32 modes' fat layers)
   // and of the direct kernel (narrow nets; not under a sample map, nor when the request was some other pass's code);
   // the sample map: Down1's thin matrix-core kernel
-  const int thin_mfma = k->variant == DG_WGRAD_VARIANT_THIN ? dg_wgrad_thin_mfma_variant(p) : 0;
-  if (thin_mfma) k->variant = DG_WGRAD_VARIANT_THIN_MFMA;
-  k->takes_gmod = thin_mfma == 1;
-  if (k->variant == DG_WGRAD_VARIANT_THIN || k->variant == DG_WGRAD_VARIANT_THIN_MFMA) k->splits = dg_wgrad_thin_ws_splits(p);
-  else if (k->variant == DG_WGRAD_VARIANT_MFMA) k->splits = dg_wgrad_mfma_ws_splits(p, accumulate);
+  if (k->variant == DG_WGRAD_VARIANT_THIN) {
+    if (thin.kernel == THIN_WGRAD_DOWN_MFMA || thin.kernel == THIN_WGRAD_UP_MFMA) k->variant = DG_WGRAD_VARIANT_THIN_MFMA;
+    k->thin = thin, k->takes_gmod = thin.takes_gmod, k->splits = thin.splits;
+  } else if (k->variant == DG_WGRAD_VARIANT_MFMA) k->splits = dg_wgrad_mfma_ws_splits(p, accumulate);
   else if ((force == DG_FORCE_AUTO || force == DG_FORCE_DIRECT) && !p->g_mod) k->splits = dg_wgrad_direct_ws_splits(p);
   k->ws_floats = k->splits * (long)(p->wmode == 2 ? 1 : 16) * p->Ci * p->Co;   // (the thin kernels: wmode 0 / 1)
   k->zero_dw = !accumulate && !p->ws && k->variant != DG_WGRAD_VARIANT_MFMA;   // (workspace form: the reduce overwrites dw)
@@ -147,7 +137,7 @@ int wgrad_dispatch(const DgWgrad* p, int accumulate, int force_flags, hipStream_
   if (k.variant == DG_WGRAD_VARIANT_MFMA) return dg_wgrad_mfma_launch(p, accumulate, s, (force_flags & DG_FORCE_FP32X3) ? 1 : 0);
   const int zrc = k.zero_dw ? dg_zero_f32(p->dw, (long)(p->wmode == 2 ? 1 : 16) * p->Ci * p->Co, s) : DG_OK;
   if (zrc) return zrc;
-  return k.variant == DG_WGRAD_VARIANT_DIRECT ? dg_wgrad_direct_launch(p, s) : dg_wgrad_thin_launch(p, s);
+  return k.variant == DG_WGRAD_VARIANT_DIRECT ? dg_wgrad_direct_launch(p, s) : thin_wgrad_launch(p, k.thin, s);
 }
 
 // every item on the LDS-DMA kernel, as one launch

@@ -1,4 +1,4 @@
-// Weight fragments of thin_up_mfma (conv_thin.hip): for each boundary class of an output row (0 interior, 1 first row,
+// Weight fragments of thin_up_mfma (thin_up_mfma.hip): for each boundary class of an output row (0 interior, 1 first row,
 // 2 last row) the 18 MFMA A fragments [frag f = ((dr + 1) * 3 + (dc + 1)) * 2 + half][64 lanes][8 bf16], i.e. the taps of
 // the 3 x 3 coarse neighbourhood folded per (row parity, column parity, output channel).  Built either by
 // thin_up_prep_kernel in front of a launch (from the bf16 shadow) or, for weights registered by the caller, by the extra

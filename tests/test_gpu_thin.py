@@ -1,4 +1,4 @@
-"""GPU parity of the thin (<= 4-channel side) LDS/VALU kernels of csrc/conv_thin.hip against the CPU oracle:
+"""GPU parity of the thin (<= 4-channel side) LDS/VALU kernels picked in csrc/conv_thin.hip (csrc/thin_*.hip) against the CPU oracle:
 Down1 forward / backward-data / weight gradient (Cin = 2) and Head forward / backward-data / weight gradient
 (Cout = 1..3), in fp32 and bf16 feature-map storage, forced through the thin path (DG_FORCE_THIN)."""
 import math
@@ -433,3 +433,109 @@ def test_param_store_rebuilds_up_fragments_with_every_refresh(L):
     st3.apply(lambda t: t.to(DEV))
     st3.refresh_shadows(torch.float32)
     assert st3.up_frag("d1_w", (2 * 64, 64, 1), 2, 32, 1) is None                    # fp32: the kernel prepares its own
+
+
+# ---- the launch fills exactly what its plan promised --------------------------------------------------------------------
+# The engine sizes a launch's workspace from the plan (dg_wgrad_plan's ws_floats, DgConvPlan's dbias_rows / sum_parts); the
+# launch writes it from its grid.  Both come from one pick (csrc/thin.h).  Here the buffer is the planned size, NaN-filled,
+# followed by a guard of allocated memory holding a sentinel: afterwards no NaN is left and the guard is untouched.
+GUARD, SENTINEL = 4096, 12345.0
+
+
+def _guarded(n):
+    buf = torch.full((n + GUARD,), SENTINEL, device=DEV)
+    buf[:n] = float("nan")
+    return buf
+
+
+def _filled_exactly(buf, n):
+    torch.cuda.synchronize()
+    assert n > 0 and buf.numel() == n + GUARD
+    assert not bool(torch.isnan(buf[:n]).any()), f"{int(torch.isnan(buf[:n]).sum())} of {n} planned floats were not written"
+    assert bool((buf[n:] == SENTINEL).all()), "the launch wrote past what its plan promised"
+
+
+@pytest.mark.parametrize("case,B,Hc,Wc,splits", [("down_mfma", 3, 4, 64, 6), ("down_mfma", 2, 8, 256, 8),
+                                                 ("up_mfma_1_of_2", 2, 4, 64, 4), ("up_mfma_3_of_4", 2, 4, 64, 4),
+                                                 ("down_valu", 3, 4, 64, 12), ("up_valu_3", 2, 4, 64, 8)])
+def test_wgrad_launch_fills_exactly_the_planned_workspace(L, case, B, Hc, Wc, splits):
+    import ctypes as C
+    from dusty_gan_amd.engine import Ops
+    lib = L.lib()
+    g = torch.Generator().manual_seed(Hc + Wc)
+    dtype = torch.float32 if "valu" in case else torch.bfloat16
+    HW = 4 * Hc * Wc
+    if case.startswith("down"):
+        wmode, Ci, Co = 0, 2, 64
+        a, a_s = torch.randn(B * HW * Ci, generator=g).to(DEV, dtype), (HW * Ci, Ci, 1)
+        e, e_s = torch.randn(B * Hc * Wc * Co, generator=g).to(DEV, dtype), (Hc * Wc * Co, Co, 1)
+    else:
+        wmode, Ci = 1, 64
+        Co, cp = {"up_mfma_1_of_2": (1, 2), "up_mfma_3_of_4": (3, 4), "up_valu_3": (3, 0)}[case]
+        a, a_s = torch.randn(B * Hc * Wc * Ci, generator=g).to(DEV, dtype), (Hc * Wc * Ci, Ci, 1)
+        if cp:                                       # pixel-major copy of the head gradient, padded to cp channels
+            e, e_s = torch.randn(B * HW * cp, generator=g).to(DEV, dtype), (HW * cp, cp, 1)
+        else:                                        # planar fp32
+            e, e_s = torch.randn(B * Co * HW, generator=g).to(DEV, dtype), (Co * HW, 1, HW)
+    dw = torch.zeros(16 * Ci * Co, device=DEV)
+    o = Ops(dtype)
+    p = o._wgrad_params(wmode, True, B, Hc, Wc, Ci, Co, a, a_s, e, e_s, dw.data_ptr(), 1.0, None, None, None, 0, 0, 0)
+    pl = L.DgWgradPlan()
+    L.check(lib.dg_wgrad_plan(C.byref(p), 1, L.DG_FORCE_THIN, C.byref(pl)), "dg_wgrad_plan")
+    assert pl.variant == (L.DG_WGRAD_VARIANT_THIN if "valu" in case else L.DG_WGRAD_VARIANT_THIN_MFMA)
+    assert pl.splits == splits and pl.ws_floats == splits * 16 * Ci * Co
+    ws = _guarded(pl.ws_floats)
+    p.ws = ws.data_ptr()
+    L.check(lib.dg_wgrad(C.byref(p), 1, L.DG_FORCE_THIN, L.stream_ptr()), "dg_wgrad")
+    _filled_exactly(ws, pl.ws_floats)
+
+
+@pytest.mark.parametrize("case", ["s2_mfma_dbias_part", "depth_head_tanh_sum_parts"])
+def test_conv_launch_fills_exactly_the_planned_partials(L, case):
+    import ctypes as C
+    lib = L.lib()
+    g = torch.Generator().manual_seed(11)
+    bf = torch.bfloat16
+    p = L.DgConv()
+    p.ring, p.scale, p.in_sk, p.w_sk = 1, 1.0, 1, 1
+    p.in_dtype = p.out_dtype = p.w_dtype = L.DG_BF16
+    if case == "s2_mfma_dbias_part":                 # Head backward-data from the two-channel pixel-major gradient
+        B, Hc, Wc, K, N = 2, 8, 64, 2, 64
+        HW = 4 * Hc * Wc
+        x = torch.randn(B * HW * K, generator=g).to(DEV, bf)
+        out = torch.empty(B * Hc * Wc * N, device=DEV, dtype=bf)
+        p.mode, p.adj, p.epi = L.MODE_S2, 1, L.EPI_MASK
+        p.in_sb, p.in_sp = HW * K, K
+        p.out_sb, p.out_sp, p.out_sn = Hc * Wc * N, N, 1
+        aux = torch.randn(B * Hc * Wc * N, generator=g).to(DEV, bf)
+        db = torch.zeros(N, device=DEV)
+        scratch = torch.zeros(L.DBIAS_WS_FLOATS, device=DEV)
+        p.aux, p.dbias, p.bias_mod, p.dbias_ws = aux.data_ptr(), db.data_ptr(), N, scratch.data_ptr()
+    else:                                            # the baseline generator's depth head: planar fp32 image, tanh applied
+        B, Hc, Wc, K, N = 2, 20, 128, 64, 1
+        HW = 4 * Hc * Wc
+        x = torch.randn(B * Hc * Wc * K, generator=g).to(DEV, bf)
+        out = torch.empty(B * N * HW, device=DEV)
+        p.mode, p.adj, p.epi, p.out_dtype = L.MODE_UP, 0, L.EPI_LINEAR, L.DG_F32
+        p.in_sb, p.in_sp = Hc * Wc * K, K
+        p.out_sb, p.out_sp, p.out_sn = N * HW, 1, HW
+        bias, nscale = torch.randn(N, generator=g).to(DEV), torch.full((N,), 0.25, device=DEV)
+        p.bias, p.bias_mod, p.nscale = bias.data_ptr(), N, nscale.data_ptr()
+    w = (torch.randn(16 * N * K, generator=g) * 0.5).to(DEV, bf)   # the T shadow [tap][n][k]
+    p.B, p.Hc, p.Wc, p.K, p.N = B, Hc, Wc, K, N
+    p.in_, p.out, p.w = x.data_ptr(), out.data_ptr(), w.data_ptr()
+    p.w_st, p.w_sn = N * K, K
+    pl = L.DgConvPlan()
+    L.check(lib.dg_conv_plan(C.byref(p), L.DG_FORCE_THIN, 0, C.byref(pl)), "dg_conv_plan")
+    if case == "s2_mfma_dbias_part":
+        assert pl.thin_mfma == 1 and pl.dbias_rows == 8
+        n = pl.dbias_rows * N
+        buf = _guarded(n)
+        p.dbias_part = buf.data_ptr()
+    else:
+        assert pl.thin_mfma == 2 and pl.sum_parts == 6
+        n = pl.sum_parts * B
+        buf = _guarded(n)
+        p.tanh_sum_parts = buf.data_ptr()
+    L.check(lib.dg_conv(C.byref(p), L.DG_FORCE_THIN, L.stream_ptr()), "dg_conv")
+    _filled_exactly(buf, n)
