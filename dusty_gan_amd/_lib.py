@@ -190,6 +190,7 @@ PROTOTYPES = {
     "dg_image_grid": [_P, _L, _I, _I, _I, _I, _F, _I, _P, _P],
     "dg_turbo_lut": [_P],
     "dg_fps": [_P, _I, _I, _I, _P, _P, _P, _P],
+    "dg_fps_map": [_P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P],
     "dg_chamfer_dir": [_P, _I, _I, _P, _I, _I, _P, _P],
     "dg_chamfer_paired": [_P, _I, _P, _I, _I, _P, _P],
     "dg_chamfer_nn": [_P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _P, _P, _P],

@@ -37,19 +37,22 @@ def _compute_nna(M_rr, M_rg, M_gg, k, sqrt=False):
 
 
 @torch.no_grad()
-def compute_cov_mmd_1nna(pcs_gen, pcs_ref, batch_size=512, metrics=("cd",), verbose=True):
-    """same signature and result keys as the reference (:113-148); `batch_size` / `verbose` only shaped its Python loop"""
+def compute_cov_mmd_1nna(pcs_gen, pcs_ref, batch_size=512, metrics=("cd",), verbose=True, M_rr=None):
+    """same signature and result keys as the reference (:113-148); `batch_size` / `verbose` only shaped its Python loop.
+    `M_rr`: the reference-against-reference matrix of the (single) metric, for a caller that scores many generated sets
+    against one reference set (tune_tolerance); left out, it is computed here as ever"""
     assert isinstance(metrics, tuple)
+    assert M_rr is None or len(metrics) == 1
     results = {}
     for metric in metrics:
         if metric not in ("cd", "emd"):
             raise NotImplementedError(f"metric '{metric}'")
         pairwise = chamfer_distance_matrix if metric == "cd" else emd_distance_matrix
-        M_rr = pairwise(pcs_ref, pcs_ref)
+        rr = pairwise(pcs_ref, pcs_ref) if M_rr is None else M_rr
         M_rg = pairwise(pcs_ref, pcs_gen)
         M_gg = pairwise(pcs_gen, pcs_gen)
         for k, v in _compute_cov_mmd(M_rg).items():
             results["{}-{}".format(k, metric)] = v
-        for k, v in _compute_nna(M_rr, M_rg, M_gg, k=1, sqrt=False).items():
+        for k, v in _compute_nna(rr, M_rg, M_gg, k=1, sqrt=False).items():
             results["1-nn-{}-{}".format(k, metric)] = v
     return results

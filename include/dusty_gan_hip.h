@@ -488,6 +488,14 @@ int dg_turbo_lut(float* host_out);
  * every point (first index on ties); pts [P,3], grid [Ng,3] (unit_cube_grid_point_cloud :11-21), counters [Ng]
  * accumulate.  dg_jsd: _jensen_shannon_divergence :96-107 of two counter vectors -> out[0]. */
 int dg_fps(const float* xyz, int B, int n, int m, float* temp, int* idx, float* out, void* stream);
+/* dg_fps_map: dg_fps on clouds with strides, addressed as in dg_chamfer_nn: coordinate c of point p of cloud b is
+ * X[b x_sb + p x_sp + c x_sc], so a planar point map [B,3,HW] (3 HW, 1, HW) is sampled where it lies, without the
+ * packed [B,HW,3] copy.  idx [B,m] int32 and out [B,m,3] (nullable) equal dg_fps's on the packed copy of the same points,
+ * bit for bit: one selection rule, one device body.  Planar input (x_sp == 1) of n <= 65 536 points keeps the running
+ * minima in registers and LDS and never touches `temp`, which may then be NULL; every other input keeps them in
+ * temp [B,n] (NULL there: DG_EINVAL). */
+int dg_fps_map(const float* X, long x_sb, long x_sp, long x_sc, int B, int n, int m, float* temp, int* idx, float* out,
+               void* stream);
 int dg_chamfer_dir(const float* A, int Na, int n, const float* Bc, int Nb, int m, float* L, void* stream);
 /* dg_chamfer_paired: the same directed means for B PAIRS of clouds, L[i] = mean_{p in A_i} min_{q in B_i} |p - q|^2 for
  * A [B,n,3], B [B,m,3] -> L [B] (the diagonal of dg_chamfer_dir's matrix: the same per-wave sums; above 1024 points the
