@@ -234,6 +234,9 @@ PROTOTYPES = {
                             _I, _P, _P, _I, _P, _P],
     "dg_sphere_adam": [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _I, _U64, _U64, _I, _P],
     "dg_depth_metrics": [_P, _P, _P, _P, _I, _I, _F, _I, _L, _F, _F, _P, _P],
+    "dg_feat_compose": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "dg_feat_compose_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "dg_alpha_adam": [_P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _L, _P],
 }
 
 _lib = None

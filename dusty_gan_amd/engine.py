@@ -968,8 +968,15 @@ class GEngine:
             z = z.contiguous().float()
             L.check(lib.dg_cast(L.ptr(z), L.ptr(self.zT), o.dt, B * c.nz, sp), "dg_cast")
         self._proj_fwd(st, B, self.zT, self.a[0])
+        return self._forward_from(st, B, 0, noise, training, want_sums)
+
+    def _forward_from(self, st, B, first, noise, training, want_sums):
+        """the generator above a[first] (which holds Proj's / Up_first's output, or a composite of several: multi-code
+        inversion): Up_(first+1)..Up3, the Head and its post-processing; returns forward's output dict"""
+        c, lib, sp = self.cfg, L.lib(), L.stream_ptr()
         for i in (1, 2, 3):
-            self._fwd(st, B, i, self.a[i - 1], self.a[i])
+            if i > first:
+                self._fwd(st, B, i, self.a[i - 1], self.a[i])
         hc = self.grid[3][0]
         # (weight (tap, n = head, k = ci) in the fp32 master [tap][ci][co]: strides (ci co, 1, co))
         frag = (st.up_frag("head_w", (self.chs[3] * c.nheads, 1, c.nheads), c.nheads, hc, 0)
@@ -1054,11 +1061,17 @@ class GEngine:
         g, sg, gdt = self._gout(i, chain)
         self.ops.wgrad(1, self.cfg.ring, B, hc, wc, ci, co, a, sa, g, sg, st.fptr(name + "_w", st.grad), s, g_dt=gdt, defer=True)
 
-    def _bwd_data(self, st, B, i, chain, want_dbias):
+    def _bwd_data(self, st, B, i, chain, want_dbias, unmasked=False):
         """layer i's backward-data into chain dp[i-1]: the gradient w.r.t. the pre-activation of a[i-1], fused lrelu' mask
-        (+ the bias gradient of the layer below)"""
+        (+ the bias gradient of the layer below).  unmasked: the gradient w.r.t. a[i-1] itself (EPI_LINEAR: a[i-1] is a
+        composite of several feature maps, not a leaky-relu output - multi-code inversion)"""
         name, hc, wc, ci, co, sa, _, s = self._layer(i)
         g, sg, gdt = self._gout(i, chain)
+        if unmasked:
+            assert not want_dbias
+            self.ops.conv(L.MODE_S2, 1, self.cfg.ring, B, hc, wc, co, ci, g, sg, chain[2][i - 1], sa, st.sptr(name + "_w"), s,
+                          L.EPI_LINEAR, in_dt=gdt)
+            return
         dbias = st.fptr(f"up{i - 1}_b" if i > 1 else "proj_b", st.grad) if want_dbias else None
         self.ops.conv(L.MODE_S2, 1, self.cfg.ring, B, hc, wc, co, ci, g, sg, chain[2][i - 1], sa, st.sptr(name + "_w"), s,
                       L.EPI_MASK, aux=self.a[i - 1], dbias=dbias, bias_mod=ci, in_dt=gdt, defer_db=True)
@@ -1133,7 +1146,8 @@ class GEngine:
             self.proj_wgrad(st, self.dp[0], self.zT, B, accumulate_proj)
 
     # ------------------------------------------------------------------ path-length regulariser (trainers/dcgan_amp.py:268-306)
-    def _backward_chain(self, st, ddepth, draw, draw_pm, dp, acts, chain, second_of, thead=None, head_ready=False):
+    def _backward_chain(self, st, ddepth, draw, draw_pm, dp, acts, chain, second_of, thead=None, head_ready=False,
+                        layers=(4, 3, 2, 1), unmasked_last=False):
         """One walk down the generator from the head to Proj's pre-activation.
         acts is None  : data only (first-order chain of d(sum x y)/dz).
         head_ready    : (data only) `draw` / `draw_pm` already hold the head gradient (GAN inversion: dg_inv_loss_grad
@@ -1142,9 +1156,13 @@ class GEngine:
                         Hessian of the head post-processing applied to `thead`); weight gradients accumulate
                         a (x) tangent-chain + tangent-activations (x) first-order chain, bias gradients the sums of
                         the tangent chain.  acts = tangent activations, chain = (draw1, draw_pm1, dp1) of the
-                        first-order walk."""
+                        first-order walk.
+        layers        : (data only, head_ready) the layers whose backward-data runs, top down - a walk that stops above Up1 or
+                        starts below the Head (multi-code inversion); unmasked_last: the last of them delivers the gradient
+                        w.r.t. its input activation itself (`_bwd_data`)."""
         c, lib = self.cfg, L.lib()
         B = self.ws_B if head_ready else ddepth.shape[0]
+        assert tuple(layers) == (4, 3, 2, 1) or (head_ready and acts is None)
         arch = ARCH_ID[c.arch]
         s_depth, s_conf = self.head_scales
         full = acts is not None
@@ -1157,11 +1175,12 @@ class GEngine:
             L.check(lib.dg_head_post_bwd(*self._head_saved(), L.ptr(ddepth), arch, c.tau, c.drop_const, B, self.HW, s_depth,
                                          s_conf, None if draw_pm is not None else L.ptr(draw),   # (pixel-major copy only)
                                          None, L.ptr(draw_pm), self.cp, None, L.stream_ptr()), "dg_head_post_bwd")
-        for i in (4, 3, 2, 1):
+        layers = tuple(layers)
+        for i in layers:
             if full:   # (not grouped)
                 self._wgrad(st, B, i, self.a[i - 1], (draw, draw_pm, dp))   # a (x) tangent chain
                 self._wgrad(st, B, i, acts[i - 1], chain)                   # tangent activations (x) first-order chain
-            self._bwd_data(st, B, i, (draw, draw_pm, dp), full)
+            self._bwd_data(st, B, i, (draw, draw_pm, dp), full, unmasked=unmasked_last and i == layers[-1])
         if full and second_of:
             self.proj_wgrad(st, dp[0], self.zT, B, True)        # z (x) tangent chain
             self.proj_wgrad(st, chain[2][0], self.vT, B, True)  # v (x) first-order chain
@@ -1237,9 +1256,20 @@ class GEngine:
         dg_inv_chamfer_grad: demo.py:508-515) -> the data-only backward-data chain -> grad_z into its fixed buffer -> dg_sphere_adam (Adam,
         renormalisation, the next step's perturbed latent into self.zT).  No parameter, gradient or counter of the model is
         touched: the step's only state is S's.  Returns the forward's output dict (views of engine workspaces)."""
+        if S.num_code > 1:
+            return self._inversion_step_multi(st, S)
+        out = self.forward(st, S.latent, S.gumbel, training=False, z_ready=True, want_sums=False)
+        self._inversion_loss_grad(S, out)
+        self._backward_chain(st, None, self.draw, self.draw_pm, self.dp, acts=None, chain=None, second_of=None,
+                             head_ready=True)
+        dzT = self.grad_z_T(st)
+        S.optimizer_launch(dzT, self.zT, L.dtype_code(self.dtype))
+        return out
+
+    def _inversion_loss_grad(self, S, out):
+        """the inversion loss of the forward pass `out` (S.B samples) and its head gradient where the chain reads it"""
         c, lib = self.cfg, L.lib()
         B, sp = S.B, L.stream_ptr()
-        out = self.forward(st, S.latent, S.gumbel, training=False, z_ready=True, want_sums=False)
         pm = self.draw_pm is not None   # bf16: the chain reads the pixel-major copy only
         C = S.chamfer
         nterm = len(S.terms) + (C is not None)
@@ -1268,10 +1298,42 @@ class GEngine:
                                             c.tau, c.drop_const, C.min_depth, C.max_depth, C.tol, B, HW, *self.head_scales, add,
                                             L.ptr(self.draw) if (add or not pm) else None, c.nheads, L.ptr(self.draw_pm), self.cp,
                                             L.ptr(S.parts), L.ptr(S.tickets), S.nchunk, L.ptr(S.loss), sp), "dg_inv_chamfer_grad")
+
+    def compose_geometry(self, layer):
+        """(P pixels, C channels) of a[layer], the feature map a multi-code inversion composes at"""
+        hc, wc = self.cfg.h0 << layer, self.cfg.w0 << layer
+        return hc * wc, self.chs[layer]
+
+    def _inversion_step_multi(self, st: ParamStore, S):
+        """One step of the multi-code inversion (mGANprior, demo.py:466-488,523-530) on this engine (batch B = S.B scans) and
+        S.lower (a GEngine of the same NetCfg and precision at batch B N: the N = S.num_code latents of every scan, row s N + n
+        code n of scan s).  Proj..Up_l of all B N latents in the lower engine -> dg_feat_compose into this engine's
+        a[l] (l = S.layer) -> Up_(l+1)..Head and the loss terms at batch B -> the data-only chain down to layer l+2, layer l+1's
+        backward-data UNMASKED (the composite is no leaky-relu output) -> dg_feat_compose_bwd: the lower engine's dp[l] and
+        d loss / d alpha -> the lower engine's chain l..1, grad_z -> dg_alpha_adam (reads the step index) -> dg_sphere_adam over the
+        B N rows (advances it)."""
+        lo, l, N, B = S.lower, S.layer, S.num_code, S.B
+        lib, sp, dt = L.lib(), L.stream_ptr(), L.dtype_code(self.dtype)
+        BN = B * N
+        P, C = self.compose_geometry(l)
+        st.refresh_shadows(self.dtype)
+        lo._proj_fwd(st, BN, lo.zT, lo.a[0])
+        for i in range(1, l + 1):
+            lo._fwd(st, BN, i, lo.a[i - 1], lo.a[i])
+        L.check(lib.dg_feat_compose(L.ptr(lo.a[l]), L.ptr(S.alpha), L.ptr(self.a[l]), dt, B, N, P, C, sp), "dg_feat_compose")
+        out = self._forward_from(st, B, l, S.gumbel, False, False)
+        self._inversion_loss_grad(S, out)
         self._backward_chain(st, None, self.draw, self.draw_pm, self.dp, acts=None, chain=None, second_of=None,
-                             head_ready=True)
-        dzT = self.grad_z_T(st)
-        S.optimizer_launch(dzT, self.zT, L.dtype_code(self.dtype))
+                             head_ready=True, layers=range(4, l, -1), unmasked_last=True)
+        L.check(lib.dg_feat_compose_bwd(L.ptr(self.dp[l]), L.ptr(lo.a[l]), L.ptr(S.alpha), L.ptr(lo.dp[l]), L.ptr(S.dalpha),
+                                        L.ptr(S.cparts), L.ptr(S.ctickets), S.cnchunk, dt, B, N, P, C, sp),
+                "dg_feat_compose_bwd")
+        if l > 0:
+            lo._backward_chain(st, None, lo.draw, lo.draw_pm, lo.dp, acts=None, chain=None, second_of=None,
+                               head_ready=True, layers=range(l, 0, -1))
+        dzT = lo.grad_z_T(st)
+        S.alpha_launch()
+        S.optimizer_launch(dzT, lo.zT, dt)
         return out
 
 

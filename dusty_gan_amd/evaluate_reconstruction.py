@@ -2,9 +2,13 @@
 
     python -m dusty_gan_amd.evaluate_reconstruction --model-path <ckpt.pth> --config-path <config.yaml>
         [--save-dir-path .] [--tol 0] [--batch-size 512] [--distance l1|l2|chamfer|l1+chamfer|...] [--num-step 1000]
+        [--num-code N --composition-layer NAME]
 
 Every test scan is reconstructed by optimising the latent of the EMA generator (dusty_gan_amd.inversion.invert), then
-scored per scan: Chamfer distance of the point clouds, depth accuracy / error, and the drop ratios."""
+scored per scan: Chamfer distance of the point clouds, depth accuracy / error, and the drop ratios.
+--num-code N > 1 (beyond the reference's command: the multi-code mode of its demo, mGANprior, demo.py:353-366) optimises N
+latents per scan, composed at --composition-layer (0..3, or a module name such as backbone.2: inversion.composition_layers);
+a pass then takes min(batch size, 4096 // N) scans.  The CSV is the same."""
 import argparse
 import csv
 import datetime
@@ -42,7 +46,30 @@ def parse_args(argv=None):
                              "which offers those two only - chamfer (the third loss of the reference's demo, demo.py:508-519) "
                              "and '+'-joined sums such as l1+chamfer")
     parser.add_argument("--num-step", type=int, default=1000)
-    return parser.parse_args(argv)
+    parser.add_argument("--num-code", type=int, default=1,
+                        help="latents per scan; above 1 (up to 64) the multi-code inversion of the reference's demo (mGANprior, "
+                             "demo.py:353-366), which needs --composition-layer")
+    parser.add_argument("--composition-layer", type=str, default=None,
+                        help="with --num-code > 1: the feature map the codes are composed at - 0..3 (the output of Proj, Up1, "
+                             "Up2, Up3) or its module name, e.g. backbone.2")
+    args = parser.parse_args(argv)
+    from .inversion import MAX_CODES, parse_composition_layer
+    if not 1 <= args.num_code <= MAX_CODES:
+        parser.error(f"--num-code: 1..{MAX_CODES}")
+    if (args.num_code > 1) != (args.composition_layer is not None):
+        parser.error("--num-code above 1 and --composition-layer go together")
+    if args.composition_layer is not None:
+        try:
+            parse_composition_layer(args.composition_layer)
+        except NotImplementedError as e:
+            parser.error(str(e))
+    return args
+
+
+def scans_per_pass(batch_size, num_code):
+    """scans of one invert call: the batch size, capped so that scans x codes stays within the lower batch's limit"""
+    from .inversion import MAX_LOWER
+    return batch_size if num_code == 1 else max(1, min(batch_size, MAX_LOWER // num_code))
 
 
 def flatten(t):
@@ -60,8 +87,9 @@ def evaluate_batch(G, lidar, arch, item, args):
     inv = lidar.invert_depth(depth)
     inv_ref = mask * inv + (1 - mask) * 0.0   # preprocess_reals (:63-69)
     names = split_distance(args.distance)
+    multi = dict(num_code=args.num_code, composition_layer=args.composition_layer) if args.num_code > 1 else {}
     res = invert(G, inv_ref, mask, num_step=args.num_step, distance=names[0] if len(names) == 1 else names,
-                 lidar=lidar if "chamfer" in names else None)
+                 lidar=lidar if "chamfer" in names else None, **multi)
     out = postprocess(res["out"], lidar, tol=args.tol)
     cd = compute_cd(flatten(xyz.float()), flatten(out["points"]))
     if "dusty" in arch:
@@ -95,7 +123,7 @@ def main(argv=None):
     cfg, G, lidar, device = utils.setup(args.model_path, args.config_path, ema=True, fix_noise=True)
     utils.set_requires_grad(G, False)
     dataset = define_dataset(cfg.dataset, phase="test")
-    loader = ScanLoader(dataset, args.batch_size, device, shuffle=False, drop_last=False, want_xyz=True,
+    loader = ScanLoader(dataset, scans_per_pass(args.batch_size, args.num_code), device, shuffle=False, drop_last=False, want_xyz=True,
                         num_workers=min(4, int(getattr(cfg, "num_workers", 4) or 1)))
     results = {k: [] for k in COLUMNS}
     for item in loader:

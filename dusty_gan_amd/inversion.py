@@ -5,7 +5,12 @@ Every step is forward (eval mode) -> dg_inv_loss_grad -> the generator's backwar
 dg_sphere_adam (GEngine.inversion_step).  The reference's demo adds a third loss, "chamfer" (demo.py:508-519): the symmetric
 Chamfer distance between the target's points and postprocess(out)["points"], the one term whose gradient reaches the
 measurability head - dg_inv_to_xyz -> two dg_chamfer_nn searches -> dg_inv_chamfer_scatter -> dg_inv_chamfer_grad.  The step index, the Adam moments and the latent live on the device, so one
-step is captured in a hipGraph and replayed; the scalars are read back once, after the loop."""
+step is captured in a hipGraph and replayed; the scalars are read back once, after the loop.
+
+num_code > 1 is the demo's multi-code mode (mGANprior, demo.py:353-366, 466-488, 523-530): N latents per scan run through the
+lower layers, their feature maps at one layer are blended per channel with learnable weights alpha (dg_feat_compose), and the
+blend runs through the rest of G as one sample; the latents are stepped by the spherical Adam, alpha by a plain Adam
+(dg_alpha_adam).  GEngine._inversion_step_multi, DESIGN.md 7b."""
 import gc
 import math
 
@@ -123,10 +128,86 @@ def _fixed_gumbel(G, B, H, W, seed, device, gumbel_noise):
     return {"pixel": noise.to(device).float().expand(B, 1, H, W).contiguous()}
 
 
+MAX_LOWER = 4096   # lower-batch samples (scans x codes) of one multi-code call
+MAX_CODES = 64     # the demo's slider ends there (demo.py:353-357)
+
+
+def composition_layers(G):
+    """{name: (C, h, w)} of the feature maps a multi-code inversion can compose at - the counterpart of the reference's
+    demo.get_feature_shapes, restricted to what is supported: the outputs of Proj, Up1, Up2 and Up3 under the reference's module
+    names ("0".."3" for the bare generator, "backbone.0".."backbone.3" for the DUSty wrappers) and, as aliases of the same
+    tensors, the last child of each block ("<blk>.1" for Proj, "<blk>.2" for Up)."""
+    bb = _backbone(G)
+    pre = "backbone." if bb is not G else ""
+    h0, w0 = bb.shape[0] >> 4, bb.shape[1] >> 4
+    out = {}
+    for l in range(4):
+        shape = (bb.chs[3 - l], h0 << l, w0 << l)
+        out[f"{pre}{l}"] = shape
+        out[f"{pre}{l}.{1 if l == 0 else 2}"] = shape
+    return out
+
+
+def parse_composition_layer(layer, wrapped=None):
+    """the index 0..3 (a[l]: the output of Proj, Up1, Up2, Up3) of `layer`: that integer, or one of composition_layers' names.
+    wrapped: True / False - the generator is a DUSty wrapper / the bare one, whose names carry / lack "backbone." (None: either
+    form).  NotImplementedError for any other module of the generator (a Pad's output, a conv's pre-activation, the Head's
+    inside); needs no device."""
+    accepted = ('0..3, or the module names "0".."3" ("backbone.0".."backbone.3" for the DUSty wrappers) and their last children '
+                '"<blk>.1" (Proj: blk 0) / "<blk>.2" (Up: blk 1..3)')
+    if isinstance(layer, bool) or layer is None:
+        raise ValueError(f"composition_layer: {accepted}")
+    if isinstance(layer, int):
+        if 0 <= layer <= 3:
+            return layer
+        raise NotImplementedError(f"composition_layer {layer}: accepted are {accepted}")
+    name = str(layer)
+    has = name.startswith("backbone.")
+    body = name[len("backbone."):] if has else name
+    parts = body.split(".")
+    ok = not (has and wrapped is False)   # (the bare generator has no "backbone." modules)
+    if ok and parts[0] in ("0", "1", "2", "3"):
+        l = int(parts[0])
+        if len(parts) == 1 or (len(parts) == 2 and parts[1] == ("1" if l == 0 else "2")):
+            return l
+    raise NotImplementedError(f"composition_layer {name!r}: accepted are {accepted}")
+
+
+def check_multi_code(num_code, composition_layer, alpha, alpha_lr, B=None, wrapped=None):
+    """the multi-code arguments of invert; returns the layer index, or None for num_code == 1.  Needs no device."""
+    if int(num_code) != num_code or num_code < 1 or num_code > MAX_CODES:
+        raise ValueError(f"num_code must be an integer in 1..{MAX_CODES}")
+    if num_code == 1:
+        if composition_layer is not None or alpha is not None or alpha_lr != 1e-3:
+            raise ValueError("composition_layer, alpha and alpha_lr belong to num_code > 1: leave them at their defaults")
+        return None
+    if composition_layer is None:
+        raise ValueError("num_code > 1 needs composition_layer (dusty_gan_amd.inversion.composition_layers lists them)")
+    layer = parse_composition_layer(composition_layer, wrapped)
+    if B is not None and B * num_code > MAX_LOWER:
+        raise ValueError(f"{B} scans x {num_code} codes = {B * num_code} lower samples: at most {MAX_LOWER} per call")
+    return layer
+
+
+def adam_table(lr, num_step, lr_rampup_ratio, lr_rampdown_ratio, noise=None):
+    """[num_step + 1][3] per-step scalars of torch's Adam under the LambdaLR schedule, formed the way torch forms them (LambdaLR's
+    lr a Python float, the step count a float32 tensor, so the bias corrections and the step size are float32 tensor
+    arithmetic): lr(k) / (1 - beta1^(k+1)), sqrt(1 - beta2^(k+1)), and noise(k) (0 without)"""
+    b1, b2 = 0.9, 0.999   # torch.optim.Adam's defaults
+    rows = []
+    for k in range(num_step + 1):
+        t = torch.tensor(float(k + 1))
+        step_lr = float(lr) * lr_schedule(k, num_step, lr_rampup_ratio, lr_rampdown_ratio)
+        rows.append(torch.stack([step_lr / (1 - b1 ** t), (1 - b2 ** t).sqrt(),
+                                 torch.tensor(noise(k) if noise is not None else 0.0)]))
+    return torch.stack(rows).float().contiguous()
+
+
 class InvState:
     """Everything one inversion's steps read and write, allocated before the loop."""
 
     NCHUNK = 16   # workgroups per sample of dg_inv_loss_grad
+    num_code = 1
 
     def __init__(self, inv_ref, mask_ref, latent, gumbel, *, num_step, distance, lr, perturb_latent, noise_ratio,
                  noise_sigma, lr_rampup_ratio, lr_rampdown_ratio, seed, lidar=None, tol=1e-8):
@@ -151,16 +232,37 @@ class InvState:
         self.noise_in = None
         self.gumbel = gumbel
         b1, b2 = 0.9, 0.999   # torch.optim.Adam's defaults
-        # the per-step scalars formed the way torch's Adam forms them: LambdaLR's lr a Python float, the step count a float32
-        # tensor, so the bias corrections and the step size are float32 tensor arithmetic
-        rows = []
-        for k in range(num_step + 1):
-            t = torch.tensor(float(k + 1))
-            step_lr = float(lr) * lr_schedule(k, num_step, lr_rampup_ratio, lr_rampdown_ratio)
-            rows.append(torch.stack([step_lr / (1 - b1 ** t), (1 - b2 ** t).sqrt(),
-                                     torch.tensor(noise_strength(k, num_step, noise_ratio, noise_sigma))]))
-        self.sched = torch.stack(rows).float().contiguous().to(dev)
+        self.sched = adam_table(lr, num_step, lr_rampup_ratio, lr_rampdown_ratio,
+                                lambda k: noise_strength(k, num_step, noise_ratio, noise_sigma)).to(dev)
         self.hp = (int(num_step), b1, b2, 1e-8, int(bool(perturb_latent)), int(seed) & (2**64 - 1), STREAM_PERTURB)
+        self._ramps = (lr_rampup_ratio, lr_rampdown_ratio)
+
+    def multi_code(self, lower, layer, num_code, alpha, alpha_lr):
+        """make this a multi-code state: self.latent holds the B N rows (row s N + n: code n of scan s), `lower` is the GEngine of
+        the lower layers at batch B N, `alpha` [B,N,C] the composition weights (stepped in place) with their Adam moments, the
+        gradient and the fixed-order sum's scratch of dg_feat_compose_bwd"""
+        dev = self.latent.device
+        self.lower, self.layer, self.num_code = lower, int(layer), int(num_code)
+        P, C = lower.compose_geometry(self.layer)
+        assert alpha.shape == (self.B, self.num_code, C) and self.latent.shape[0] == self.B * self.num_code
+        self.alpha = alpha
+        self.m_alpha = torch.zeros_like(alpha)
+        self.v_alpha = torch.zeros_like(alpha)
+        self.dalpha = torch.zeros_like(alpha)
+        # workgroups per (scan, code) of the backward composition: about 64 KB of the feature map each, at most 64
+        es = 2 if lower.dtype == torch.bfloat16 else 4
+        self.cnchunk = max(1, min(64, P, (P * C * es) // 65536))
+        rows = self.B * self.num_code
+        self.cparts = torch.zeros(rows * self.cnchunk * C, dtype=torch.float32, device=dev)
+        self.ctickets = torch.zeros(rows, dtype=torch.int32, device=dev)
+        self.sched_a = adam_table(alpha_lr, self.hp[0], *self._ramps).to(dev)
+
+    def alpha_launch(self):
+        """dg_alpha_adam on d loss / d alpha at the device step index, BEFORE the step's dg_sphere_adam advances it"""
+        ns, b1, b2, eps = self.hp[:4]
+        L.check(L.lib().dg_alpha_adam(L.ptr(self.dalpha), L.ptr(self.alpha), L.ptr(self.m_alpha), L.ptr(self.v_alpha),
+                                      L.ptr(self.step), L.ptr(self.sched_a), ns, b1, b2, eps, self.alpha.numel(),
+                                      L.stream_ptr()), "dg_alpha_adam")
 
     def optimizer_launch(self, dzT, zT, z_dtype, prime=False):
         """dg_sphere_adam on the gradient dz^T [nz][Bp] (prime: only the first step's generator input into zT)"""
@@ -174,7 +276,8 @@ class InvState:
 
 def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, perturb_latent=True, noise_ratio=0.75,
            noise_sigma=1.0, lr_rampup_ratio=0.05, lr_rampdown_ratio=0.25, seed=0, latent=None, graph=True,
-           noise_fn=None, gumbel_noise=None, on_step=None, lidar=None, tol=1e-8):
+           noise_fn=None, gumbel_noise=None, on_step=None, lidar=None, tol=1e-8, num_code=1, composition_layer=None,
+           alpha=None, alpha_lr=1e-3):
     """Reconstruct inv_ref [B,1,H,W] (inverse depth in [0,1]) under mask_ref [B,1,H,W] by optimising G's latent
     (evaluate_reconstruction.py:84-118).  G: what utils.setup returns (the bare 'none' generator or a DUSty1 / DUSty2
     wrapper), run in eval mode at its own precision; nothing of G is modified.
@@ -186,10 +289,26 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
     d loss / d latent [B,nz], latent [B,nz]) after every step (eager loop).
     graph: capture one step (after two eager ones) and replay it; results equal the eager loop's bit for bit.
     Returns {"latent", "out", "inv_gen", "loss"}: the reference's loop variables after the loop - the optimised latent, the
-    last step's generator output and tanh_to_sigmoid of its unmasked depth, and the last step's per-sample loss."""
+    last step's generator output and tanh_to_sigmoid of its unmasked depth, and the last step's per-sample loss.
+
+    num_code = N in 2..64: the demo's multi-code mode (mGANprior, demo.py:353-366, 466-488, 523-530).  N latents per scan run
+    through G up to composition_layer - 0..3 or one of composition_layers(G)'s names: the output of Proj, Up1, Up2 or Up3 - where
+    their feature maps are blended per channel with the weights alpha [B,N,C] (default 1/N, stepped by a plain Adam of
+    lr alpha_lr under the same LambdaLR schedule); the blend runs through the rest of G as one sample.  Then `latent` (given and
+    returned) and noise_fn(k) are [B,N,nz] - the default initial latent is the Philox draws of B N rows, row b N + n code n of
+    scan b, each normalised; the device-drawn perturbation keeps its per-row keying - the result carries "alpha" [B,N,C], and
+    on_step is called as on_step(k, loss [B], dlatent [B,N,nz], latent, dalpha [B,N,C], alpha).  "loss", "out" and "inv_gen" stay
+    per scan.  With num_code = 1 the three other arguments must stay at their defaults (ValueError).
+    The reference runs ONE scan (B = 1) under torch.manual_seed(0); B > 1 here is B independent such problems in one batch.
+    The lower layers run at batch B N, at most 4096 per call (ValueError): GEngine.alloc holds per lower sample the
+    feature maps a0..a3 and their gradients (2 x 1 966 080 elements at 64 x 1024 with 512 / 256 / 128 / 64 channels: 7.9 MB in
+    bf16, 15.7 MB in fp32) plus the head's buffers (gout, draw, mask, depth, in bf16 the pixel-major gradient and a3's mask bits:
+    2.4 - 3.0 MB with three heads) - roughly 10 MB in bf16 and 17 MB in fp32.  fp32x3 split storage is not built for it."""
     from .utils.lidar import unit_map
     check_distance(distance, lidar)
     bb = _backbone(G)
+    layer = check_multi_code(num_code, composition_layer, alpha, alpha_lr, inv_ref.shape[0], wrapped=bb is not G)
+    N = int(num_code)
     if not inv_ref.is_cuda:
         raise RuntimeError("invert runs on the GPU only (no CPU fallback)")
     if num_step < 1:
@@ -200,24 +319,45 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
     if hasattr(G, "_sync"):
         G._sync()   # the wrapper's tau / drop_const onto the backbone
     eng, st = bb.engine(), bb.store
+    if N > 1 and eng.x2_asked:
+        raise NotImplementedError("multi-code inversion is not built for the fp32x3 split storage (x2)")
     if latent is None:
-        latent = _draw_normal(int(seed) & (2**64 - 1), STREAM_LATENT, B * bb.in_ch, dev).view(B, bb.in_ch)
+        latent = _draw_normal(int(seed) & (2**64 - 1), STREAM_LATENT, B * N * bb.in_ch, dev).view(B * N, bb.in_ch)
         normalize_rows(latent)
-    latent = latent.detach().to(dev).float().clone().contiguous()
+    elif N > 1 and tuple(latent.shape) != (B, N, bb.in_ch):
+        raise ValueError(f"latent must be [B,N,nz] = {(B, N, bb.in_ch)} with num_code > 1")
+    latent = latent.detach().to(dev).float().clone().contiguous().view(B * N, bb.in_ch)
     S = InvState(inv_ref, mask_ref, latent, _fixed_gumbel(G, B, H, W, seed, dev, gumbel_noise), num_step=num_step,
                  distance=distance, lr=lr, perturb_latent=perturb_latent, noise_ratio=noise_ratio, noise_sigma=noise_sigma,
                  lr_rampup_ratio=lr_rampup_ratio, lr_rampdown_ratio=lr_rampdown_ratio, seed=seed,
                  lidar=lidar, tol=tol)
     # every buffer of the loop exists before it, allocated on the caller's stream
     eng.alloc(B, dev)
-    eng.grad_z_buffers()
+    low = eng   # the engine the latents enter: the generator's own, or the lower one of a multi-code inversion
+    if N > 1:
+        low = E.GEngine(eng.cfg, eng.dtype, x3=eng.ops.x3)
+        low.alloc(B * N, dev)
+        C = low.chs[layer]
+        if alpha is None:
+            alpha = torch.full((B, N, C), 1.0 / N)
+        elif tuple(alpha.shape) != (B, N, C):
+            raise ValueError(f"alpha must be [B,N,C] = {(B, N, C)}")
+        S.multi_code(low, layer, N, alpha.detach().to(dev).float().clone().contiguous(), alpha_lr)
+    low.grad_z_buffers()
     zdt = L.dtype_code(eng.dtype)
     zero = torch.zeros_like(latent)
 
     def injected(k):
         if not perturb_latent:
             return zero
-        return noise_fn(k).to(dev).float().contiguous() if k < num_step else zero
+        return noise_fn(k).to(dev).float().contiguous().view(B * N, -1) if k < num_step else zero
+
+    def report(k):
+        dz = low._dzw[:, :B * N].t()
+        if N == 1:
+            return on_step(k, S.loss.clone(), dz.clone(), S.latent.clone())
+        return on_step(k, S.loss.clone(), dz.reshape(B, N, -1).clone(), S.latent.view(B, N, -1).clone(), S.dalpha.clone(),
+                       S.alpha.clone())
 
     if noise_fn is not None or on_step is not None:
         graph = False
@@ -232,7 +372,7 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
         with torch.cuda.stream(s):
             if noise_fn is not None:
                 S.noise_in = injected(0)
-            S.optimizer_launch(None, eng.zT, zdt, prime=True)
+            S.optimizer_launch(None, low.zT, zdt, prime=True)
             out = None
             n_eager = min(num_step, 2) if graph else num_step
             for k in range(n_eager):
@@ -240,7 +380,7 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
                     S.noise_in = injected(k + 1)
                 out = eng.inversion_step(st, S)
                 if on_step is not None:
-                    on_step(k, S.loss.clone(), eng._dzw[:, :B].t().clone(), S.latent.clone())
+                    report(k)
             if num_step > n_eager:
                 g = torch.cuda.CUDAGraph()
                 was = gc.isenabled()
@@ -260,4 +400,8 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
         del g
     res_out = {key: v.clone() for key, v in out.items()}
     depth = eng.gout[:, 0:1]
-    return {"latent": S.latent.clone(), "out": res_out, "inv_gen": unit_map(depth, 0), "loss": S.loss.clone()}
+    res = {"latent": S.latent.clone(), "out": res_out, "inv_gen": unit_map(depth, 0), "loss": S.loss.clone()}
+    if N > 1:
+        res["latent"] = res["latent"].view(B, N, -1)
+        res["alpha"] = S.alpha.clone()
+    return res

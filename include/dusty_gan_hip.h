@@ -766,6 +766,27 @@ int dg_sphere_adam(const float* grad, long g_sb, long g_sk, float* latent, float
 int dg_depth_metrics(const float* inv_ref, const float* inv_gen, const float* mask, const float* keep, int kc,
                      int keep_is_depth, float tol, int B, long HW, float min_depth, float max_depth, float* out, void* stream);
 
+/* ---- Multi-code GAN inversion (mGANprior)  demo.py:353-366, 466-488, 523-530 ------------------------------------------------
+ * N latents per scan run through the generator's lower layers; their feature maps at one layer - pixel-major
+ * [sample][P pixels][C channels] in `dtype` (DG_F32 / DG_BF16), code n of scan s = lower-batch row s N + n - are blended per
+ * channel with alpha [B,N,C] fp32 and the blend runs on as one sample.
+ * dg_feat_compose: out[s,p,c] = sum_n alpha[s,n,c] a[s N + n,p,c], accumulated in fp32 in code order, rounded once on the store.
+ * dg_feat_compose_bwd: from g [B,P,C] = d loss / d out (NO leaky-relu factor in it):
+ *   dpre[s N + n,p,c] = g[s,p,c] alpha[s,n,c] f(a[s N + n,p,c]),  f(x) = sqrt(2) for x > 0, else 0.2 sqrt(2): the factor the conv
+ *   kernels' DG_EPI_MASK epilogue takes from `aux` - the gradient w.r.t. the pre-activations of the lower rows;
+ *   dalpha[s,n,c] = sum_p g[s,p,c] a[s N + n,p,c], fp32, in a fixed order: nchunk (1..P) workgroups per (s, n) leave partial sums in
+ *   parts [B N][nchunk][C] and draw tickets [B N] (both zero on entry, left zero; not read when nchunk = 1); the last one adds the
+ *   partials in chunk order.  Two launches on the same data give the same bits.
+ * Any C, P; vector accesses where C % 4 == 0 (bf16: C % 8 == 0 for the widest) and the pointers are aligned.  P C < 2^31.
+ * dg_alpha_adam: torch.optim.Adam (defaults) on alpha [n] with moments m, v at step index k = *step_dev, which it only READS:
+ * launch it before the dg_sphere_adam of the same step, whose last workgroup advances the index.  sched [num_step + 1][3] as
+ * dg_sphere_adam's (columns 0, 1: lr(k) / (1 - beta1^(k+1)), sqrt(1 - beta2^(k+1)); column 2 unused), row num_step beyond it. */
+int dg_feat_compose(const void* a, const float* alpha, void* out, int dtype, int B, int N, int P, int C, void* stream);
+int dg_feat_compose_bwd(const void* g, const void* a, const float* alpha, void* dpre, float* dalpha, float* parts,
+                        unsigned* tickets, int nchunk, int dtype, int B, int N, int P, int C, void* stream);
+int dg_alpha_adam(const float* grad, float* alpha, float* m, float* v, const unsigned long long* step_dev, const float* sched,
+                  int num_step, float beta1, float beta2, float eps, long n, void* stream);
+
 const char* dg_version(void);
 
 #ifdef __cplusplus

@@ -4,6 +4,9 @@ different length: the difference per extra step is the replayed step's time (war
     python scripts/bench_inversion.py [--batches 32 512] [--dtypes bf16 fp32] [--steps 200] [--distance l1 chamfer l1+chamfer]
 --nn N: also time dg_chamfer_nn against dg_chamfer_paired (the index-free floor) on B = 32 pairs of N-point clouds
 (--batches or --dtypes with no value: skip the step benchmark and time the search only).
+--num-code N [N ...] with --composition-layer L [L ...]: the multi-code inversion (mGANprior) at every (N, L); N = 1 is the
+single-code step.  --compose: time dg_feat_compose / dg_feat_compose_bwd alone at the chosen (B, N, L, dtype) and report their
+achieved bytes per second (operands streamed once: the algorithmic traffic).
 Prints one JSON line per configuration."""
 import argparse
 import json
@@ -68,6 +71,49 @@ def bench_nn(n, B=32, reps=10, warm=3):
     print(json.dumps({"what": "nearest-neighbour search, ms", "B": B, "n": n, **res}), flush=True)
 
 
+def bench_compose(B, N, layer, dt, reps=20, warm=5):
+    """the two composition kernels on full-width feature maps of layer `layer` (64x1024, channels 512 / 256 / 128 / 64):
+    median event time of one launch and the algorithmic bytes (forward: N maps read, one written; backward: g once per code - it
+    is re-read from the caches, counted once per scan here - N maps read, N written) per second"""
+    from dusty_gan_amd import _lib as L
+    lib = L.lib()
+    dtype = {"bf16": torch.bfloat16, "fp32": torch.float32}[dt]
+    es = 2 if dt == "bf16" else 4
+    P, C = (4 * 64) << (2 * layer), 512 >> layer
+    a = torch.randn(B * N, P, C, device="cuda").to(dtype)
+    g = torch.randn(B, P, C, device="cuda").to(dtype)
+    alpha = torch.full((B, N, C), 1.0 / N, device="cuda")
+    out, dpre, dalpha = torch.empty_like(g), torch.empty_like(a), torch.empty_like(alpha)
+    nchunk = max(1, min(64, P, (P * C * es) // 65536))
+    parts = torch.zeros(B * N * nchunk * C, device="cuda")
+    tickets = torch.zeros(B * N, dtype=torch.int32, device="cuda")
+    code = L.dtype_code(dtype)
+
+    def fwd():
+        L.check(lib.dg_feat_compose(L.ptr(a), L.ptr(alpha), L.ptr(out), code, B, N, P, C, L.stream_ptr()), "dg_feat_compose")
+
+    def bwd():
+        L.check(lib.dg_feat_compose_bwd(L.ptr(g), L.ptr(a), L.ptr(alpha), L.ptr(dpre), L.ptr(dalpha), L.ptr(parts), L.ptr(tickets),
+                                        nchunk, code, B, N, P, C, L.stream_ptr()), "dg_feat_compose_bwd")
+
+    nbytes = {"dg_feat_compose": (B * N + B) * P * C * es, "dg_feat_compose_bwd": (2 * B * N + B) * P * C * es}
+    for name, fn in (("dg_feat_compose", fwd), ("dg_feat_compose_bwd", bwd)):
+        ts = []
+        for r in range(warm + reps):
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if r >= warm:
+                ts.append(e0.elapsed_time(e1))
+        med = sorted(ts)[len(ts) // 2]
+        print(json.dumps({"what": name, "dtype": dt, "B": B, "N": N, "layer": layer, "P": P, "C": C, "ms": round(med, 4),
+                          "min_ms": round(min(ts), 4), "bytes": nbytes[name], "TB_per_s": round(nbytes[name] / (med * 1e-3) / 1e12, 3),
+                          "sclk_mhz": gpu_clock()}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="*", default=[32, 512], help="no value: skip the step benchmark")
@@ -76,7 +122,18 @@ def main():
     ap.add_argument("--short", type=int, default=20)
     ap.add_argument("--distance", nargs="+", default=["l1"], help="'+'-joined terms out of l1, l2, chamfer; one run each")
     ap.add_argument("--nn", type=int, default=0)
+    ap.add_argument("--num-code", type=int, nargs="+", default=[1], help="latents per scan; above 1: multi-code inversion")
+    ap.add_argument("--composition-layer", type=int, nargs="+", default=[], help="0..3, with --num-code above 1")
+    ap.add_argument("--compose", action="store_true", help="time the two composition kernels alone instead of the step")
     a = ap.parse_args()
+    combos = [(n, l) for n in a.num_code for l in (a.composition_layer if n > 1 else [None])]
+    if a.compose:
+        for dt in a.dtypes:
+            for B in a.batches:
+                for n, l in combos:
+                    if n > 1:
+                        bench_compose(B, n, l, dt)
+        return
     if a.nn:
         bench_nn(a.nn)
     from dusty_gan_amd.inversion import invert
@@ -94,10 +151,12 @@ def main():
         for B in a.batches:
             ref = torch.rand(B, 1, 64, 1024, device="cuda")
             mask = (torch.rand(B, 1, 64, 1024, device="cuda") > 0.1).float()
-            for dist in a.distance:
+            for dist, (ncode, layer) in ((d, c) for d in a.distance for c in combos):
                 names = tuple(dist.split("+"))
                 kw = dict(gumbel_noise=gum, distance=names[0] if len(names) == 1 else names,
                           lidar=lidar if "chamfer" in names else None)
+                if ncode > 1:
+                    kw.update(num_code=ncode, composition_layer=layer)
                 invert(G, ref, mask, num_step=a.short, **kw)   # warm-up: shadows, workspaces, clocks
                 ms = {}
                 for n in (a.short, a.steps):
@@ -110,7 +169,7 @@ def main():
                     ms[n] = e0.elapsed_time(e1)
                 step_ms = (ms[a.steps] - ms[a.short]) / (a.steps - a.short)
                 print(json.dumps({"what": "inversion step (graph replay)", "arch": "dusty2", "shape": [64, 1024], "nz": 512,
-                                  "dtype": dt, "B": B, "distance": dist, "sclk_mhz": gpu_clock(), "ms_per_step": round(step_ms, 4),
+                                  "dtype": dt, "B": B, "distance": dist, "num_code": ncode, "composition_layer": layer, "sclk_mhz": gpu_clock(), "ms_per_step": round(step_ms, 4),
                                   "s_per_1000_steps": round(step_ms, 4),
                                   "ms_total": {str(k): round(v, 2) for k, v in ms.items()}}), flush=True)
             del ref, mask
