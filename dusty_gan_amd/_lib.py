@@ -237,6 +237,10 @@ PROTOTYPES = {
     "dg_feat_compose": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "dg_feat_compose_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "dg_alpha_adam": [_P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _L, _P],
+    "dg_corrupt_mask": [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P],
+    "dg_additive_noise": [_P, _P, _F, _L, _P, _P],
+    "dg_median3x3": [_P, _I, _I, _I, _P, _P],
+    "dg_hole_fill": [_P, _P, _I, _I, _I, _F, _P, _P, _P],
 }
 
 _lib = None

@@ -2,13 +2,16 @@
 
     python -m dusty_gan_amd.evaluate_reconstruction --model-path <ckpt.pth> --config-path <config.yaml>
         [--save-dir-path .] [--tol 0] [--batch-size 512] [--distance l1|l2|chamfer|l1+chamfer|...] [--num-step 1000]
-        [--num-code N --composition-layer NAME]
+        [--num-code N --composition-layer NAME] [--corruption NAME [--corruption-seed 0]]
 
 Every test scan is reconstructed by optimising the latent of the EMA generator (dusty_gan_amd.inversion.invert), then
 scored per scan: Chamfer distance of the point clouds, depth accuracy / error, and the drop ratios.
 --num-code N > 1 (beyond the reference's command: the multi-code mode of its demo, mGANprior, demo.py:353-366) optimises N
 latents per scan, composed at --composition-layer (0..3, or a module name such as backbone.2: inversion.composition_layers);
-a pass then takes min(batch size, 4096 // N) scans.  The CSV is the same."""
+a pass then takes min(batch size, 4096 // N) scans.  The CSV is the same.
+--corruption NAME (beyond the reference's command: the restoration experiment of its demo, demo.py:126-137, 385-397) degrades
+every target - "additive noise", "low resolution", "dropout" or "closing" (dusty_gan_amd.corruption) - and inverts against the
+degraded scan; every column is still scored against the FULL scan.  Same columns, same file name."""
 import argparse
 import csv
 import datetime
@@ -34,6 +37,14 @@ def _distance_arg(text):
     return text
 
 
+def _corruption_arg(text):
+    from .corruption import canonical
+    try:
+        return canonical(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
 def parse_args(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument("--model-path", type=str, required=True)
@@ -52,6 +63,12 @@ def parse_args(argv=None):
     parser.add_argument("--composition-layer", type=str, default=None,
                         help="with --num-code > 1: the feature map the codes are composed at - 0..3 (the output of Proj, Up1, "
                              "Up2, Up3) or its module name, e.g. backbone.2")
+    parser.add_argument("--corruption", type=_corruption_arg, default=None,
+                        help="corrupt every target before the inversion (the restoration experiment of the reference's demo, "
+                             "demo.py:126-137): 'additive noise', 'low resolution', 'dropout' or 'closing' (additive_noise and "
+                             "low_resolution are accepted too); the scores are against the full scan")
+    parser.add_argument("--corruption-seed", type=int, default=0,
+                        help="Philox seed of the corruption's draws (scan i of the dataset draws the same numbers in any batch)")
     args = parser.parse_args(argv)
     from .inversion import MAX_CODES, parse_composition_layer
     if not 1 <= args.num_code <= MAX_CODES:
@@ -77,8 +94,10 @@ def flatten(t):
     return t.flatten(2).permute(0, 2, 1).contiguous()
 
 
-def evaluate_batch(G, lidar, arch, item, args):
-    """one batch of the reference's loop body (:80-152) -> {column: list}"""
+def evaluate_batch(G, lidar, arch, item, args, first_index=0):
+    """one batch of the reference's loop body (:80-152) -> {column: list}.  With args.corruption the latent is optimised
+    against the corrupted (depth, mask) - the Chamfer term's reference points included - and every column is scored against
+    the full scan (demo.py:385-397); first_index: the dataset index of the batch's first scan (keys the corruption's draws)"""
     from .inversion import invert
     from .utils.lidar import postprocess
     from .utils.metrics.depth import depth_metrics
@@ -86,9 +105,16 @@ def evaluate_batch(G, lidar, arch, item, args):
     xyz, depth, mask = item["xyz"], item["depth"], item["mask"].float()
     inv = lidar.invert_depth(depth)
     inv_ref = mask * inv + (1 - mask) * 0.0   # preprocess_reals (:63-69)
+    tgt_ref, tgt_mask = inv_ref, mask
+    corruption = getattr(args, "corruption", None)
+    if corruption is not None:
+        from .corruption import apply_corruption
+        dep_c, tgt_mask = apply_corruption(depth, mask, corruption, seed=getattr(args, "corruption_seed", 0), first_index=first_index)
+        inv_c = lidar.invert_depth(dep_c)
+        tgt_ref = tgt_mask * inv_c + (1 - tgt_mask) * 0.0   # demo.py:396-397
     names = split_distance(args.distance)
     multi = dict(num_code=args.num_code, composition_layer=args.composition_layer) if args.num_code > 1 else {}
-    res = invert(G, inv_ref, mask, num_step=args.num_step, distance=names[0] if len(names) == 1 else names,
+    res = invert(G, tgt_ref, tgt_mask, num_step=args.num_step, distance=names[0] if len(names) == 1 else names,
                  lidar=lidar if "chamfer" in names else None, **multi)
     out = postprocess(res["out"], lidar, tol=args.tol)
     cd = compute_cd(flatten(xyz.float()), flatten(out["points"]))
@@ -127,7 +153,7 @@ def main(argv=None):
                         num_workers=min(4, int(getattr(cfg, "num_workers", 4) or 1)))
     results = {k: [] for k in COLUMNS}
     for item in loader:
-        for k, v in evaluate_batch(G, lidar, str(cfg.model.gen.arch), item, args).items():
+        for k, v in evaluate_batch(G, lidar, str(cfg.model.gen.arch), item, args, first_index=len(results["cd"])).items():
             results[k] += v
     os.makedirs(args.save_dir_path, exist_ok=True)
     save_path = osp.join(args.save_dir_path, f"{datetime.datetime.now().isoformat()}.csv")

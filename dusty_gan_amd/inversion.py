@@ -19,7 +19,8 @@ import torch
 from . import _lib as L
 from . import engine as E
 
-# Philox stream ids of the inversion's own draws (the model's and the trainer's generators use 0-9)
+# Philox stream ids of the inversion's own draws (the model's and the trainer's generators use 0-9); 14 is the target
+# corruptions' (corruption.STREAM_CORRUPT)
 STREAM_LATENT, STREAM_PERTURB, STREAM_GUMBEL = 11, 12, 13
 
 

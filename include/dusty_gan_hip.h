@@ -787,6 +787,31 @@ int dg_feat_compose_bwd(const void* g, const void* a, const float* alpha, void* 
 int dg_alpha_adam(const float* grad, float* alpha, float* m, float* v, const unsigned long long* step_dev, const float* sched,
                   int num_step, float beta1, float beta2, float eps, long n, void* stream);
 
+/* ---- Target corruptions of the restoration experiment  demo.py:71-137, 385-397 ------------------------------------------------
+ * The demo corrupts the scan it inverts against and compares the inversion with the full scan.  Images are fp32 [B,1,H,W],
+ * contiguous.
+ * dg_corrupt_mask: out = mask row_keep[h] col_keep[w] (u < rate); row_keep [H], col_keep [W], u [B,H,W] are each optional
+ *   (NULL: factor 1; `rate` is read only with u).  out == mask is allowed.  One body for dropout_noise (demo.py:71-74: a pixel
+ *   is KEPT where u < rate), sparse_hlines / sparse_vlines (:77-88: rows / columns ::int(1 / rate)), random_lines (:91-95),
+ *   corrupt_half (:98-101) and corrupt_quarter (:104-108); the caller builds the keep vectors.
+ * dg_additive_noise: out = x + (noise strength), the product rounded to fp32 before the sum, never one FMA (:111-113:
+ *   `randn_like(depth) * strength`, then `depth + noise`).  out == x is allowed.
+ * dg_median3x3: kornia.filters.median_blur(x, (3, 3)) as closing calls it (:117): the 5th smallest of the nine taps, taps
+ *   outside the image read as ZERO (not circular, not replicated).  out != x.
+ * dg_hole_fill: the `while` loop of closing (:118-123) on x in place, per sample.  A sweep sets every pixel with x <= thresh
+ *   (the reference's 1e-8) to the maximum of its 3x3 neighbourhood - centre included, taps outside the image ignored
+ *   (F.max_pool2d pads with -inf) - and every pixel of sweep k reads the state after sweep k - 1 (Jacobi).  A sample stops when
+ *   no hole is left, when a sweep filled nothing (no pixel of the sample exceeds thresh: the reference's loop never ends
+ *   there; that sweep is discarded) and in any case after max(H, W) - 1 sweeps (at least one), within which a valid pixel
+ *   reaches every other.  sweeps [B]: the sweeps that filled something; left [B]: the holes remaining (0, or H W for an
+ *   all-hole sample, which comes back unchanged).  tmp: B H W floats of scratch (the second buffer of the sweeps), != x.  One
+ *   workgroup per sample, no host read-back between sweeps.  H W <= 2^18, else DG_EUNSUPPORTED. */
+int dg_corrupt_mask(const float* mask, const float* row_keep, const float* col_keep, const float* u, float rate, int B, int H,
+                    int W, float* out, void* stream);
+int dg_additive_noise(const float* x, const float* noise, float strength, long n, float* out, void* stream);
+int dg_median3x3(const float* x, int B, int H, int W, float* out, void* stream);
+int dg_hole_fill(float* x, float* tmp, int B, int H, int W, float thresh, int* sweeps, int* left, void* stream);
+
 const char* dg_version(void);
 
 #ifdef __cplusplus
