@@ -10,7 +10,7 @@
 // dalpha's sum over pixels has a fixed order: a thread walks its pixels in order, the rows of a workgroup are added in row order
 // (LDS), the workgroups of one (s, n) in chunk order by the one that draws the last ticket (common.h) - run to run, and a
 // replayed graph against the eager loop, the bits are the same.
-#include "common.h"
+#include "adam.h"
 
 namespace {
 
@@ -148,12 +148,7 @@ __global__ __launch_bounds__(FC_THREADS) void alpha_adam_kernel(const float* __r
   const int k = (int)*(volatile const unsigned long long*)step;
   const float* sk = sched + 3 * min(k, num_step);
   const float step_size = sk[0], bc2s = sk[1];
-  const float gr = grad[i];
-  const float mi = m[i] + (1.f - beta1) * (gr - m[i]);          // exp_avg.lerp_(grad, 1 - beta1)
-  const float vi = v[i] * beta2 + (1.f - beta2) * gr * gr;      // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-  m[i] = mi;
-  v[i] = vi;
-  x[i] = x[i] - step_size * (mi / (sqrtf(vi) / bc2s + eps));
+  adam_torch_apply(grad[i], m[i], v[i], x[i], step_size, bc2s, 1.f - beta1, beta2, 1.f - beta2, eps);
 }
 
 // the widest vector the channel count and the pointers allow: 16 bytes, 8 bytes (bf16), else single elements

@@ -15,6 +15,7 @@
 //                            inv_to_xyz and the EVAL-mode head post-processing, the head gradient.
 // Every per-sample sum is a fixed-order reduction (block sums, then the partials of a sample in chunk order): an inversion
 // is bit-reproducible run to run.
+#include "adam.h"
 #include "head_post.h"
 
 namespace {
@@ -264,11 +265,7 @@ __global__ __launch_bounds__(SA_THREADS) void sphere_adam_kernel(SphereArgs a) {
       const int j = tid + e * SA_THREADS;
       if (j >= a.nz) break;
       const float g = a.grad[(long)b * a.g_sb + (long)j * a.g_sk];
-      const float mj = m[j] + w1 * (g - m[j]);          // exp_avg.lerp_(grad, 1 - beta1)
-      const float vj = v[j] * a.beta2 + w2 * g * g;     // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-      m[j] = mj;
-      v[j] = vj;
-      x[e] = x[e] - step_size * (mj / (sqrtf(vj) / bc2s + a.eps));
+      adam_torch_apply(g, m[j], v[j], x[e], step_size, bc2s, w1, a.beta2, w2, a.eps);
       ss += x[e] * x[e];
     }
     // SphericalOptimizer (utils/__init__.py:229-234): row / sqrt(mean(row^2) + 1e-9), one fixed-order block sum

@@ -1,15 +1,13 @@
 // Optimizer / parameter-state kernels: fused Adam (+EMA, + low-precision shadow write), the casts and the transposed weight
 // shadow used by the MFMA forward kernels (whose last launch of a step also advances the step's counters: step_inputs.h).
+#include "adam.h"
 #include "step_inputs.h"
 #include "thin_up_frag.h"
 #include <cstdlib>
 typedef __attribute__((ext_vector_type(4))) float f32x4_opt;
 
-// torch.optim.Adam (no weight decay / amsgrad) as configured at trainers/dcgan_amp.py:116-125, fused with
-// ema_inplace (:30-35) and with the T-typed shadow copy the conv kernels read.  All buffers are flat.
-//   g <- grad * gscale (gscale = 1/world_size after a SUM all-reduce)
-//   m <- b1 m + (1-b1) g ; v <- b2 v + (1-b2) g^2 ; p <- p - (lr/bc1) m / (sqrt(v)/sqrt(bc2) + eps)
-//   ema <- d ema + (1-d) p   (only where ema != null)
+// Adam + EMA (adam.h) fused with the T-typed shadow copy the conv kernels read.  All buffers are flat.
+//   g <- grad * gscale (gscale = 1/world_size after a SUM all-reduce) ; m <- b1 m + (1-b1) g ; ema only where ema != null
 template <typename T>
 __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ grad,
                                                        float* __restrict__ m, float* __restrict__ v,
@@ -18,10 +16,11 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, co
                                                        float b2, float eps, float ema_decay,
                                                        const unsigned long long* __restrict__ stepp, float lr) {
   if (stepp) {  // step count in device memory (graph replay): bias corrections computed here
-    const float t = (float)(*stepp + 1ull);
-    lr_bc1 = lr / (1.f - (b1 > 0.f ? powf(b1, t) : 0.f));
-    inv_sqrt_bc2 = rsqrtf(1.f - powf(b2, t));
+    const float t = adam_step_t(stepp);
+    lr_bc1 = adam_lr_bc1(lr, b1, t);
+    inv_sqrt_bc2 = adam_inv_sqrt_bc2(b2, t);
   }
+  const AdamCoef c{lr_bc1, inv_sqrt_bc2, b2, eps, ema_decay};
   // 16 bytes per lane per stream, grid-stride.  m == nullptr (beta1 == 0: exp_avg IS the scaled gradient) drops two
   // of the nine fp32 streams; the exported optimizer state rebuilds exp_avg from the gradient buffer.
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -35,28 +34,14 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, co
     float ev[4] = {e4.x, e4.y, e4.z, e4.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float mi = b1 * mv[k] + (1.f - b1) * gg[k];
-      const float vi = b2 * vv[k] + (1.f - b2) * gg[k] * gg[k];
-      mv[k] = mi;
-      vv[k] = vi;
-      pv[k] = pv[k] - lr_bc1 * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-      ev[k] = ema_decay * ev[k] + (1.f - ema_decay) * pv[k];
+      mv[k] = b1 * mv[k] + (1.f - b1) * gg[k];
+      adam_ema_apply(mv[k], gg[k], vv[k], pv[k], ev[k], c);
     }
     ((float4*)p)[i] = make_float4(pv[0], pv[1], pv[2], pv[3]);
     ((float4*)v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
     if (m) ((float4*)m)[i] = make_float4(mv[0], mv[1], mv[2], mv[3]);
     if (ema) ((float4*)ema)[i] = make_float4(ev[0], ev[1], ev[2], ev[3]);
-    if (shadow) {  // one 8- or 16-byte store per lane (four 2-byte stores were a quarter of this kernel's store instructions)
-      if constexpr (sizeof(T) == 2) {
-        const T h[4] = {(T)pv[0], (T)pv[1], (T)pv[2], (T)pv[3]};
-        uint2 pk;
-        pk.x = (unsigned)__builtin_bit_cast(unsigned short, h[0]) | ((unsigned)__builtin_bit_cast(unsigned short, h[1]) << 16);
-        pk.y = (unsigned)__builtin_bit_cast(unsigned short, h[2]) | ((unsigned)__builtin_bit_cast(unsigned short, h[3]) << 16);
-        ((uint2*)shadow)[i] = pk;
-      } else {
-        ((float4*)shadow)[i] = make_float4(pv[0], pv[1], pv[2], pv[3]);
-      }
-    }
+    if (shadow) shadow_store4(shadow + 4 * i, 0, pv);
   }
 }
 
@@ -91,8 +76,7 @@ __global__ __launch_bounds__(256) void adam_fused_kernel(float* __restrict__ p, 
     if ((int)blockIdx.x >= segs.s[i].first_block) k = i;
   const OptSeg& sg = segs.s[k];
   const int blk = (int)blockIdx.x - sg.first_block;
-  const float t = (float)(*stepp + 1ull);
-  const float inv_sqrt_bc2 = rsqrtf(1.f - powf(b2, t));
+  const AdamCoef c{lr, adam_inv_sqrt_bc2(b2, adam_step_t(stepp)), b2, eps, ema_decay};
   // Adam (beta1 = 0) + EMA + every store of four consecutive parameters at flat float4 index i4, given their gradient sum.
   // The parameter-state loads are issued by `state_load` BEFORE the partial rows are summed (they do not depend on the sum:
   // more bytes in flight, a shorter dependent chain per workgroup).
@@ -112,26 +96,11 @@ __global__ __launch_bounds__(256) void adam_fused_kernel(float* __restrict__ p, 
     float vv[4] = {v4.x, v4.y, v4.z, v4.w}, ev[4] = {e4.x, e4.y, e4.z, e4.w};
     pn[0] = p4.x; pn[1] = p4.y; pn[2] = p4.z; pn[3] = p4.w;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float vi = b2 * vv[q] + (1.f - b2) * gg[q] * gg[q];
-      vv[q] = vi;
-      pn[q] = pn[q] - lr * (gg[q] / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-      ev[q] = ema_decay * ev[q] + (1.f - ema_decay) * pn[q];
-    }
+    for (int q = 0; q < 4; ++q) adam_ema_apply(gg[q], gg[q], vv[q], pn[q], ev[q], c);
     ((float4*)p)[i4] = make_float4(pn[0], pn[1], pn[2], pn[3]);
     ((float4*)v)[i4] = make_float4(vv[0], vv[1], vv[2], vv[3]);
     if (ema) ((float4*)ema)[i4] = make_float4(ev[0], ev[1], ev[2], ev[3]);
-    if (shadow) {
-      if constexpr (sizeof(ST) == 2) {
-        const ST h[4] = {(ST)pn[0], (ST)pn[1], (ST)pn[2], (ST)pn[3]};
-        uint2 pk;
-        pk.x = (unsigned)__builtin_bit_cast(unsigned short, h[0]) | ((unsigned)__builtin_bit_cast(unsigned short, h[1]) << 16);
-        pk.y = (unsigned)__builtin_bit_cast(unsigned short, h[2]) | ((unsigned)__builtin_bit_cast(unsigned short, h[3]) << 16);
-        ((uint2*)shadow)[i4] = pk;
-      } else {
-        ((float4*)shadow)[i4] = make_float4(pn[0], pn[1], pn[2], pn[3]);
-      }
-    }
+    if (shadow) shadow_store4(shadow, 4 * i4, pn);
   };
   // the sum of a piece's partial rows for the float4 at index e4 of the SEGMENT, rows sp0, sp0 + step, ... (8 loads in flight)
   auto part_sum = [&](long e4, int sp0, int step) {
@@ -231,15 +200,7 @@ __global__ __launch_bounds__(256) void adam_fused_kernel(float* __restrict__ p, 
     for (int r0 = 0; r0 < R; r0 += 4) {
       const float o[4] = {tl[(r0 + 0) * (CW + 1) + c], tl[(r0 + 1) * (CW + 1) + c], tl[(r0 + 2) * (CW + 1) + c],
                           tl[(r0 + 3) * (CW + 1) + c]};
-      if constexpr (sizeof(ST) == 2) {
-        const ST h[4] = {(ST)o[0], (ST)o[1], (ST)o[2], (ST)o[3]};
-        uint2 pk;
-        pk.x = (unsigned)__builtin_bit_cast(unsigned short, h[0]) | ((unsigned)__builtin_bit_cast(unsigned short, h[1]) << 16);
-        pk.y = (unsigned)__builtin_bit_cast(unsigned short, h[2]) | ((unsigned)__builtin_bit_cast(unsigned short, h[3]) << 16);
-        *(uint2*)(dst + r0) = pk;
-      } else {
-        *(float4*)(dst + r0) = make_float4(o[0], o[1], o[2], o[3]);
-      }
+      shadow_store4(dst, r0, o);
     }
   }
 }
@@ -280,8 +241,7 @@ __global__ __launch_bounds__(256) void adam_proj_fused_kernel(float* __restrict_
     dT[row * nbp + bp] = d;
   }
   __syncthreads();
-  const float t = (float)(*stepp + 1ull);
-  const float inv_sqrt_bc2 = rsqrtf(1.f - powf(b2, t));
+  const AdamCoef c{lr, adam_inv_sqrt_bc2(b2, adam_step_t(stepp)), b2, eps, ema_decay};
   const int quads = K / 4, kq = tid % quads, rpp = 256 / quads;
   for (int row = tid / quads; row < APF_ROWS && r0 + row < Np; row += rpp) {
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
@@ -301,37 +261,42 @@ __global__ __launch_bounds__(256) void adam_proj_fused_kernel(float* __restrict_
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float g = acc[k] * wscale * gscale;
-      const float vi = b2 * vv[k] + (1.f - b2) * g * g;
-      vv[k] = vi;
-      pv[k] = pv[k] - lr * (g / (sqrtf(vi) * inv_sqrt_bc2 + eps));
-      ev[k] = ema_decay * ev[k] + (1.f - ema_decay) * pv[k];
+      adam_ema_apply(g, g, vv[k], pv[k], ev[k], c);
     }
     ((float4*)p)[i4] = make_float4(pv[0], pv[1], pv[2], pv[3]);
     ((float4*)v)[i4] = make_float4(vv[0], vv[1], vv[2], vv[3]);
     if (ema) ((float4*)ema)[i4] = make_float4(ev[0], ev[1], ev[2], ev[3]);
-    if (shadow) {
-      if constexpr (sizeof(ST) == 2) {
-        const ST h[4] = {(ST)pv[0], (ST)pv[1], (ST)pv[2], (ST)pv[3]};
-        uint2 pk;
-        pk.x = (unsigned)__builtin_bit_cast(unsigned short, h[0]) | ((unsigned)__builtin_bit_cast(unsigned short, h[1]) << 16);
-        pk.y = (unsigned)__builtin_bit_cast(unsigned short, h[2]) | ((unsigned)__builtin_bit_cast(unsigned short, h[3]) << 16);
-        ((uint2*)shadow)[i4] = pk;
-      } else {
-        ((float4*)shadow)[i4] = make_float4(pv[0], pv[1], pv[2], pv[3]);
-      }
-    }
+    if (shadow) shadow_store4(shadow, 4 * i4, pv);
+  }
+}
+
+// master [16][ci][co] fp32 -> shadow [16][co][ci] T: the 32 x 32 block (ti, tj) of one tap through an LDS tile
+template <typename T>
+__device__ __forceinline__ void transpose_tile32(const float* master, T* shadow, int Ci, int Co, int tap, int ti, int tj) {
+  __shared__ float tile[32][33];
+  const int ci0 = ti * 32, co0 = tj * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+  const float* src = master + (long)tap * Ci * Co;
+  T* dst = shadow + (long)tap * Ci * Co;
+  for (int r = ty; r < 32; r += 8) {
+    const int ci = ci0 + r, co = co0 + tx;
+    tile[r][tx] = (ci < Ci && co < Co) ? src[(long)ci * Co + co] : 0.f;
+  }
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8) {
+    const int co = co0 + r, ci = ci0 + tx;
+    if (ci < Ci && co < Co) dst[(long)co * Ci + ci] = (T)tile[tx][r];
   }
 }
 
 // all conv segments of a network in one launch: desc[5 i + (0..4)] = (source element offset in `master`, destination
-// pointer, Ci, Co, first tile index); a tile = (tap, 32 x 32 block of [ci][co]) as in transpose_shadow_kernel
+// pointer, Ci, Co, first tile index); a tile = (tap, 32 x 32 block of [ci][co]) as in transpose_tile32
 struct UpFrags { DgUpFrag f[4]; int n; int first_block; };   // blocks >= first_block: 3 x UP_FRAG_BLOCKS per fragment set
 // (+ optionally one last block that advances the step's counters and files its scalars: dg_transpose_shadow_multi_tail)
 template <typename T>
 __global__ __launch_bounds__(256) void transpose_shadow_multi_kernel(const float* __restrict__ master,
                                                                      const long long* __restrict__ desc, int nseg,
                                                                      UpFrags uf, CounterAdds ca, int ca_block) {
-  __shared__ float tile[32][33];
   if ((int)blockIdx.x == ca_block) { counter_adds_body(ca); return; }
   if (uf.n > 0 && (int)blockIdx.x >= uf.first_block) {
     const int job = (int)blockIdx.x - uf.first_block, per = 3 * UP_FRAG_BLOCKS;
@@ -352,19 +317,8 @@ __global__ __launch_bounds__(256) void transpose_shadow_multi_kernel(const float
   int t = (int)(blockIdx.x - d[4]);
   const int tap = t / (tci * tco);
   t -= tap * tci * tco;
-  const int ci0 = (t / tco) * 32, co0 = (t % tco) * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-  const float* src = master + d[0] + (long)tap * Ci * Co;
-  T* dst = (T*)d[1] + (long)tap * Ci * Co;
-  for (int r = ty; r < 32; r += 8) {
-    const int ci = ci0 + r, co = co0 + tx;
-    tile[r][tx] = (ci < Ci && co < Co) ? src[(long)ci * Co + co] : 0.f;
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int co = co0 + r, ci = ci0 + tx;
-    if (ci < Ci && co < Co) dst[(long)co * Ci + ci] = (T)tile[tx][r];
-  }
+  const int ti = t / tco, tj = t % tco;
+  transpose_tile32(master + d[0], (T*)d[1], Ci, Co, tap, ti, tj);
 }
 
 template <typename T>
@@ -421,50 +375,50 @@ __global__ void uncast_kernel(const T* __restrict__ src, float* __restrict__ dst
   if (i < n) dst[i] = (float)src[i];
 }
 
-// master [16][ci][co] fp32 -> shadow [16][co][ci] T, through a 32x32 LDS tile per (tap, ci-tile, co-tile)
+// master [16][ci][co] fp32 -> shadow [16][co][ci] T, a workgroup per (tap, ci-tile, co-tile)
 template <typename T>
 __global__ __launch_bounds__(256) void transpose_shadow_kernel(const float* __restrict__ src, T* __restrict__ dst,
                                                                int Ci, int Co) {
-  __shared__ float tile[32][33];
-  const int tap = blockIdx.z;
-  const int ci0 = blockIdx.y * 32, co0 = blockIdx.x * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
-  const float* s = src + (long)tap * Ci * Co;
-  T* d = dst + (long)tap * Ci * Co;
-  for (int r = ty; r < 32; r += 8) {
-    const int ci = ci0 + r, co = co0 + tx;
-    tile[r][tx] = (ci < Ci && co < Co) ? s[(long)ci * Co + co] : 0.f;
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int co = co0 + r, ci = ci0 + tx;
-    if (ci < Ci && co < Co) d[(long)co * Ci + ci] = (T)tile[tx][r];
-  }
+  transpose_tile32(src, dst, Ci, Co, blockIdx.z, blockIdx.y, blockIdx.x);
 }
 
 static inline unsigned nblk(long n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
+
+// adam_ema_kernel over n elements: the bias factors from the host (step_dev == nullptr) or formed in the kernel from *step_dev
+static int adam_ema_launch(float* p, const float* grad, float* m, float* v, float* ema, void* shadow, int shadow_dtype, long n,
+                           float gscale, float lr, float lr_bc1, float inv_sqrt_bc2, float beta1, float beta2, float eps,
+                           const unsigned long long* step_dev, float ema_decay, void* s_) {
+  hipStream_t s = (hipStream_t)s_;
+  if (n <= 0) return DG_OK;
+  if (n % 4 != 0) return DG_EINVAL;  // flat stores are padded to 64 elements
+  const long n4 = n / 4;
+  unsigned grid = nblk(n4);
+  if (grid > 256 * 16) grid = 256 * 16;
+  if (shadow && shadow_dtype == DG_BF16)
+    adam_ema_kernel<bf16><<<grid, 256, 0, s>>>(p, grad, m, v, ema, (bf16*)shadow, n4, gscale, lr_bc1, inv_sqrt_bc2, beta1, beta2, eps, ema_decay, step_dev, lr);
+  else
+    adam_ema_kernel<float><<<grid, 256, 0, s>>>(p, grad, m, v, ema, (float*)shadow, n4, gscale, lr_bc1, inv_sqrt_bc2, beta1, beta2, eps, ema_decay, step_dev, lr);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
 
 extern "C" {
 
 int dg_adam_ema_step(float* p, const float* grad, float* m, float* v, float* ema, void* shadow, int shadow_dtype,
                      long n, float gscale, float lr, float beta1, float beta2, float eps, int step, float ema_decay,
                      void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  if (n <= 0) return DG_OK;
-  if (n % 4 != 0) return DG_EINVAL;  // flat stores are padded to 64 elements
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float lr_bc1 = (float)((double)lr / bc1);
-  const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-  const long n4 = n / 4;
-  unsigned grid = nblk(n4);
-  if (grid > 256 * 16) grid = 256 * 16;
-  if (shadow && shadow_dtype == DG_BF16)
-    adam_ema_kernel<bf16><<<grid, 256, 0, s>>>(p, grad, m, v, ema, (bf16*)shadow, n4, gscale, lr_bc1, inv_sqrt_bc2, beta1, beta2, eps, ema_decay, nullptr, lr);
-  else
-    adam_ema_kernel<float><<<grid, 256, 0, s>>>(p, grad, m, v, ema, (float*)shadow, n4, gscale, lr_bc1, inv_sqrt_bc2, beta1, beta2, eps, ema_decay, nullptr, lr);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
+  return adam_ema_launch(p, grad, m, v, ema, shadow, shadow_dtype, n, gscale, lr, (float)((double)lr / bc1),
+                         (float)(1.0 / sqrt(bc2)), beta1, beta2, eps, nullptr, ema_decay, s_);
+}
+
+int dg_adam_ema_step_dev(float* p, const float* grad, float* m, float* v, float* ema, void* shadow, int shadow_dtype,
+                         long n, float gscale, float lr, float beta1, float beta2, float eps,
+                         const unsigned long long* step_dev, float ema_decay, void* s_) {
+  if (n > 0 && !step_dev) return DG_EINVAL;
+  return adam_ema_launch(p, grad, m, v, ema, shadow, shadow_dtype, n, gscale, lr, 0.f, 0.f, beta1, beta2, eps, step_dev,
+                         ema_decay, s_);
 }
 
 // up to 16 fp32 buffers -> DG_BF16X2 twins in one launch (the split-bf16 copies of the fat layers' weight shadows)
@@ -511,23 +465,6 @@ int dg_transpose_shadow(const float* master, void* dst, int dtype, int Ci, int C
   dim3 grid((Co + 31) / 32, (Ci + 31) / 32, 16);
   if (dtype == DG_BF16) transpose_shadow_kernel<bf16><<<grid, 256, 0, s>>>(master, (bf16*)dst, Ci, Co);
   else transpose_shadow_kernel<float><<<grid, 256, 0, s>>>(master, (float*)dst, Ci, Co);
-  HIP_CHECK_RET(hipGetLastError());
-  return DG_OK;
-}
-
-int dg_adam_ema_step_dev(float* p, const float* grad, float* m, float* v, float* ema, void* shadow, int shadow_dtype,
-                         long n, float gscale, float lr, float beta1, float beta2, float eps,
-                         const unsigned long long* step_dev, float ema_decay, void* s_) {
-  hipStream_t s = (hipStream_t)s_;
-  if (n <= 0) return DG_OK;
-  if (n % 4 != 0 || !step_dev) return DG_EINVAL;
-  const long n4 = n / 4;
-  unsigned grid = nblk(n4);
-  if (grid > 256 * 16) grid = 256 * 16;
-  if (shadow && shadow_dtype == DG_BF16)
-    adam_ema_kernel<bf16><<<grid, 256, 0, s>>>(p, grad, m, v, ema, (bf16*)shadow, n4, gscale, 0.f, 0.f, beta1, beta2, eps, ema_decay, step_dev, lr);
-  else
-    adam_ema_kernel<float><<<grid, 256, 0, s>>>(p, grad, m, v, ema, (float*)shadow, n4, gscale, 0.f, 0.f, beta1, beta2, eps, ema_decay, step_dev, lr);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }

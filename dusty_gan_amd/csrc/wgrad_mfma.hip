@@ -11,6 +11,7 @@
 //     full-rate shape), or stored when there is a single split and nothing to accumulate onto.
 //   * the per-sample weight (dy_b for the real batch) costs no second accumulator set: the running sum is
 //     kept divided by the current sample's weight and rescaled by rs_old / rs_new when the sample changes.
+#include "adam.h"
 #include "mfma_common.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -234,8 +235,7 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(WgradP p, int tiles_n, 
     // tile is first transposed through LDS (64 rows at a time, the rows of one wave-row) and then walked with 16-byte
     // accesses, 32 lanes covering one 512-byte row segment.
     static_assert(BM == 128 && BN == 128 && sizeof(lds) >= 64 * BN * 4, "ADAM epilogue: 128 x 128 tiles");
-    const float t = (float)(*ad.stepp + 1ull);
-    const float inv_sqrt_bc2 = rsqrtf(1.f - powf(ad.b2, t));
+    const AdamCoef c{ad.lr, adam_inv_sqrt_bc2(ad.b2, adam_step_t(ad.stepp)), ad.b2, ad.eps, ad.ema_decay};
     const float gmul = p.scale * cur_rs * ad.gscale;
     float* stage = (float*)lds;
     __syncthreads();  // every wave is done reading the operand tiles
@@ -270,24 +270,14 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(WgradP p, int tiles_n, 
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const float g = gv[k] * gmul;
-            const float vi = ad.b2 * vv[k] + (1.f - ad.b2) * g * g;
-            vv[k] = vi;
-            pv[k] = pv[k] - ad.lr * (g / (sqrtf(vi) * inv_sqrt_bc2 + ad.eps));
-            ev[k] = ad.ema_decay * ev[k] + (1.f - ad.ema_decay) * pv[k];
+            adam_ema_apply(g, g, vv[k], pv[k], ev[k], c);
           }
           __builtin_nontemporal_store(nt4{pv[0], pv[1], pv[2], pv[3]}, (nt4*)ad.p + i4);
           __builtin_nontemporal_store(nt4{vv[0], vv[1], vv[2], vv[3]}, (nt4*)ad.v + i4);
           if (ad.ema) __builtin_nontemporal_store(nt4{ev[0], ev[1], ev[2], ev[3]}, (nt4*)ad.ema + i4);
           if (ad.shadow) {
-            if (ad.shadow_bf16) {
-              const bf16 h[4] = {(bf16)pv[0], (bf16)pv[1], (bf16)pv[2], (bf16)pv[3]};
-              uint2 pk;
-              pk.x = (unsigned)__builtin_bit_cast(unsigned short, h[0]) | ((unsigned)__builtin_bit_cast(unsigned short, h[1]) << 16);
-              pk.y = (unsigned)__builtin_bit_cast(unsigned short, h[2]) | ((unsigned)__builtin_bit_cast(unsigned short, h[3]) << 16);
-              ((uint2*)ad.shadow)[i4] = pk;
-            } else {
-              ((float4*)ad.shadow)[i4] = make_float4(pv[0], pv[1], pv[2], pv[3]);
-            }
+            if (ad.shadow_bf16) shadow_store4((bf16*)ad.shadow, 4 * i4, pv);
+            else shadow_store4((float*)ad.shadow, 4 * i4, pv);
           }
         }
       }
