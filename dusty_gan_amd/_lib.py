@@ -89,6 +89,7 @@ class DgWgrad(C.Structure):
 
 
 XSUM_PARTS = 8   # DG_XSUM_PARTS of include/dusty_gan_hip.h
+EXPORT_CHUNK = 1024   # DG_EXPORT_CHUNK: the pixels per workgroup of dg_export_points (sizes its chunk_counts workspace)
 
 
 class DgFetch(C.Structure):
@@ -241,6 +242,8 @@ PROTOTYPES = {
     "dg_additive_noise": [_P, _P, _F, _L, _P, _P],
     "dg_median3x3": [_P, _I, _I, _I, _P, _P],
     "dg_hole_fill": [_P, _P, _I, _I, _I, _F, _P, _P, _P],
+    "dg_latent_walk": [_P, _P, _I, _I, _I, _P, _P],
+    "dg_export_points": [_P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -9,6 +9,7 @@
 //     (utils/__init__.py:163-178, utils/lidar.py:38-68).
 // Both are HBM-bound: one 16-byte cell read per output pixel / one image-sized stream in, three out.
 #include "common.h"
+#include "inv_point.h"
 
 namespace {
 
@@ -74,25 +75,15 @@ __global__ __launch_bounds__(256) void inv_to_xyz_kernel(const float* __restrict
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const long px = i % hw, b = i / hw;
-  float inv = in[i];
-  if (from_tanh) {  // tanh_to_sigmoid(.).clamp_(0, 1)  utils/__init__.py:168
-    inv = (inv + 1.f) / 2.f;
-    inv = fminf(fmaxf(inv, 0.f), 1.f);
-  }
+  const float inv = dg_inv01(in[i], from_tanh);   // the pixel body: inv_point.h (shared with the point-cloud export)
   if (depth01) depth01[i] = inv;
-  const bool valid = fabsf(inv - drop_const) > tol;                           // lidar.py:59
-  const float disp = inv * (1.f / min_d - 1.f / max_d) + 1.f / max_d;          // revert_depth :40-43
-  float d = 1.f / disp;
-  d = (d - min_d) / (max_d - min_d);                                           // :45-46
-  d = d * (max_d - min_d) + min_d;                                             // :61
-  d = d / max_d;                                                               // :62
-  d = valid ? d : 0.f;                                                         // :63
-  const float pitch = angle[px], yaw = angle[hw + px];
-  const float cp = cosf(pitch), sp = sinf(pitch), cy = cosf(yaw), sy = sinf(yaw);
+  const bool valid = dg_inv_valid(inv, drop_const, tol);
+  float x, y, z;
+  dg_inv_point(inv, valid, min_d, max_d, angle[px], angle[hw + px], x, y, z);
   const long o = b * 3 * hw + px;
-  points[o] = d * cp * cy;                                                     // pol_to_xyz :49-56
-  points[o + hw] = d * cp * sy;
-  points[o + 2 * hw] = d * sp;
+  points[o] = x;
+  points[o + hw] = y;
+  points[o + 2 * hw] = z;
 }
 
 // mode 0: tanh_to_sigmoid(x).clamp(0,1)  (depth_orig, utils/__init__.py:169-170);  mode 1: sigmoid(x) (confidence, :171-172)

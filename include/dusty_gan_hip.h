@@ -812,6 +812,24 @@ int dg_additive_noise(const float* x, const float* noise, float strength, long n
 int dg_median3x3(const float* x, int B, int H, int W, float* out, void* stream);
 int dg_hole_fill(float* x, float* tmp, int B, int H, int W, float thresh, int* sweeps, int* left, void* stream);
 
+/* ---- the synthesis command (dusty_gan_amd/synthesis.py; csrc/synthesis.hip) -----------------------
+ * dg_latent_walk: out[i] = walk(w_i, z0, z1) for i < n with w = torch.linspace(0, 1, n) in float32 (n = 1: w = 0);
+ * z0, z1 [nz], out [n, nz].  mode 0 = lerp, 1 = slerp  utils/interp.py:4-16: slerp's angle comes from the normalised
+ * endpoints, the un-normalised ones are blended.  Norms and dot product are reduced once per launch; arithmetic in
+ * float64, rounded once per output (lerp's rows 0 and n - 1 are z0 and z1 exactly).  Endpoints on one line (|cos| = 1 in
+ * float32) give non-finite rows under slerp.  n < 1, nz < 1 or an unknown mode: DG_EINVAL.
+ * dg_export_points: generated inverse depth inv [B,1,H,W] (as dg_inv_to_xyz's `in`, with its from_tanh / drop_const /
+ * tol) on the angle grid [2,H,W] -> out [B, H W, 4] float32 (16-byte aligned): for every scan b, out[b, 0:counts[b]]
+ * holds one KITTI record (x, y, z, 0) in METRES per valid pixel, in row-major pixel order (ring 0 first, columns
+ * ascending).  A pixel is valid by dg_inv_to_xyz's predicate and its coordinates are that function's `points` times
+ * max_depth (one pixel body, csrc/inv_point.h).  Records at and beyond counts[b] are not written.  chunk_counts: workspace
+ * of B * ceil(H W / DG_EXPORT_CHUNK) int32 (need not be initialised).  Two launches, no atomics: two calls give the same
+ * bytes.  H W > 2^31 - 1: DG_EINVAL. */
+#define DG_EXPORT_CHUNK 1024
+int dg_latent_walk(const float* z0, const float* z1, int n, int nz, int mode, float* out, void* stream);
+int dg_export_points(const float* inv, const float* angle, int B, int H, int W, int from_tanh, float min_depth,
+                     float max_depth, float drop_const, float tol, int* chunk_counts, float* out, int* counts, void* stream);
+
 const char* dg_version(void);
 
 #ifdef __cplusplus
