@@ -244,6 +244,7 @@ PROTOTYPES = {
     "dg_hole_fill": [_P, _P, _I, _I, _I, _F, _P, _P, _P],
     "dg_latent_walk": [_P, _P, _I, _I, _I, _P, _P],
     "dg_export_points": [_P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P],
+    "dg_points_to_depth": [_P, _L, _I, _P, _I, _I, _P, _I, _I, _D, _D, _D, _F, _P, _P, _P, _P, _P],
 }
 
 _lib = None

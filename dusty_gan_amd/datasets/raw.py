@@ -22,10 +22,9 @@ H_RINGS = 64  # the reference hard-codes the last ring's row (process_kitti.py:1
 class RawScanError(L.DgError):
     """a raw scan the reference's script would have raised on; `.names` lists the scans (files)"""
 
-    def __init__(self, names):
+    def __init__(self, names, why="more than 128 ring starts (a ring row below -64, where numpy's index raises)"):
         self.names = list(names)
-        super().__init__("more than 128 ring starts (a ring row below -64, where numpy's index raises): "
-                         + ", ".join(str(n) for n in self.names))
+        super().__init__(why + ": " + ", ".join(str(n) for n in self.names))
 
 
 def _device(device):
@@ -221,6 +220,50 @@ def _read_bin_into(path, dst):
     with open(path, "rb") as f:
         if f.readinto(memoryview(dst).cast("B")) != dst.nbytes:
             raise ValueError(f"{path}: changed size while being read")
+
+
+def _cloud_rows(path):
+    """(rows, columns) of a cloud file: a KITTI `.bin` (N x 4 float32) or a `.npy` of shape N x 3 or N x 4"""
+    if path.endswith(".npy"):
+        with open(path, "rb") as f:
+            header = _npy_header(f)
+        if header is None or len(header[0]) != 2 or header[0][1] not in (3, 4):
+            raise RawScanError([path], "not an N x 3 or N x 4 .npy array")
+        n, cols = int(header[0][0]), int(header[0][1])
+    else:
+        size = osp.getsize(path)
+        if size % 16:
+            raise RawScanError([path], f"{size} bytes is not a whole number of (x, y, z, reflectance) float32 records")
+        n, cols = size // 16, 4
+    if n == 0:
+        raise RawScanError([path], "an empty cloud")
+    return n, cols
+
+
+def read_clouds(paths, max_depth, device=None):
+    """cloud files -> (records [B,Nmax,4] float32 in UNIT space (metres / max_depth; column 3 as stored, 0 for N x 3 files),
+    counts [B] int32) on `device`: what LiDAR.points_to_depth takes with counts=.  A file is a KITTI `.bin` (N x 4
+    little-endian float32, metres) or a `.npy` of shape N x 3 or N x 4 (metres).  Clouds shorter than the longest are padded
+    with zero records, which points_to_depth does not read.  An empty file, a `.bin` whose size is not a multiple of 16 bytes
+    or a `.npy` of another shape raises RawScanError naming the file."""
+    paths = [os.fspath(p) for p in paths]
+    if not paths:
+        raise FileNotFoundError("read_clouds: no cloud files")
+    shapes = [_cloud_rows(p) for p in paths]
+    counts = np.array([n for n, _ in shapes], dtype=np.int32)
+    records = np.zeros((len(paths), int(counts.max()), 4), dtype=np.float32)
+    for b, (path, (n, cols)) in enumerate(zip(paths, shapes)):
+        if not path.endswith(".npy"):
+            _read_bin_into(path, records[b, :n])
+        elif cols == 4:
+            _read_npy_into(path, records[b, :n])
+        else:
+            xyz = np.empty((n, 3), dtype=np.float32)
+            _read_npy_into(path, xyz)
+            records[b, :n, :3] = xyz
+        records[b, :n, :3] /= np.float32(max_depth)
+    dev = _device(device)
+    return torch.from_numpy(records).to(dev), torch.from_numpy(counts).to(dev)
 
 
 class _ProjSlot:

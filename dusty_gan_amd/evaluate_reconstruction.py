@@ -45,13 +45,13 @@ def _corruption_arg(text):
         raise argparse.ArgumentTypeError(str(e))
 
 
-def parse_args(argv=None):
-    parser = argparse.ArgumentParser()
+def add_inversion_arguments(parser, batch_size=512):
+    """the flags every inversion command shares (this one and dusty_gan_amd.reconstruct)"""
     parser.add_argument("--model-path", type=str, required=True)
     parser.add_argument("--config-path", type=str, required=True)
     parser.add_argument("--save-dir-path", type=str, default=".")
     parser.add_argument("--tol", type=float, default=0)
-    parser.add_argument("--batch-size", type=int, default=512)
+    parser.add_argument("--batch-size", type=int, default=batch_size)
     parser.add_argument("--distance", default="l1", type=_distance_arg,
                         help="the inversion loss: l1 or l2 (the reference's command), or - beyond the reference's command, "
                              "which offers those two only - chamfer (the third loss of the reference's demo, demo.py:508-519) "
@@ -69,7 +69,9 @@ def parse_args(argv=None):
                              "low_resolution are accepted too); the scores are against the full scan")
     parser.add_argument("--corruption-seed", type=int, default=0,
                         help="Philox seed of the corruption's draws (scan i of the dataset draws the same numbers in any batch)")
-    args = parser.parse_args(argv)
+
+
+def check_inversion_arguments(parser, args):
     from .inversion import MAX_CODES, parse_composition_layer
     if not 1 <= args.num_code <= MAX_CODES:
         parser.error(f"--num-code: 1..{MAX_CODES}")
@@ -80,6 +82,13 @@ def parse_args(argv=None):
             parse_composition_layer(args.composition_layer)
         except NotImplementedError as e:
             parser.error(str(e))
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser()
+    add_inversion_arguments(parser)
+    args = parser.parse_args(argv)
+    check_inversion_arguments(parser, args)
     return args
 
 
@@ -94,10 +103,12 @@ def flatten(t):
     return t.flatten(2).permute(0, 2, 1).contiguous()
 
 
-def evaluate_batch(G, lidar, arch, item, args, first_index=0):
+def evaluate_batch(G, lidar, arch, item, args, first_index=0, outputs=None):
     """one batch of the reference's loop body (:80-152) -> {column: list}.  With args.corruption the latent is optimised
     against the corrupted (depth, mask) - the Chamfer term's reference points included - and every column is scored against
-    the full scan (demo.py:385-397); first_index: the dataset index of the batch's first scan (keys the corruption's draws)"""
+    the full scan (demo.py:385-397); first_index: the dataset index of the batch's first scan (keys the corruption's draws);
+    outputs: a dict that receives the postprocessed generator outputs ("depth", "points", "normals", ...), the optimised
+    inverse depth "inv_gen" and the inversion's target "target_inv" / "target_mask" (dusty_gan_amd.reconstruct)"""
     from .inversion import invert
     from .utils.lidar import postprocess
     from .utils.metrics.depth import depth_metrics
@@ -117,6 +128,8 @@ def evaluate_batch(G, lidar, arch, item, args, first_index=0):
     res = invert(G, tgt_ref, tgt_mask, num_step=args.num_step, distance=names[0] if len(names) == 1 else names,
                  lidar=lidar if "chamfer" in names else None, **multi)
     out = postprocess(res["out"], lidar, tol=args.tol)
+    if outputs is not None:
+        outputs.update(out, inv_gen=res["inv_gen"], target_inv=tgt_ref, target_mask=tgt_mask)
     cd = compute_cd(flatten(xyz.float()), flatten(out["points"]))
     if "dusty" in arch:
         keep, keep_is_depth = out["mask"], False

@@ -1,0 +1,158 @@
+"""Reconstruct your own point clouds by GAN inversion: cloud in, restored cloud out.
+
+    python -m dusty_gan_amd.reconstruct --model-path <ckpt.pth> --config-path <config.yaml> --points PATH [PATH ...]
+        [--save-dir-path .] [--batch-size 32] [--tau 2] [--no-images] [--no-bins]
+        [--distance l1] [--num-step 1000] [--tol 0] [--num-code N --composition-layer NAME]
+        [--corruption NAME [--corruption-seed 0]]
+
+PATH is a cloud file - a KITTI `.bin` (N x 4 float32, metres) or a `.npy` of shape N x 3 or N x 4 - or a directory, whose
+`*.bin` / `*.npy` files are taken in sorted order.  The points may come in any order and from any sensor: every cloud is
+projected onto the model's angle grid by LiDAR.points_to_depth (reference: Coordinate.points_to_depth, utils/lidar.py:70-107,
+which the reference's demo feeds its inversion with), then inverted and scored exactly as evaluate_reconstruction does
+with a dataset's scans; the inversion flags are that command's own.  Under <save-dir-path>/reconstruction/ it writes
+    scores.csv             one row per file: its stem, then evaluate_reconstruction's columns (against the projected cloud)
+    targets/<stem>.npy     [2,H,W] float32: the projected normalised depth (1 where no point fell) and its mask
+    points/<stem>.bin      the reconstruction as KITTI records (x, y, z, 0) in metres (synthesis.export_points)
+    images/<stem>.png      target (as the inversion saw it: corrupted with --corruption) beside reconstruction, three rows:
+                           inverse depth (turbo), mask, bird's-eye view
+Two files with the same stem are refused before any work starts."""
+import argparse
+import csv
+import glob
+import os
+import os.path as osp
+
+from .evaluate_reconstruction import COLUMNS, add_inversion_arguments, check_inversion_arguments, evaluate_batch, scans_per_pass
+
+PICTURES = ("inv.png", "mask.png", "bev.png")   # synthesize.pictures_of's names, top to bottom
+
+
+def expand_paths(paths):
+    """files as given, a directory's *.bin / *.npy in sorted order -> [(stem, path)]; ValueError on a stem met twice, a
+    directory without clouds or a path that does not exist"""
+    files = []
+    for p in paths:
+        p = os.fspath(p)
+        if osp.isdir(p):
+            found = sorted(glob.glob(osp.join(p, "*.bin")) + glob.glob(osp.join(p, "*.npy")))
+            if not found:
+                raise ValueError(f"{p}: no *.bin or *.npy files")
+            files += found
+        elif osp.isfile(p):
+            files.append(p)
+        else:
+            raise ValueError(f"{p}: no such file or directory")
+    seen = {}
+    for path in files:
+        stem = osp.splitext(osp.basename(path))[0]
+        if stem in seen:
+            raise ValueError(f"two clouds named {stem!r}: {seen[stem]} and {path} (the outputs are named after the stem)")
+        seen[stem] = path
+    return list(seen.items())
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser()
+    add_inversion_arguments(parser, batch_size=32)
+    parser.add_argument("--points", type=str, nargs="+", required=True, help="cloud files (.bin / .npy) or directories of them")
+    parser.add_argument("--tau", type=float, default=2, help="points_to_depth's depth weight exp(-tau depth), 0..16")
+    parser.add_argument("--no-images", action="store_true")
+    parser.add_argument("--no-bins", action="store_true")
+    args = parser.parse_args(argv)
+    check_inversion_arguments(parser, args)
+    if not 0 <= args.tau <= 16:
+        parser.error("--tau: 0..16")
+    if args.batch_size < 1:
+        parser.error("--batch-size must be at least 1")
+    try:
+        args.clouds = expand_paths(args.points)
+    except ValueError as e:
+        parser.error(str(e))
+    return args
+
+
+def project_clouds(lidar, paths, tau, device):
+    """cloud files -> evaluate_batch's item dict: "depth" / "mask" = points_to_depth of the clouds, "xyz" = the projected
+    target's own point map"""
+    from .datasets.raw import read_clouds
+    records, counts = read_clouds(paths, lidar.max_depth, device)
+    depth, valid = lidar.points_to_depth(records, drop_value=1, tau=tau, counts=counts)
+    mask = valid.float()
+    inv_ref = mask * lidar.invert_depth(depth)
+    return {"depth": depth, "mask": mask, "xyz": lidar.inv_to_xyz(inv_ref)}
+
+
+def _side_by_side(pics_target, pics_recon, b):
+    """file b's picture: per row of PICTURES, target beside reconstruction (make_grid of the two), rows stacked and
+    padded on the right to the widest -> uint8 [H,W,3]"""
+    import numpy as np
+    import torch
+
+    from .utils.render import image_grid
+    rows = []
+    for name in PICTURES:
+        (xt, color, scale), (xr, _, _) = pics_target[name], pics_recon[name]
+        rows.append(image_grid(torch.cat([xt[b:b + 1], xr[b:b + 1]], dim=0), color=color, scale=scale).cpu().numpy())
+    width = max(r.shape[1] for r in rows)
+    return np.concatenate([np.pad(r, ((0, 0), (0, width - r.shape[1]), (0, 0))) for r in rows], axis=0)
+
+
+def main(argv=None):
+    """-> the directory written (<save-dir-path>/reconstruction)"""
+    args = parse_args(argv)
+    import numpy as np
+    import torch
+
+    from . import synthesis as S
+    from . import utils
+    from .synthesize import pictures_of
+    from .utils.lidar import xyz_to_normal
+    cfg, G, lidar, device = utils.setup(args.model_path, args.config_path, ema=True, fix_noise=True)
+    utils.set_requires_grad(G, False)
+    if lidar.angle is None:
+        raise RuntimeError(f"no angle grid: {lidar.angle_file!r} does not exist (utils/lidar.py:120)")
+    arch = str(cfg.model.gen.arch)
+    out_dir = osp.join(args.save_dir_path, "reconstruction")
+    images, bins = not args.no_images, not args.no_bins
+    for sub in ["targets"] + ["images"] * images + ["points"] * bins:
+        os.makedirs(osp.join(out_dir, sub), exist_ok=True)
+    if images:
+        R, t = (v.to(device) for v in S.view())
+    written, rows = [], []
+    step = scans_per_pass(args.batch_size, args.num_code)
+    for i in range(0, len(args.clouds), step):
+        stems, paths = zip(*args.clouds[i:i + step])
+        item = project_clouds(lidar, paths, args.tau, device)
+        target = torch.cat([item["depth"], item["mask"]], dim=1).cpu().numpy()
+        for b, stem in enumerate(stems):
+            written.append(osp.join(out_dir, "targets", f"{stem}.npy"))
+            np.save(written[-1], target[b])
+        outputs = {}
+        cols = evaluate_batch(G, lidar, arch, item, args, first_index=i, outputs=outputs)
+        rows += [[stem] + [repr(float(cols[k][b])) for k in COLUMNS] for b, stem in enumerate(stems)]
+        if bins:
+            records, counts = S.export_points(outputs["depth"], lidar, tol=args.tol, from_tanh=False)
+            written += S.write_bins(records, counts, osp.join(out_dir, "points"), names=stems)
+        if images:
+            from PIL import Image
+            if "mask" not in outputs:   # a baseline generator drops where its depth is (near) zero: evaluate_batch's keep rule
+                outputs["mask"] = (outputs["depth"] > args.tol).float()
+            pts = lidar.inv_to_xyz(outputs["target_inv"])
+            tgt = {"depth": outputs["target_inv"], "mask": outputs["target_mask"], "points": pts, "normals": xyz_to_normal(pts)}
+            pics_t = {name: (x, color, scale) for name, x, color, scale in pictures_of(tgt, R, t)}
+            pics_r = {name: (x, color, scale) for name, x, color, scale in pictures_of(outputs, R, t)}
+            for b, stem in enumerate(stems):
+                written.append(osp.join(out_dir, "images", f"{stem}.png"))
+                Image.fromarray(_side_by_side(pics_t, pics_r, b)).save(written[-1])
+    with open(osp.join(out_dir, "scores.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["name"] + COLUMNS)
+        w.writerows(rows)
+    written.append(osp.join(out_dir, "scores.csv"))
+    for path in written:
+        print("wrote:", path)
+    return out_dir
+
+
+if __name__ == "__main__":
+    main()

@@ -126,14 +126,14 @@ def bin_path(dir, index):
     return os.path.join(dir, "{:06d}.bin".format(int(index)))
 
 
-def write_bins(records, counts, dir, first_index=0):
-    """records [B,HW,4], counts [B] -> dir/<first_index + b:06d>.bin, counts[b] * 4 little-endian float32 each (what
-    np.fromfile(path, np.float32).reshape(-1, 4) reads back); only records[b, :counts[b]] is copied to the host.
-    Returns the paths."""
+def write_bins(records, counts, dir, first_index=0, names=None):
+    """records [B,HW,4], counts [B] -> dir/<first_index + b:06d>.bin (or dir/<names[b]>.bin), counts[b] * 4 little-endian
+    float32 each (what np.fromfile(path, np.float32).reshape(-1, 4) reads back); only records[b, :counts[b]] is copied to
+    the host.  Returns the paths."""
     os.makedirs(dir, exist_ok=True)
     paths = []
     for b, k in enumerate(counts.tolist()):
-        path = bin_path(dir, first_index + b)
+        path = bin_path(dir, first_index + b) if names is None else os.path.join(dir, f"{names[b]}.bin")
         records[b, :int(k)].detach().cpu().contiguous().numpy().astype("<f4", copy=False).tofile(path)
         paths.append(path)
     return paths

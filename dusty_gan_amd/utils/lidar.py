@@ -4,7 +4,9 @@ On the training path it provides `fetch_reals` (Coordinate.invert_depth :31-36 f
 drop-constant fill of Trainer.fetch_reals, trainers/dcgan_amp.py:154-160).  On the output side it turns generated
 inverse depth into the unit-space point map (`inv_to_xyz` :58-65 with revert_depth / pol_to_xyz) on the sensor's
 angle grid (`angles.pt`, resized like LiDAR.init_coordmap :127-130).  All arithmetic is in csrc/ (step_inputs.h,
-step_inputs.hip, lidar_io.hip, incl. the surface-normal image of utils/geometry.py); `points_to_depth` (:67-108, used by the reconstruction demo only) is not built.
+step_inputs.hip, lidar_io.hip, incl. the surface-normal image of utils/geometry.py).  `points_to_depth` (:70-107) is the way in for
+arbitrary clouds: every point is binned into the pixel of the angle grid whose (elevation, azimuth) is nearest
+(csrc/points_depth.hip).
 """
 import math
 import os
@@ -13,6 +15,10 @@ import torch
 import torch.nn.functional as F
 
 from .. import _lib as L
+from .render import _workspace   # zero-at-rest u64 words per (device, stream, size), shared with the renderers
+
+TAU_MAX = 16.0          # dg_points_to_depth: exp(-tau) stays 17 bits above the sums' 2^-40 quantum
+MAX_POINTS = 1 << 18    # its points per cloud and pixels per image (dg_fix40's range analysis)
 
 
 class LiDAR:
@@ -132,6 +138,45 @@ class LiDAR:
                                       self.max_depth, self.drop_const, float(tol), L.ptr(d01), L.ptr(pts),
                                       L.stream_ptr()), "dg_inv_to_xyz")
         return (pts, d01) if return_depth else pts
+
+    def points_to_depth(self, xyz, drop_value=1, tol=1e-8, tau=2, *, counts=None, return_index=False):
+        """utils/lidar.py:70-107 (with `normalize_minmax` where line 104 calls a `minmax_norm` that does not exist).
+        xyz [B,N,3] or [B,N,4] records (x, y, z[, anything]) in unit space (metres / max_depth), in any order ->
+        (depth_2d [B,1,H,W] float32 normalised depth, drop_value where no point fell; valid [B,1,H,W] bool), and idx [B,N]
+        int32 with return_index (the pixel of every point, -1 for a point that took no part).  counts [B]: cloud b is
+        xyz[b, :counts[b]], the records behind it are not read.  `tol` is unused, as in the reference.  The image does not
+        depend on the order of the points (integer sums); no azimuth wrap-around (dg_points_to_depth)."""
+        if self.angle is None:
+            raise RuntimeError(f"no angle grid: {self.angle_file!r} does not exist (utils/lidar.py:120)")
+        if not (isinstance(xyz, torch.Tensor) and xyz.is_cuda):
+            raise RuntimeError("points_to_depth runs on the GPU only (no CPU fallback)")
+        if xyz.ndim != 3 or xyz.shape[2] not in (3, 4) or xyz.shape[0] < 1 or xyz.shape[1] < 1:
+            raise ValueError(f"points_to_depth: expected [B,N,3] or [B,N,4] records, got {tuple(xyz.shape)}")
+        if not 0.0 <= float(tau) <= TAU_MAX:   # (a NaN fails both)
+            raise ValueError(f"points_to_depth: tau must lie in [0, {TAU_MAX:g}] (the fixed-point sums' resolution), got {tau}")
+        x = xyz.contiguous().float()
+        B, N, stride = x.shape
+        H, W = self.H, self.W
+        if N > MAX_POINTS or H * W > MAX_POINTS:
+            raise ValueError(f"points_to_depth: at most {MAX_POINTS} points per cloud and pixels per image, got {N} and {H * W}")
+        if counts is not None:
+            if tuple(counts.shape) != (B,):
+                raise ValueError(f"points_to_depth: counts must be [B] = [{B}], got {tuple(counts.shape)}")
+            counts = counts.to(device=x.device, dtype=torch.int32).contiguous()
+        if self.angle.device != x.device:
+            self.to(x.device)
+        depth = torch.empty(B, 1, H, W, dtype=torch.float32, device=x.device)
+        valid = torch.empty(B, 1, H, W, dtype=torch.bool, device=x.device)
+        idx = torch.empty(B, N, dtype=torch.int32, device=x.device) if return_index else None
+        acc = _workspace(x.device, B * H * W * 2)
+        try:
+            L.check(L.lib().dg_points_to_depth(L.ptr(x), N * stride, stride, L.ptr(counts), B, N, L.ptr(self.angle), H, W,
+                                               self.min_depth, self.max_depth, float(tau), float(drop_value), L.ptr(acc),
+                                               L.ptr(depth), L.ptr(valid), L.ptr(idx), L.stream_ptr()), "dg_points_to_depth")
+        except BaseException:
+            acc.zero_()   # (a failure between the two launches must not leave sums behind: the words are zero at rest)
+            raise
+        return (depth, valid, idx) if return_index else (depth, valid)
 
 
 def unit_map(x, mode):

@@ -830,6 +830,30 @@ int dg_latent_walk(const float* z0, const float* z1, int n, int nz, int mode, fl
 int dg_export_points(const float* inv, const float* angle, int B, int H, int W, int from_tanh, float min_depth,
                      float max_depth, float drop_const, float tol, int* chunk_counts, float* out, int* counts, void* stream);
 
+/* ---- an arbitrary point cloud onto the range image (utils/lidar.py:70-107; csrc/points_depth.hip) -----
+ * dg_points_to_depth: Coordinate.points_to_depth.  rec: B clouds of N records of `stride` (3 or 4) floats, rec_sb floats
+ * between clouds (>= N stride), record = (x, y, z[, anything]) in UNIT space (metres / max_depth): KITTI (x, y, z, r)
+ * records go in where they lie.  counts [B] int32 (nullable = N everywhere; clamped to [0, N]): records at and beyond
+ * counts[b] are not read.  angle [2,H,W] fp32 (elevation, azimuth).  Per point d_u = |xyz|, d_m = d_u max_depth, w =
+ * exp(-tau d_u) [min_depth < d_m < max_depth] (both strict), u = atan2(z, hypot(x, y)), v = atan2(y, x), id = the pixel
+ * minimising (u - U)^2 + (v - V)^2 over all H W pixels, the LOWEST index on a tie (strict `<` over ascending indices);
+ * the distance is formed from differences in fp32, the per-point quantities in double.  NO AZIMUTH WRAP-AROUND, as in the
+ * reference: a pixel row ends half a pixel from +-pi, so a point across the seam is still nearest to the row's end pixel on
+ * its own side.  Per pixel depth_2d = sum w d_m / (sum w + 1e-8), valid = depth_2d != 0, depth [B,H,W] fp32 = (depth_2d -
+ * min_depth) / (max_depth - min_depth) where valid and drop_value elsewhere; valid [B,H,W] bytes 0 / 1.  (The reference's
+ * line 104 calls a `minmax_norm` that does not exist; `normalize_minmax` is what is built.)  A point with a non-finite
+ * coordinate takes no part, nor does the origin.  idx [B,N] int32 (nullable): the pixel of every point, -1 for one that
+ * took no part (out of range, non-finite, at or beyond counts[b]).
+ * acc: caller-owned u64 words [B,H W,2] = (sum w d_u, sum w) in 24.40 fixed point (dg_fix40), ZERO AT REST: all zeros
+ * before the call, zeroed again by its second launch.  Integer atomics: depth, valid and idx are bit-identical for any
+ * permutation of the points (idx permuted with them), eager or replayed from a graph.  Two launches (search + sums; finish).
+ * Limits: H W <= 2^18 and N <= 2^18 (DG_EUNSUPPORTED above: the codec's range, as dg_chamfer_nn); 0 <= tau <= 16 (w >=
+ * e^-16 = 2^-23, 17 bits above the 2^-40 quantum), 0 <= min_depth < max_depth finite, stride 3 or 4, B <= 65535, no NULL
+ * but counts and idx: DG_EINVAL, nothing launched. */
+int dg_points_to_depth(const float* rec, long rec_sb, int stride, const int* counts, int B, int N, const float* angle, int H,
+                       int W, double min_depth, double max_depth, double tau, float drop_value, unsigned long long* acc,
+                       float* depth, unsigned char* valid, int* idx, void* stream);
+
 const char* dg_version(void);
 
 #ifdef __cplusplus
