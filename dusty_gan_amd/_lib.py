@@ -234,6 +234,7 @@ PROTOTYPES = {
     "dg_inv_chamfer_grad": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _L, _F, _F, _I, _P, _I, _P,
                             _I, _P, _P, _I, _P, _P],
     "dg_sphere_adam": [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _I, _U64, _U64, _I, _P],
+    "dg_sphere_adam_rows": [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _I, _U64, _U64, _I, _I, _P],
     "dg_depth_metrics": [_P, _P, _P, _P, _I, _I, _F, _I, _L, _F, _F, _P, _P],
     "dg_feat_compose": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "dg_feat_compose_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -245,6 +246,9 @@ PROTOTYPES = {
     "dg_latent_walk": [_P, _P, _I, _I, _I, _P, _P],
     "dg_export_points": [_P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P],
     "dg_points_to_depth": [_P, _L, _I, _P, _I, _I, _P, _I, _I, _D, _D, _D, _F, _P, _P, _P, _P, _P],
+    "dg_pixel_winner": [_P, _L, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "dg_raydrop_keep": [_P, _I, _P, _P, _U64, _U64, _U64, _F, _F, _I, _I, _I, _I, _P, _P, _P],
+    "dg_raydrop_gather": [_P, _L, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
 }
 
 _lib = None

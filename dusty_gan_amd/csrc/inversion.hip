@@ -235,6 +235,7 @@ struct SphereArgs {
   int perturb;
   uint64_t seed, stream;
   int prime;
+  int row0;   // the perturbation's row key of row 0 (dg_sphere_adam_rows: a scan's dataset index; 0 otherwise)
 };
 
 __global__ __launch_bounds__(SA_THREADS) void sphere_adam_kernel(SphereArgs a) {
@@ -291,7 +292,7 @@ __global__ __launch_bounds__(SA_THREADS) void sphere_adam_kernel(SphereArgs a) {
     float z = x[e];
     if (a.perturb) {
       const float n = a.noise_in ? a.noise_in[(long)b * a.nz + j]
-                                 : str * latent_normal(a.seed, a.stream, kz, b, j, a.nz);
+                                 : str * latent_normal(a.seed, a.stream, kz, a.row0 + b, j, a.nz);
       z = z + n;
     }
     if (a.z_bf16) ((bf16*)a.zT)[(long)b * a.nz + j] = (bf16)z;
@@ -440,11 +441,12 @@ int dg_inv_chamfer_grad(const float* P, const float* R, const float* d1, const f
   return DG_OK;
 }
 
-int dg_sphere_adam(const float* grad, long g_sb, long g_sk, float* latent, float* m, float* v, unsigned long long* step_dev,
-                   unsigned* ticket, const float* noise_in, void* zT, int z_dtype, int B, int nz, const float* sched,
-                   int num_step, float beta1, float beta2, float eps, int perturb, uint64_t seed, uint64_t stream_id, int prime,
-                   void* s_) {
-  if (!latent || !step_dev || !zT || !sched || B <= 0 || nz <= 0 || num_step <= 0) return DG_EINVAL;
+// row b's perturbation is keyed as row row0 + b (dg_sphere_adam: row0 = 0)
+int dg_sphere_adam_rows(const float* grad, long g_sb, long g_sk, float* latent, float* m, float* v, unsigned long long* step_dev,
+                        unsigned* ticket, const float* noise_in, void* zT, int z_dtype, int B, int nz, const float* sched,
+                        int num_step, float beta1, float beta2, float eps, int perturb, uint64_t seed, uint64_t stream_id,
+                        int prime, int row0, void* s_) {
+  if (row0 < 0 || !latent || !step_dev || !zT || !sched || B <= 0 || nz <= 0 || num_step <= 0) return DG_EINVAL;
   if (!prime && (!grad || !m || !v || !ticket)) return DG_EINVAL;
   if (z_dtype != DG_F32 && z_dtype != DG_BF16) return DG_EINVAL;
   if (nz > SA_THREADS * SA_PER) return DG_EUNSUPPORTED;
@@ -453,10 +455,18 @@ int dg_sphere_adam(const float* grad, long g_sb, long g_sk, float* latent, float
   a.latent = latent; a.m = m; a.v = v; a.step = step_dev; a.ticket = ticket; a.noise_in = noise_in;
   a.zT = zT; a.z_bf16 = z_dtype == DG_BF16; a.B = B; a.nz = nz;
   a.sched = sched; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.num_step = num_step;
-  a.perturb = perturb; a.seed = seed; a.stream = stream_id; a.prime = prime;
+  a.perturb = perturb; a.seed = seed; a.stream = stream_id; a.prime = prime; a.row0 = row0;
   sphere_adam_kernel<<<B, SA_THREADS, 0, (hipStream_t)s_>>>(a);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
+}
+
+int dg_sphere_adam(const float* grad, long g_sb, long g_sk, float* latent, float* m, float* v, unsigned long long* step_dev,
+                   unsigned* ticket, const float* noise_in, void* zT, int z_dtype, int B, int nz, const float* sched,
+                   int num_step, float beta1, float beta2, float eps, int perturb, uint64_t seed, uint64_t stream_id, int prime,
+                   void* s_) {
+  return dg_sphere_adam_rows(grad, g_sb, g_sk, latent, m, v, step_dev, ticket, noise_in, zT, z_dtype, B, nz, sched, num_step, beta1,
+                             beta2, eps, perturb, seed, stream_id, prime, 0, s_);
 }
 
 int dg_depth_metrics(const float* inv_ref, const float* inv_gen, const float* mask, const float* keep, int kc,

@@ -29,6 +29,7 @@
 //     discontinuity, and per point it is a few hundred flops against 5 H W in the search.
 //   * finish : ratio, valid, normalised depth, drop_value fill; zeroes the words (ZERO AT REST, as dg_splat_accum's).
 #include "common.h"
+#include "points_body.h"
 
 namespace {
 
@@ -42,18 +43,7 @@ constexpr int PD_MC = 512;                    // pixels per LDS chunk (4 KB), tw
 constexpr int PD_LD = PD_MC / PD_THREADS;     // chunk pixels loaded per thread
 #define PD_MAX (1l << 18)                     // points per cloud (dg_fix40's range analysis) and pixels per image
 
-// one record -> does the point take part?  (u, v) as the search uses them; wd = w d_u and w as the sums take them
-__device__ __forceinline__ bool pd_point(const float* __restrict__ rec, double min_depth, double max_depth, double tau, float& u,
-                                         float& v, double& wd, double& w) {
-  const double x = (double)rec[0], y = (double)rec[1], z = (double)rec[2];
-  const double r2 = x * x + y * y, d_u = sqrt(r2 + z * z), d_m = d_u * max_depth;
-  if (!(d_m > min_depth && d_m < max_depth)) return false;   // non-finite coordinates and the origin fail here too
-  u = (float)atan2(z, sqrt(r2));
-  v = (float)atan2(y, x);
-  w = exp(-tau * d_u);
-  wd = w * d_u;
-  return true;
-}
+// (pd_point, the per-point body, lives in points_body.h: raydrop.hip's pixel winner shares it)
 
 __global__ __launch_bounds__(PD_THREADS) void points_search_kernel(const float* __restrict__ rec, long rec_sb, int stride,
                                                                    const int* __restrict__ counts, int N,

@@ -38,6 +38,36 @@ static int fill_counter_adds(CounterAdds& a, unsigned long long* const* counters
   return DG_OK;
 }
 
+// ---- GumbelSigmoid.logistic_noise (models/dusty.py:30-36) straight from the generator: element o of U1 is word o & 3 of Philox
+//      counter offset + o / 4, U2 the same (n + 3) / 4 counters further - exactly what two uniform fills of n elements followed
+//      by dg_logistic_noise produce, in one launch and without the two 4 n-byte round trips.  philox_logistic4: the four
+//      elements of group i in registers (step_inputs.hip's draws store them; raydrop.hip's keep kernel consumes them in place).
+__device__ __forceinline__ void philox_logistic4(uint64_t seed, uint64_t stream, uint64_t offset, float eps, long n, long i,
+                                                 float (&v)[4]) {
+  const uint64_t n4 = (uint64_t)((n + 3) / 4);
+  uint32_t r1[4], r2[4];
+  philox4x32_10(seed, offset + (uint64_t)i, stream, r1);
+  philox4x32_10(seed, offset + n4 + (uint64_t)i, stream, r2);
+  const float s24 = 1.f / 16777216.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float u1 = (float)(r1[j] >> 8) * s24, u2 = (float)(r2[j] >> 8) * s24;
+    v[j] = -logf(logf(u1 + eps) / logf(u2 + eps) + eps);
+  }
+}
+__device__ __forceinline__ void philox_logistic_body(uint64_t seed, uint64_t stream, uint64_t offset, float eps, long n,
+                                                     float* __restrict__ out, long i) {
+  if (4 * i >= n) return;
+  float v[4];
+  philox_logistic4(seed, stream, offset, eps, n, i, v);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const long o = 4 * i + j;
+    if (o >= n) break;
+    out[o] = v[j];
+  }
+}
+
 // ---- fetch_reals (trainers/dcgan_amp.py:154-160; utils/lidar.py:31-36; utils/__init__.py:70-73)
 __device__ __forceinline__ float fetch_real_px(float pol, float m, float min_d, float max_d, float drop_const) {
   const float depth = pol * (max_d - min_d) + min_d;

@@ -57,25 +57,7 @@ __global__ void philox_fill_dev_kernel(uint64_t seed, uint64_t stream, const uns
   philox_fill_body(seed, stream, draw_offset(offp, base), kind, lo, hi, ilo, ihi, n, out, nullptr,
                    (long)blockIdx.x * blockDim.x + threadIdx.x);
 }
-// GumbelSigmoid.logistic_noise (models/dusty.py:30-36) straight from the generator: element o of U1 is word o & 3 of Philox
-// counter offset + o / 4, U2 the same (n + 3) / 4 counters further - exactly what two uniform fills of n elements followed
-// by dg_logistic_noise produce, in one launch and without the two 4 n-byte round trips
-__device__ __forceinline__ void philox_logistic_body(uint64_t seed, uint64_t stream, uint64_t offset, float eps, long n,
-                                                     float* __restrict__ out, long i) {
-  if (4 * i >= n) return;
-  const uint64_t n4 = (uint64_t)((n + 3) / 4);
-  uint32_t r1[4], r2[4];
-  philox4x32_10(seed, offset + (uint64_t)i, stream, r1);
-  philox4x32_10(seed, offset + n4 + (uint64_t)i, stream, r2);
-  const float s24 = 1.f / 16777216.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const long o = 4 * i + j;
-    if (o >= n) break;
-    const float u1 = (float)(r1[j] >> 8) * s24, u2 = (float)(r2[j] >> 8) * s24;
-    out[o] = -logf(logf(u1 + eps) / logf(u2 + eps) + eps);
-  }
-}
+// (philox_logistic_body, GumbelSigmoid.logistic_noise straight from the generator: step_inputs.h - raydrop.hip draws with it too)
 __global__ void philox_logistic_dev_kernel(uint64_t seed, uint64_t stream, const unsigned long long* __restrict__ offp,
                                            float eps, long n, float* __restrict__ out) {
   philox_logistic_body(seed, stream, *offp, eps, n, out, (long)blockIdx.x * blockDim.x + threadIdx.x);

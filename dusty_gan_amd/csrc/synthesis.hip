@@ -4,21 +4,18 @@
 //     the dot product are reduced once, then the rows are written.
 //   * export_count_kernel / export_points_kernel : generated inverse depth -> one KITTI record (x, y, z, 0) in metres per
 //     VALID pixel, packed in row-major pixel order per scan: an ordered stream compaction fused behind the pixel body of
-//     inv_to_xyz (inv_point.h).  Two launches and no waiting between workgroups: the first counts the valid pixels of every
-//     chunk of DG_EXPORT_CHUNK consecutive pixels; the second recomputes validity, sums the counts of the chunks before
-//     its own, ranks its pixels with a wave ballot and a scan of the wave totals in LDS, and stores each record with one
-//     16-byte store at its final place.  No atomics: the bytes do not depend on the order workgroups run in.
+//     inv_to_xyz (inv_point.h).  Two launches and no waiting between workgroups (the compaction itself: compact.h): the
+//     first counts the valid pixels of every chunk of DG_EXPORT_CHUNK consecutive pixels; the second recomputes validity,
+//     sums the counts of the chunks before its own, ranks its pixels with a wave ballot and a scan of the wave totals in
+//     LDS, and stores each record with one 16-byte store at its final place.  No atomics: the bytes do not depend on the
+//     order workgroups run in.
 //     HBM traffic: 4 B of depth per pixel in each launch (the second read is L2-warm at the sizes of a batch), 8 B of
 //     angles per VALID pixel (at most per pixel), 16 B written per kept point.
 #include "common.h"
+#include "compact.h"
 #include "inv_point.h"
 
 namespace {
-
-constexpr int EXP_THREADS = 256;
-constexpr int EXP_ITERS = DG_EXPORT_CHUNK / EXP_THREADS;   // a thread's pixels of a chunk, EXP_THREADS apart
-constexpr int EXP_SEGS = DG_EXPORT_CHUNK / 64;             // the chunk's runs of 64 consecutive pixels (one wave ballot each)
-static_assert(DG_EXPORT_CHUNK % EXP_THREADS == 0 && EXP_THREADS % 64 == 0, "a chunk is whole waves of consecutive pixels");
 
 // the sum of v over the workgroup's 256 threads, in a fixed order (every thread gets it)
 __device__ __forceinline__ double block_sum256(double v, double* red) {
@@ -76,88 +73,44 @@ __global__ __launch_bounds__(256) void latent_walk_kernel(const float* __restric
 }
 
 // launch 1: chunk_counts[b][c] = the valid pixels among pixels [c CHUNK, min((c + 1) CHUNK, hw)) of scan b
-__global__ __launch_bounds__(EXP_THREADS) void export_count_kernel(const float* __restrict__ in, long hw, long nchunk,
-                                                                   int from_tanh, float drop_const, float tol,
-                                                                   int* __restrict__ chunk_counts) {
-  __shared__ int wsum[EXP_THREADS / 64];
-  const int tid = threadIdx.x;
+__global__ __launch_bounds__(CP_THREADS) void export_count_kernel(const float* __restrict__ in, long hw, long nchunk,
+                                                                  int from_tanh, float drop_const, float tol,
+                                                                  int* __restrict__ chunk_counts) {
   const long b = (long)blockIdx.x / nchunk, c = (long)blockIdx.x % nchunk;
   const float* src = in + b * hw;
-  int cnt = 0;   // wave-uniform
-#pragma unroll
-  for (int k = 0; k < EXP_ITERS; ++k) {
-    const long px = c * DG_EXPORT_CHUNK + k * EXP_THREADS + tid;
-    const bool v = px < hw && dg_inv_valid(dg_inv01(src[px < hw ? px : 0], from_tanh), drop_const, tol);
-    cnt += __popcll(__ballot(v));
-  }
-  if ((tid & 63) == 0) wsum[tid >> 6] = cnt;
-  __syncthreads();
-  if (tid == 0) {
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < EXP_THREADS / 64; ++w) s += wsum[w];
-    chunk_counts[blockIdx.x] = s;
-  }
+  cp_count_chunk(c, [&](int, long px) { return px < hw && dg_inv_valid(dg_inv01(src[px < hw ? px : 0], from_tanh), drop_const, tol); },
+                 chunk_counts + blockIdx.x);
 }
 
 // launch 2: the records of chunk c of scan b, placed behind those of the chunks before it
-__global__ __launch_bounds__(EXP_THREADS) void export_points_kernel(const float* __restrict__ in,
-                                                                    const float* __restrict__ angle, long hw, long nchunk,
-                                                                    int from_tanh, float min_d, float max_d, float drop_const,
-                                                                    float tol, const int* __restrict__ chunk_counts,
-                                                                    float4* __restrict__ out, int* __restrict__ counts) {
-  __shared__ int wpre[EXP_THREADS / 64];
-  __shared__ int seg[EXP_SEGS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+__global__ __launch_bounds__(CP_THREADS) void export_points_kernel(const float* __restrict__ in,
+                                                                   const float* __restrict__ angle, long hw, long nchunk,
+                                                                   int from_tanh, float min_d, float max_d, float drop_const,
+                                                                   float tol, const int* __restrict__ chunk_counts,
+                                                                   float4* __restrict__ out, int* __restrict__ counts) {
   const long b = (long)blockIdx.x / nchunk, c = (long)blockIdx.x % nchunk;
-  // the points of this scan's earlier chunks (read-only data of the finished first launch: nothing to wait for)
-  int before = 0;
-  for (long c2 = tid; c2 < c; c2 += EXP_THREADS) before += chunk_counts[b * nchunk + c2];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o);
-  if (lane == 0) wpre[wave] = before;
-
   const float* src = in + b * hw;
-  float4 rec[EXP_ITERS];
-  bool valid[EXP_ITERS];
-  int rank[EXP_ITERS];   // the valid pixels before this one in its run of 64
-#pragma unroll
-  for (int k = 0; k < EXP_ITERS; ++k) {
-    const long px = c * DG_EXPORT_CHUNK + k * EXP_THREADS + tid;
-    float inv = 0.f;
-    valid[k] = false;
-    if (px < hw) {
-      inv = dg_inv01(src[px], from_tanh);
-      valid[k] = dg_inv_valid(inv, drop_const, tol);
-    }
-    rec[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (valid[k]) {
-      float x, y, z;
-      dg_inv_point(inv, true, min_d, max_d, angle[px], angle[hw + px], x, y, z);
-      rec[k] = make_float4(x * max_d, y * max_d, z * max_d, 0.f);   // metres; reflectance 0
-    }
-    const unsigned long long m = __ballot(valid[k]);
-    rank[k] = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) seg[k * (EXP_THREADS / 64) + wave] = __popcll(m);   // run k * 4 + wave starts at pixel k * 256 + wave * 64
-  }
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int w = 0; w < EXP_THREADS / 64; ++w) base += wpre[w];
   float4* dst = out + b * hw;
-#pragma unroll
-  for (int k = 0; k < EXP_ITERS; ++k) {
-    const int s = k * (EXP_THREADS / 64) + wave;
-    int pre = base;
-    for (int t = 0; t < s; ++t) pre += seg[t];
-    if (valid[k]) dst[pre + rank[k]] = rec[k];   // pre + rank < the scan's count <= hw
-  }
-  if (c == nchunk - 1 && tid == 0) {
-    int total = base;
-#pragma unroll
-    for (int t = 0; t < EXP_SEGS; ++t) total += seg[t];
-    counts[b] = total;
-  }
+  float4 rec[CP_ITERS];
+  cp_place_chunk(
+      chunk_counts + b * nchunk, c,
+      [&](int k, long px) {
+        float inv = 0.f;
+        bool valid = false;
+        if (px < hw) {
+          inv = dg_inv01(src[px], from_tanh);
+          valid = dg_inv_valid(inv, drop_const, tol);
+        }
+        rec[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (valid) {
+          float x, y, z;
+          dg_inv_point(inv, true, min_d, max_d, angle[px], angle[hw + px], x, y, z);
+          rec[k] = make_float4(x * max_d, y * max_d, z * max_d, 0.f);   // metres; reflectance 0
+        }
+        return valid;
+      },
+      [&](int k, int pos) { dst[pos] = rec[k]; },   // pos < the scan's count <= hw
+      c == nchunk - 1 ? counts + b : nullptr);
 }
 
 }  // namespace
@@ -178,9 +131,9 @@ int dg_export_points(const float* inv, const float* angle, int B, int H, int W, 
   const long hw = (long)H * W, nchunk = (hw + DG_EXPORT_CHUNK - 1) / DG_EXPORT_CHUNK;
   if (hw > 0x7fffffffL || (long)B * nchunk > 0x7fffffffL) return DG_EINVAL;   // int32 counts; one workgroup per chunk
   const int grid = (int)((long)B * nchunk);
-  export_count_kernel<<<grid, EXP_THREADS, 0, (hipStream_t)s_>>>(inv, hw, nchunk, from_tanh, drop_const, tol, chunk_counts);
+  export_count_kernel<<<grid, CP_THREADS, 0, (hipStream_t)s_>>>(inv, hw, nchunk, from_tanh, drop_const, tol, chunk_counts);
   HIP_CHECK_RET(hipGetLastError());
-  export_points_kernel<<<grid, EXP_THREADS, 0, (hipStream_t)s_>>>(inv, angle, hw, nchunk, from_tanh, min_depth, max_depth,
+  export_points_kernel<<<grid, CP_THREADS, 0, (hipStream_t)s_>>>(inv, angle, hw, nchunk, from_tanh, min_depth, max_depth,
                                                                  drop_const, tol, chunk_counts,
                                                                  reinterpret_cast<float4*>(out), counts);
   HIP_CHECK_RET(hipGetLastError());

@@ -240,18 +240,21 @@ def _cloud_rows(path):
     return n, cols
 
 
-def read_clouds(paths, max_depth, device=None):
+def read_clouds(paths, max_depth, device=None, *, return_raw=False):
     """cloud files -> (records [B,Nmax,4] float32 in UNIT space (metres / max_depth; column 3 as stored, 0 for N x 3 files),
     counts [B] int32) on `device`: what LiDAR.points_to_depth takes with counts=.  A file is a KITTI `.bin` (N x 4
     little-endian float32, metres) or a `.npy` of shape N x 3 or N x 4 (metres).  Clouds shorter than the longest are padded
     with zero records, which points_to_depth does not read.  An empty file, a `.bin` whose size is not a multiple of 16 bytes
-    or a `.npy` of another shape raises RawScanError naming the file."""
+    or a `.npy` of another shape raises RawScanError naming the file.  return_raw: a third result, the same records in METRES
+    as the files hold them, bit for bit (raydrop.gather copies its output from them: dividing and multiplying back would not
+    be exact)."""
     paths = [os.fspath(p) for p in paths]
     if not paths:
         raise FileNotFoundError("read_clouds: no cloud files")
     shapes = [_cloud_rows(p) for p in paths]
     counts = np.array([n for n, _ in shapes], dtype=np.int32)
     records = np.zeros((len(paths), int(counts.max()), 4), dtype=np.float32)
+    raw = np.zeros_like(records) if return_raw else None
     for b, (path, (n, cols)) in enumerate(zip(paths, shapes)):
         if not path.endswith(".npy"):
             _read_bin_into(path, records[b, :n])
@@ -261,9 +264,12 @@ def read_clouds(paths, max_depth, device=None):
             xyz = np.empty((n, 3), dtype=np.float32)
             _read_npy_into(path, xyz)
             records[b, :n, :3] = xyz
+        if raw is not None:
+            raw[b, :n] = records[b, :n]
         records[b, :n, :3] /= np.float32(max_depth)
     dev = _device(device)
-    return torch.from_numpy(records).to(dev), torch.from_numpy(counts).to(dev)
+    res = (torch.from_numpy(records).to(dev), torch.from_numpy(counts).to(dev))
+    return res + (torch.from_numpy(raw).to(dev),) if return_raw else res
 
 
 class _ProjSlot:

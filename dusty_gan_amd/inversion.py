@@ -20,7 +20,7 @@ from . import _lib as L
 from . import engine as E
 
 # Philox stream ids of the inversion's own draws (the model's and the trainer's generators use 0-9); 14 is the target
-# corruptions' (corruption.STREAM_CORRUPT)
+# corruptions' (corruption.STREAM_CORRUPT), 15 the ray-drop transfer's (raydrop.STREAM_RAYDROP)
 STREAM_LATENT, STREAM_PERTURB, STREAM_GUMBEL = 11, 12, 13
 
 
@@ -43,11 +43,11 @@ def normalize_rows(latent):
     return latent.div_(latent.pow(2).mean(dim=1, keepdim=True).add(1e-9).sqrt())
 
 
-def _draw_normal(seed, stream_id, n, device):
-    """n standard normals of Philox (seed, stream_id) from counter 0 (dg_philox_fill kind 1).  No device counter: a
+def _draw_normal(seed, stream_id, n, device, offset=0):
+    """n standard normals of Philox (seed, stream_id) from counter `offset` (dg_philox_fill kind 1).  No device counter: a
     utils.rng.Philox would queue its advance with whatever trainer's counter queue is current."""
     out = torch.empty(n, dtype=torch.float32, device=device)
-    L.check(L.lib().dg_philox_fill(seed, stream_id, 0, 1, 0.0, 1.0, 0, 1, n, L.ptr(out), L.stream_ptr()), "dg_philox_fill")
+    L.check(L.lib().dg_philox_fill(seed, stream_id, int(offset), 1, 0.0, 1.0, 0, 1, n, L.ptr(out), L.stream_ptr()), "dg_philox_fill")
     return out
 
 
@@ -211,8 +211,9 @@ class InvState:
     num_code = 1
 
     def __init__(self, inv_ref, mask_ref, latent, gumbel, *, num_step, distance, lr, perturb_latent, noise_ratio,
-                 noise_sigma, lr_rampup_ratio, lr_rampdown_ratio, seed, lidar=None, tol=1e-8):
+                 noise_sigma, lr_rampup_ratio, lr_rampdown_ratio, seed, lidar=None, tol=1e-8, row0=0):
         dev = inv_ref.device
+        self.row0 = int(row0)   # the perturbation's row key of latent row 0
         B, _, H, W = inv_ref.shape
         self.B, self.HW = B, H * W
         self.ref = inv_ref.detach().float().contiguous()
@@ -270,15 +271,16 @@ class InvState:
         B, nz = self.latent.shape
         Bp = dzT.shape[1] if dzT is not None else 0
         ns, b1, b2, eps, pert, seed, sid = self.hp
-        L.check(L.lib().dg_sphere_adam(L.ptr(dzT), 1, Bp, L.ptr(self.latent), L.ptr(self.m), L.ptr(self.v), L.ptr(self.step),
-                                       L.ptr(self.ticket), L.ptr(self.noise_in), L.ptr(zT), z_dtype, B, nz, L.ptr(self.sched),
-                                       ns, b1, b2, eps, pert, seed, sid, int(prime), L.stream_ptr()), "dg_sphere_adam")
+        L.check(L.lib().dg_sphere_adam_rows(L.ptr(dzT), 1, Bp, L.ptr(self.latent), L.ptr(self.m), L.ptr(self.v), L.ptr(self.step),
+                                            L.ptr(self.ticket), L.ptr(self.noise_in), L.ptr(zT), z_dtype, B, nz, L.ptr(self.sched),
+                                            ns, b1, b2, eps, pert, seed, sid, int(prime), self.row0, L.stream_ptr()),
+                "dg_sphere_adam_rows")
 
 
 def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, perturb_latent=True, noise_ratio=0.75,
            noise_sigma=1.0, lr_rampup_ratio=0.05, lr_rampdown_ratio=0.25, seed=0, latent=None, graph=True,
            noise_fn=None, gumbel_noise=None, on_step=None, lidar=None, tol=1e-8, num_code=1, composition_layer=None,
-           alpha=None, alpha_lr=1e-3):
+           alpha=None, alpha_lr=1e-3, first_index=0):
     """Reconstruct inv_ref [B,1,H,W] (inverse depth in [0,1]) under mask_ref [B,1,H,W] by optimising G's latent
     (evaluate_reconstruction.py:84-118).  G: what utils.setup returns (the bare 'none' generator or a DUSty1 / DUSty2
     wrapper), run in eval mode at its own precision; nothing of G is modified.
@@ -301,6 +303,9 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
     on_step is called as on_step(k, loss [B], dlatent [B,N,nz], latent, dalpha [B,N,C], alpha).  "loss", "out" and "inv_gen" stay
     per scan.  With num_code = 1 the three other arguments must stay at their defaults (ValueError).
     The reference runs ONE scan (B = 1) under torch.manual_seed(0); B > 1 here is B independent such problems in one batch.
+    first_index: the dataset index of the batch's first scan.  Scan b draws its default initial latent and its perturbations as
+    latent row(s) (first_index + b) N .. of one long batch, so a scan keyed by its index draws the same numbers in whatever
+    batch it travels (0: the batch's own rows; above 0 the default latent needs N nz % 4 == 0, a Philox group per 4 elements).
     The lower layers run at batch B N, at most 4096 per call (ValueError): GEngine.alloc holds per lower sample the
     feature maps a0..a3 and their gradients (2 x 1 966 080 elements at 64 x 1024 with 512 / 256 / 128 / 64 channels: 7.9 MB in
     bf16, 15.7 MB in fp32) plus the head's buffers (gout, draw, mask, depth, in bf16 the pixel-major gradient and a3's mask bits:
@@ -322,8 +327,14 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
     eng, st = bb.engine(), bb.store
     if N > 1 and eng.x2_asked:
         raise NotImplementedError("multi-code inversion is not built for the fp32x3 split storage (x2)")
+    first_index = int(first_index)
+    if first_index < 0 or (first_index + B) * N >= 2**31:
+        raise ValueError(f"first_index: 0 <= (first_index + B) num_code < 2^31, got {first_index}")
     if latent is None:
-        latent = _draw_normal(int(seed) & (2**64 - 1), STREAM_LATENT, B * N * bb.in_ch, dev).view(B * N, bb.in_ch)
+        if first_index and (N * bb.in_ch) % 4:
+            raise ValueError("first_index > 0 draws the default latent per scan: num_code * nz must be a multiple of 4")
+        latent = _draw_normal(int(seed) & (2**64 - 1), STREAM_LATENT, B * N * bb.in_ch, dev,
+                              offset=first_index * N * bb.in_ch // 4).view(B * N, bb.in_ch)
         normalize_rows(latent)
     elif N > 1 and tuple(latent.shape) != (B, N, bb.in_ch):
         raise ValueError(f"latent must be [B,N,nz] = {(B, N, bb.in_ch)} with num_code > 1")
@@ -331,7 +342,7 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
     S = InvState(inv_ref, mask_ref, latent, _fixed_gumbel(G, B, H, W, seed, dev, gumbel_noise), num_step=num_step,
                  distance=distance, lr=lr, perturb_latent=perturb_latent, noise_ratio=noise_ratio, noise_sigma=noise_sigma,
                  lr_rampup_ratio=lr_rampup_ratio, lr_rampdown_ratio=lr_rampdown_ratio, seed=seed,
-                 lidar=lidar, tol=tol)
+                 lidar=lidar, tol=tol, row0=first_index * N)
     # every buffer of the loop exists before it, allocated on the caller's stream
     eng.alloc(B, dev)
     low = eng   # the engine the latents enter: the generator's own, or the lower one of a multi-code inversion

@@ -723,6 +723,8 @@ int dg_adam_proj_fused(float* p, float* v, float* ema, void* shadow, int shadow_
  * word pairs as dg_philox_fill kind 1 - or noise_in [B,nz] when given (the perturbation itself, injected).  The last
  * row's workgroup increments *step_dev (ticket [1]: zero on entry, left zero).
  * prime = 1: no optimiser step, only zT for step *step_dev (the first forward).  nz <= 1024.
+ * dg_sphere_adam_rows: the same with the perturbation of row b keyed as row row0 + b (stream word stream_id | (row0 + b) <<
+ * 32; row0 >= 0): a scan keyed by its dataset index draws the same perturbations in any batch.  row0 = 0 is dg_sphere_adam.
  * dg_depth_metrics: compute_depth_error + compute_depth_accuracy (utils/metrics/depth.py) of revert_depth(inv, norm=False)
  * (utils/lidar.py:38-47) of inv_ref / inv_gen [B,HW] under mask [B,HW], and the drop ratios of the evaluation CSV
  * (evaluate_reconstruction.py:138-152): out [B,9] = abs_rel, sq_rel, rmse, rmse_log, accuracy_1..3, drop_gen, drop_ref.
@@ -763,6 +765,10 @@ int dg_sphere_adam(const float* grad, long g_sb, long g_sk, float* latent, float
                    unsigned* ticket, const float* noise_in, void* zT, int z_dtype, int B, int nz, const float* sched,
                    int num_step, float beta1, float beta2, float eps, int perturb, uint64_t seed, uint64_t stream_id, int prime,
                    void* stream);
+int dg_sphere_adam_rows(const float* grad, long g_sb, long g_sk, float* latent, float* m, float* v, unsigned long long* step_dev,
+                        unsigned* ticket, const float* noise_in, void* zT, int z_dtype, int B, int nz, const float* sched,
+                        int num_step, float beta1, float beta2, float eps, int perturb, uint64_t seed, uint64_t stream_id,
+                        int prime, int row0, void* stream);
 int dg_depth_metrics(const float* inv_ref, const float* inv_gen, const float* mask, const float* keep, int kc,
                      int keep_is_depth, float tol, int B, long HW, float min_depth, float max_depth, float* out, void* stream);
 
@@ -853,6 +859,40 @@ int dg_export_points(const float* inv, const float* angle, int B, int H, int W, 
 int dg_points_to_depth(const float* rec, long rec_sb, int stride, const int* counts, int B, int N, const float* angle, int H,
                        int W, double min_depth, double max_depth, double tau, float drop_value, unsigned long long* acc,
                        float* depth, unsigned char* valid, int* idx, void* stream);
+
+/* ---- ray-drop transfer: G's inferred drops applied to the cloud that was inverted (dusty_gan_amd/raydrop.py;
+ * csrc/raydrop.hip).  The paper's use of the measurability head on simulated scans; the reference holds no
+ * code for it.
+ * dg_pixel_winner: win [B,H W] int32 = for every pixel the NEAREST of the points dg_points_to_depth binned into it (idx
+ *   [B,N] as that call returned it; rec / rec_sb / stride / counts as given to it), -1 for a pixel without a point.  Nearest
+ *   by d_u = |xyz| in double on the float32 coordinates (the per-point body of dg_points_to_depth, csrc/points_body.h)
+ *   rounded once to float32; equal rounded ranges: the LOWEST point index.  An idx outside [0, H W) takes no part.  ws:
+ *   caller-owned u64 words [B,H W], ZERO AT REST (all zeros before the call, zeroed again by its second launch); one
+ *   integer atomic max per point on the complemented key (range bits << 32 | index): the same bits for any launch order,
+ *   eager or replayed.  Two launches.  stride 3 or 4, B <= 65535, H W <= 2^31 - 1, no NULL but counts: DG_EINVAL.
+ * dg_raydrop_keep: keep [B,K,H,W] uint8 = win >= 0 && mp && mi for K realisations of the drop.  conf [B,arch,H,W]: G's raw
+ *   confidence logits (arch 1 dusty1: h1; 2 dusty2: h1, h2); mp / mi are head_px_fwd's (csrc/head_post.h) in eval mode:
+ *   mp = sigmoid((h1 + noise) / tau) > 0.5, mi = h2 > 0 (dusty2; 1 otherwise).  noise_in [B,K,H W] when given; NULL:
+ *   GumbelSigmoid.logistic_noise drawn from Philox - for scan first_index + b, realisation k, pixel p the element p of the
+ *   dg_philox_logistic_dev draw of H W elements at counter offset (first_index + b) 2 ceil(H W / 4) with the stream word
+ *   (stream_id | k << 32): the number does not depend on B, on K or on the batch a scan travels in.  stream_id < 2^32.
+ *   noise_out (nullable) [B,K,H W]: the noise used.  With H W % 4 == 0 keep must be 4-byte and noise_out 16-byte aligned.
+ *   One launch.  arch 1 or 2, tau > 0, B and K in 1..65535: else DG_EINVAL.
+ * dg_raydrop_gather: for every (b, k), over the pixels p in row-major order with keep[b,k,p] != 0 and 0 <= win[b,p] < N:
+ *   out_records[b,k,j] = the `stride` 32-bit words of record win[b,p] of rec (ANY buffer of the layout given: the caller's
+ *   records in metres come back unchanged, bit for bit) with column 3 = 0 for stride 3; out_labels[b,k,j] =
+ *   labels[b, win[b,p]] (labels [B,N] uint32 and out_labels both, or neither); out_index[b,k,j] = win[b,p]; j ascending
+ *   from 0; out_counts[b,k] = the number of such pixels.  Outputs are [B,K,H W(,4)]; rows at and beyond the count are not
+ *   written.  chunk_counts: workspace of B K ceil(H W / DG_EXPORT_CHUNK) int32 (need not be initialised).  Two launches, no
+ *   atomics (dg_export_points' ordered compaction): two calls give the same bytes.  out_records 16-byte aligned. */
+int dg_pixel_winner(const float* rec, long rec_sb, int stride, const int* counts, const int* idx, int B, int N, int H, int W,
+                    unsigned long long* ws, int* win, void* stream);
+int dg_raydrop_keep(const float* conf, int arch, const int* win, const float* noise_in, uint64_t seed, uint64_t stream_id,
+                    uint64_t first_index, float eps, float tau, int B, int K, int H, int W, unsigned char* keep,
+                    float* noise_out, void* stream);
+int dg_raydrop_gather(const float* rec, long rec_sb, int stride, int N, const int* win, const unsigned char* keep,
+                      const unsigned* labels, int B, int K, int H, int W, int* chunk_counts, float* out_records,
+                      unsigned* out_labels, int* out_index, int* out_counts, void* stream);
 
 const char* dg_version(void);
 
