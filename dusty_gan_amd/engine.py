@@ -8,7 +8,7 @@ import ctypes as C
 import math
 import os
 import warnings
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import torch
 
@@ -282,8 +282,16 @@ class NetCfg:
         self.arch, self.ring, self.tau, self.drop_const = arch, bool(ring), float(tau), float(drop_const)
         self.nheads = 1 + ARCH_ID[arch]
         self.h0, self.w0 = self.H >> 4, self.W >> 4
+        self.proj_rows = self.h0 * self.w0 * self.ch[3]   # Proj.weight is [proj_rows][nz], rows in (y, x, c) order
+        self.proj_scale = 1.0 / math.sqrt(self.proj_rows)  # ... and its eq-lr scale
         if dis_in_ch != 1:
             raise NotImplementedError("discriminator in_ch != 1 (the range-image path is single channel)")
+
+
+ProjOperands = namedtuple("ProjOperands", "dp0 zT op_dtype nb rows nz scale")
+ProjOperands.__doc__ = """What the optimizer needs to form Proj.weight's gradient itself (FlatAdam.step `fused_proj`,
+dg_adam_proj_fused): scale * dp0^T zT over `nb` samples - gradient rows dp0 [nb][rows], input rows zT [nb][nz], both of
+C-ABI dtype `op_dtype` (| DG_FORCE_FP32X3).  Built by GEngine.proj_operands."""
 
 
 def conv_algorithmic(mode, B, Hc, Wc, K, N, ies, oes, wes, reads_aux, mask_bits=0):
@@ -630,6 +638,13 @@ class Ops:
             b = self._x2_scratch[key] = torch.empty(t.numel(), dtype=torch.float32, device=t.device)
         return b
 
+    def gemm_rows_f32(self, a, g):
+        """the operand pair (a, g) of Proj's weight-gradient GEMM shape (wmode 2) as that shape's kernels take it: they are the
+        fp32 kernels, so a split-bf16 operand goes through an fp32 copy (scratch roles "wa" / "wg")"""
+        a = x2_unpack(a, self._f32_copy("wa", a)) if is_x2(a) else a
+        g = x2_unpack(g, self._f32_copy("wg", g)) if is_x2(g) else g
+        return a, g
+
     @property
     def _f(self):
         """the `force` argument of the C ABI: request code | flag bits"""
@@ -868,11 +883,8 @@ class Ops:
 
     def _wgrad_params(self, wmode, ring, B, Hc, Wc, Ci, Co, a, a_strides, g, g_strides, dw_ptr, scale, rowscale, a_dt, g_dt,
                       a_off, g_off, g_mod):
-        if wmode == 2:   # Proj's GEMM shape runs on the fp32 kernels: split-bf16 operands through fp32 copies
-            if is_x2(a):
-                a = x2_unpack(a, self._f32_copy("wa", a))
-            if is_x2(g):
-                g = x2_unpack(g, self._f32_copy("wg", g))
+        if wmode == 2:   # Proj's GEMM shape runs on the fp32 kernels
+            a, g = self.gemm_rows_f32(a, g)
         if is_x2(a):
             a_dt = L.DG_BF16X2
         if is_x2(g):
@@ -1028,11 +1040,10 @@ class GEngine:
 
     def _proj_fwd(self, st, B, src, dst, tangent=False):
         """Proj (dcgan_eqlr.py:6-16): GEMM [B,nz] x [N',nz]^T, N' = h0*w0*C3 in (y,x,c) order"""
-        c = self.cfg
-        Np = c.h0 * c.w0 * self.chs[0]
+        c, Np = self.cfg, self.cfg.proj_rows
         kw = dict(aux=self.a[0]) if tangent else dict(bias=st.fptr("proj_b"), bias_mod=self.chs[0])
         self.ops.conv(L.MODE_GEMM, 0, 1, B, 1, 1, c.nz, Np, src, (c.nz, 0, 1), dst, (Np, 0, 1), st.sptr("proj_w"),
-                      1.0 / math.sqrt(Np), L.EPI_MASK if tangent else L.EPI_LRELU, **kw)
+                      c.proj_scale, L.EPI_MASK if tangent else L.EPI_LRELU, **kw)
 
     def _fwd(self, st, B, i, src, dst, tangent=False, **head_kw):
         """Up x3 (dcgan_eqlr.py:19-26) / Head (dcgan_eqlr.py:29-46: all heads in one pass, planar fp32 output).  tangent (as in
@@ -1085,10 +1096,13 @@ class GEngine:
     def proj_wgrad(self, st: ParamStore, dp0, zT, nb, accumulate=False):
         """Proj weight gradient dW[n'][k] = s * sum_b dp0[b][n'] z[b][k] over `nb` samples (the local batch, or the
         all-gathered global batch in data-parallel runs: utils/dist.py).  Plain stores unless accumulating."""
-        c = self.cfg
-        Np = c.h0 * c.w0 * c.ch[3]
+        c, Np = self.cfg, self.cfg.proj_rows
         self.ops.wgrad(2, 1, 1, 1, nb, Np, c.nz, dp0, (0, Np, 1), zT, (0, c.nz, 1), st.fptr("proj_w", st.grad),
-                       1.0 / math.sqrt(Np), accumulate=int(accumulate))
+                       c.proj_scale, accumulate=int(accumulate))
+
+    def proj_operands(self, dp0, zT, nb, op_dtype):
+        """the operands of proj_wgrad(st, dp0, zT, nb) for the optimizer to form that gradient itself"""
+        return ProjOperands(dp0, zT, op_dtype, nb, self.cfg.proj_rows, self.cfg.nz, self.cfg.proj_scale)
 
     def backward(self, st: ParamStore, ddepth, accumulate_proj=False, skip_proj=False, data_only=False,
                  chain_first=False, after_chain=None, after_up1=None):
@@ -1194,8 +1208,7 @@ class GEngine:
 
     def grad_z_buffers(self):
         """allocate (once per batch size) grad_z's operand dp0^T, zero-padded to Bp columns, and its result; returns Bp"""
-        c = self.cfg
-        Np = c.h0 * c.w0 * c.ch[3]
+        c, Np = self.cfg, self.cfg.proj_rows
         Bp = (self.ws_B + 63) // 64 * 64
         if self._dzT is None or self._dzT.shape != (Np, Bp) or self._dzT.dtype != self.dtype:
             self._dzT = torch.zeros(Np, Bp, dtype=self.dtype, device=self.dp[0].device)
@@ -1205,9 +1218,7 @@ class GEngine:
     def grad_z_T(self, st: ParamStore):
         """grad_z's result in place: the engine's fixed buffer dz^T [nz][Bp] (Bp = B rounded up to 64; column b = sample b),
         the operand of a replayed step's optimizer (GAN inversion)."""
-        c = self.cfg
-        B = self.ws_B
-        Np = c.h0 * c.w0 * c.ch[3]
+        c, B, Np = self.cfg, self.ws_B, self.cfg.proj_rows
         Bp = self.grad_z_buffers()
         dp0 = x2_unpack(self.dp[0]) if is_x2(self.dp[0]) else self.dp[0]
         self._dzT[:, :B].copy_(dp0.view(B, Np).t())
@@ -1216,7 +1227,7 @@ class GEngine:
         # the kernel splits its reduction over (sample, row) units: present the Np rows as R "samples" of Np / R rows
         R = 512 if Np % (512 * 64) == 0 else 1
         self.ops.wgrad(2, 1, R, 1, Np // R, c.nz, Bp, shadow, ((Np // R) * c.nz, c.nz, 1), self._dzT,
-                       ((Np // R) * Bp, Bp, 1), L.ptr(self._dzw), 1.0 / math.sqrt(Np), accumulate=1)
+                       ((Np // R) * Bp, Bp, 1), L.ptr(self._dzw), c.proj_scale, accumulate=1)
         return self._dzw
 
     def tangent_forward(self, st: ParamStore, v):

@@ -13,6 +13,7 @@ What differs underneath:
   * the path-length regulariser (solver.loss.pl > 0) is a forward-over-reverse pass (Trainer._path_length);
   * scalars are gathered with ONE packed all-reduce and read back lazily.
 """
+import enum
 import math
 import os
 import os.path as osp
@@ -41,6 +42,32 @@ def _world():
 
 def _rank():
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+class ProjRoute(enum.Enum):
+    """How the G phase produces Proj.weight's gradient - 96 % of G's gradient bytes, 268 MB in fp32.
+    in_optimizer: it exists only inside the optimizer's launch (`FlatAdam.regen_grad` materialises it on demand)."""
+    MATERIALISED = "materialised"   # written by the backward pass
+    FUSED = "fused"                 # never written: dg_adam_proj_fused forms it from the local operands
+    GATHER = "gather"               # formed from the all-gathered operands by proj_wgrad
+    GATHER_FUSED = "gather_fused"   # formed from the all-gathered operands inside the optimizer
+    skips_backward = property(lambda self: self is not ProjRoute.MATERIALISED)          # G's backward pass leaves it out
+    gathers = property(lambda self: self in (ProjRoute.GATHER, ProjRoute.GATHER_FUSED))  # its operands travel, not it
+    in_optimizer = property(lambda self: self in (ProjRoute.FUSED, ProjRoute.GATHER_FUSED))
+
+
+def proj_route(*, multi_rank_schedule, n_acc, dtype, proj_first, fuse_ok, fuse_fp32, beta1, profiling):
+    """The route of a G step, from plain values.  multi_rank_schedule: several ranks, or DUSTY_GAN_FORCE_SEG=1; proj_first:
+    the store's first segment is proj_w; fuse_ok: DUSTY_GAN_FUSE_PROJ is on and the optimizer kernel has not refused the
+    shape; fuse_fp32: DUSTY_GAN_FUSE_PROJ_FP32.  Operands are gathered in any dtype, but only bf16 ones are taken by the
+    optimizer's global-batch form; the local form also takes fp32 rows."""
+    if n_acc != 1 or not proj_first:
+        return ProjRoute.MATERIALISED
+    fusable = fuse_ok and beta1 == 0.0 and not profiling
+    if multi_rank_schedule:
+        return ProjRoute.GATHER_FUSED if fusable and dtype == torch.bfloat16 else ProjRoute.GATHER
+    local_ok = fusable and (dtype == torch.bfloat16 or (dtype == torch.float32 and fuse_fp32))
+    return ProjRoute.FUSED if local_ok else ProjRoute.MATERIALISED
 
 
 class LazyScalars(Mapping):
@@ -243,9 +270,9 @@ class FlatAdam:
 
     def step(self, gscale=1.0, ema_store=None, ema_decay=0.0, shadow_dtype=torch.float32, fused_proj=None, between=None,
              extra=None, sole=False):
-        """fused_proj = (dp0, zT, op_dtype, nb, Np, K, wscale): the first segment of the store is Proj.weight [Np][K] and
-        its gradient is NOT in st.grad - the kernel forms wscale * dp0^T zT itself (dg_adam_proj_fused).  Returns
-        False (and does nothing) if that kernel refuses the shape, so the caller can fall back.
+        """fused_proj (engine.ProjOperands, or a plain tuple in its field order): the first segment of the store is
+        Proj.weight [rows][nz] and its gradient is NOT in st.grad - the kernel forms scale * dp0^T zT itself
+        (dg_adam_proj_fused).  Returns False (and does nothing) if that kernel refuses the shape, so the caller can fall back.
         extra: gradient terms the caller left to the optimizer launch (`will_fuse`): {segment: dg_batch_wsum operands}.
         sole: the caller vouches that a fat conv segment's pending partial tiles are its only gradient term this step (one
         micro-batch, no path-length terms) and that the gradient buffer was zero-filled at the step's start."""
@@ -255,7 +282,8 @@ class FlatAdam:
         if fused_proj is not None:
             if self.betas[0] != 0.0:
                 return False
-            off = fused_proj[4] * fused_proj[5]
+            fp = E.ProjOperands(*fused_proj)
+            off = fp.rows * fp.nz
         plan = self._fused_plan(st, off, extra, sole) if self.will_fuse(shadow_dtype) else None
         if plan is None:
             if extra:   # (the terms left to the fused launch, as launches of their own)
@@ -274,10 +302,9 @@ class FlatAdam:
         ses = 2 if shadow_dtype == torch.bfloat16 else 4
         ema_ptr = L.ptr(ema_store.flat) if ema_store is not None else None
         if fused_proj is not None:
-            dp0, zT, op_dt, nb, Np, K, wscale = fused_proj
             rc = lib.dg_adam_proj_fused(L.ptr(st.flat), L.ptr(st.v), ema_ptr,
-                                        None if st.shadow is st.flat else L.ptr(st.shadow), sdt, L.ptr(dp0), L.ptr(zT),
-                                        op_dt, nb, Np, K, wscale, gscale, self.lr, self.betas[1], self.eps,
+                                        None if st.shadow is st.flat else L.ptr(st.shadow), sdt, L.ptr(fp.dp0), L.ptr(fp.zT),
+                                        fp.op_dtype, fp.nb, fp.rows, fp.nz, fp.scale, gscale, self.lr, self.betas[1], self.eps,
                                         L.ptr(self._step_dev), ema_decay, L.stream_ptr())
             if rc == L.DG_EUNSUPPORTED:
                 return False   # (nothing consumed: the caller's fall-back call plans again)
@@ -306,10 +333,6 @@ class FlatAdam:
         if ema_store is not None:
             ema_store._seen_version = -1  # its shadows are rebuilt lazily when G_ema is used
         return True
-
-
-def _store(net):
-    return net.store
 
 
 def _backbone(G):
@@ -483,6 +506,7 @@ class Trainer:
         self._works, self._comm_events = {}, None
         self._fuse_proj_ok = os.environ.get("DUSTY_GAN_FUSE_PROJ", "1") != "0"
         self._fuse_proj_fp32 = os.environ.get("DUSTY_GAN_FUSE_PROJ_FP32", "1") != "0"   # (A/B of the round-6 fp32 forms)
+        self.proj_route = None   # the ProjRoute of the last G step (optimize_G)
         # Collectives INSIDE the captured step (nccl = RCCL only): the process group enqueues a captured collective on its
         # own stream behind an event of the capture stream, and work.wait() joins it back - fork / join edges of ONE hipGraph,
         # no host call and no stream hand-off between graph segments at replay.  "1": try it first and fall back to the
@@ -747,9 +771,14 @@ class Trainer:
             gc.enable()
         self._gc_was_on = None
 
+    @property
+    def _multi_rank_schedule(self):
+        """several ranks (or DUSTY_GAN_FORCE_SEG=1 in one process) at one micro-batch: bucketed, overlapped exchanges"""
+        return (self.world > 1 or self._force_seg) and self.n_acc == 1
+
     def _bucketed(self):
-        """multi-rank schedule (also with DUSTY_GAN_FORCE_SEG=1 in one process): bucketed, overlapped exchanges"""
-        on = (self.world > 1 or self._force_seg) and self.n_acc == 1
+        """`_multi_rank_schedule`, with the segment order its buckets rely on checked once"""
+        on = self._multi_rank_schedule
         if on and not getattr(self, "_buckets_checked", False):
             # the buckets are cut by OFFSET in the flat gradient buffers and travel while later kernels still write other
             # offsets: that is only sound for this segment order (engine.g_segments / d_segments)
@@ -868,32 +897,25 @@ class Trainer:
                         L.check(lib.dg_scale(L.ptr(g), vscale, g.numel(), L.ptr(vg), sp), "dg_scale")
                     # (:229: the penalty's logged mean rides on the tangent's BlurVH launch)
                     deng.forward(Dst, vg, 2 * B, tangent_of=0, mean=(ssq, B, L.ptr(scal) + 12))
-                # weight gradients: real (weighted by dLoss/dy_real) + fake halves and tangent (x) real chain, one launch
-                # per fat layer (engine.DEngine.wgrad_r1)
-                for layers in (((4,), (3, 2, 1)) if bucketed else ((4, 3, 2, 1),)):
-                    deng.wgrad_r1(Dst, B, rs, layers=layers)
-                    if 4 in layers:
-                        if not fused:
-                            deng.final_wgrad(Dst, 0, 2 * B, dy)
-                        if (not bucketed and self.n_acc == 1 and not deng.x2 and self.optim_D.will_fuse(self.dtype)):
-                            # (round 6: the R1 term of the final conv's weight gradient is summed by the optimizer's launch)
-                            extra_D = {"final_w": deng.final_wgrad_term(2 * B, B)}
-                        else:
-                            deng.final_wgrad(Dst, 2 * B, B, None)
-                        if bucketed:
-                            self._allreduce_async("D.hi", Dst.grad[cut:])
             else:
                 deng.backward_data(Dst, 0, 2 * B, dy, None, want_dbias=True, skip_final=fused)
-                if not bucketed:
-                    deng.wgrad(Dst, 0, 0, 2 * B, None)
-                    if not fused:
-                        deng.final_wgrad(Dst, 0, 2 * B, dy)
+            # weight gradients by layer group: bucketed, layer 4 first (its bucket travels beside the rest); else one group
+            for layers in (((4,), (3, 2, 1)) if bucketed else (((4, 3, 2, 1),) if gp > 0 else ((1, 2, 3, 4),))):
+                if gp > 0:
+                    # real (weighted by dLoss/dy_real) + fake halves and tangent (x) real chain, one launch per fat layer
+                    deng.wgrad_r1(Dst, B, rs, layers=layers)
                 else:
-                    deng.wgrad(Dst, 0, 0, 2 * B, None, layers=(4,))
+                    deng.wgrad(Dst, 0, 0, 2 * B, None, layers=layers)
+                if 4 in layers:   # ... followed by the final conv's weight-gradient terms and the exchange of [d4_w, end)
                     if not fused:
                         deng.final_wgrad(Dst, 0, 2 * B, dy)
-                    self._allreduce_async("D.hi", Dst.grad[cut:])
-                    deng.wgrad(Dst, 0, 0, 2 * B, None, layers=(3, 2, 1))
+                    if gp > 0 and not bucketed and self.n_acc == 1 and not deng.x2 and self.optim_D.will_fuse(self.dtype):
+                        # (round 6: the R1 term of the final conv's weight gradient is summed by the optimizer's launch)
+                        extra_D = {"final_w": deng.final_wgrad_term(2 * B, B)}
+                    elif gp > 0:
+                        deng.final_wgrad(Dst, 2 * B, B, None)
+                    if bucketed:
+                        self._allreduce_async("D.hi", Dst.grad[cut:])
             self._mb.append({"x_real": x_real, "m_real": m_real, "rand": rand, "synth": synth, "geng": gengs[j]})
         if self._bucketed():
             self._allreduce_async("D.lo", Dst.grad[:Dst.seg["d4_w"].off])
@@ -908,34 +930,49 @@ class Trainer:
     # ------------------------------------------------------------------ G phase (reference :240-316)
     @_own_counters
     def optimize_G(self):
-        lib, sp = L.lib(), L.stream_ptr()
-        B = self.local_batch
-        Gb, D = _backbone(self.G), self.D
-        Gst, Dst = Gb.store, D.store
+        """One generator update: the micro-batches' backward passes, Proj.weight's gradient by the step's route
+        (`self.proj_route`, decided here once: `proj_route`) with the gradient exchange, then Adam + EMA.  An in-optimizer
+        route whose kernel refuses the shape falls back within the step - the tail bucket is waited for, the gradient is
+        materialised from the same operands, the plain optimizer runs - and switches the fused forms off for good: from
+        the next step on the route is GATHER or MATERIALISED."""
+        Gst = _backbone(self.G).store
         pl_on = "pl" in self.criterion
         if "G" in getattr(self, "_grads_zeroed", ()):
             self._grads_zeroed.discard("G")     # (filled with the step's arena: _begin_step)
         else:
             self.optim_G.zero_grad(skip=("proj_w",) if self.n_acc == 1 else ())
-        gather_proj = (self.world > 1 or self._force_seg) and self.n_acc == 1 and next(iter(Gst.seg)) == "proj_w"
-        fuse_proj = (not gather_proj and self.world == 1 and self.n_acc == 1 and self.dtype in (torch.bfloat16, torch.float32)
-                     and (self.dtype == torch.bfloat16 or self._fuse_proj_fp32)
-                     and next(iter(Gst.seg)) == "proj_w" and Gst.seg["proj_w"].off == 0 and self._fuse_proj_ok
-                     and self.optim_G.betas[0] == 0.0 and E.PROFILE is None)
-        fuse_gathered = (gather_proj and self.dtype == torch.bfloat16 and Gst.seg["proj_w"].off == 0
-                         and self._fuse_proj_ok and self.optim_G.betas[0] == 0.0 and E.PROFILE is None)
-        if not (fuse_proj or fuse_gathered):
+        route = self.proj_route = proj_route(
+            multi_rank_schedule=self._multi_rank_schedule, n_acc=self.n_acc, dtype=self.dtype,
+            proj_first=next(iter(Gst.seg)) == "proj_w", fuse_ok=self._fuse_proj_ok, fuse_fp32=self._fuse_proj_fp32,
+            beta1=self.optim_G.betas[0], profiling=E.PROFILE is not None)
+        self._g_backward(route, pl_on)
+        operands, gscale, tail_wait = self._proj_exchange(route, pl_on)
+        # Adam + EMA fused (:312, :316); the in-optimizer routes also fold Proj.weight's gradient GEMM into the kernel
+        adam = dict(gscale=gscale, ema_store=_backbone(self.G_ema).store, ema_decay=self.ema_decay, shadow_dtype=self.dtype)
+        ok = self.optim_G.step(fused_proj=operands, between=tail_wait, sole=self.n_acc == 1 and not pl_on, **adam)
+        if not ok:  # shape the fused kernel does not take: materialise the gradient and run the plain optimizer
+            if tail_wait is not None:
+                tail_wait()
+            self.optim_G.regen_grad()
             self.optim_G.regen_grad = None
-        deng = D.engine()
+            self._fuse_proj_ok = False
+            self.optim_G.step(**adam)
+        self._mb = []
+        return self._dev_scal
+
+    def _g_backward(self, route, pl_on):
+        """the micro-batch loop of the G phase: D on the fake batch, the loss step, D's backward-data and G's backward pass
+        (+ the path-length block), with Proj.weight's gradient left out where `route` forms it later"""
+        B, scal = self.local_batch, self._dev_scal
+        Gst, Dst = _backbone(self.G).store, self.D.store
+        deng = self.D.engine()
         w_gan = float(self.loss_weight["gan"]) / self.n_acc
-        f32 = dict(dtype=torch.float32, device=self.device)
-        scal = self._dev_scal
         for j in gradient_accumulation(self.n_acc, True, (self.G, self.D)):
             mb = self._mb[j]
             rand = mb["rand"]
             # :255/:259 A(real) and D(real) feed only the relativistic losses (loss.py:76-85); the other metrics'
             # loss_G never reads pred_real (loss.py:66-75), so that pass is not run for them
-            dy = torch.empty(B, **f32)
+            dy = torch.empty(B, dtype=torch.float32, device=self.device)
             if self.criterion["gan"].relativistic:
                 # fake first: its slots 0..B carry the backward (:256, :255, :259-260, updated D)
                 y = deng.forward_aug(Dst, self.A, [(mb["synth"]["depth"], rand["aug"][3]), (mb["x_real"], rand["aug"][2])], 0)
@@ -946,14 +983,13 @@ class Trainer:
             fused = deng.final_gan_bwd(Dst, 0, B, self.gan_code, True, 1.0, w_gan, y_real, L.ptr(y), False, dy, None, None,
                                        L.ptr(scal) + 16, False, False)
             if not fused:
-                L.check(lib.dg_gan_g_step(self.gan_code, y_real, L.ptr(y), B, w_gan, L.ptr(dy), L.ptr(scal) + 16, sp),
-                        "dg_gan_g_step")
+                L.check(L.lib().dg_gan_g_step(self.gan_code, y_real, L.ptr(y), B, w_gan, L.ptr(dy), L.ptr(scal) + 16,
+                                              L.stream_ptr()), "dg_gan_g_step")
             deng.backward_data(Dst, 0, B, dy, None, want_dbias=False, skip_final=fused)
             ddepth = deng.backward_input_aug(Dst, 0, B, self.A, rand["aug"][3], lazy=True)
-            overlap = gather_proj and not pl_on  # (the path-length block adds to every gradient after this pass)
-            if overlap:
+            if route.gathers and not pl_on:  # (the path-length block adds to every gradient after this pass)
                 geng = mb["geng"]
-                zg, dg = self._gather_bufs(geng, B)
+                zg, dg = self._gather_bufs(geng.zT, geng.dp[0])
                 # two exchanges: the operand gather starts behind the backward-data chain and travels beside every weight
                 # gradient; the tail bucket (all of G's gradient but Proj.weight, 11 MB) starts behind the last weight
                 # gradient and travels beside the fused Proj optimizer (0.3 ms), which only needs the gather - the rest of
@@ -963,80 +999,58 @@ class Trainer:
                     after_chain=lambda: self._comm_issue("G.gather", lambda: D_.all_gather_pair((zg, dg), (geng.zT, geng.dp[0]))))
                 self._allreduce_async("G.tail", Gst.grad[Gst.seg["proj_b"].off:])
             else:
-                mb["geng"].backward(Gst, ddepth, accumulate_proj=(j > 0), skip_proj=gather_proj or fuse_proj)
+                mb["geng"].backward(Gst, ddepth, accumulate_proj=(j > 0), skip_proj=route.skips_backward)
             if pl_on:
                 # (Proj.weight's two path-length terms follow its adversarial term: materialised here, or - when that
                 # gradient is formed inside the optimizer / from gathered operands - appended to its operand list below)
-                self._path_length(Gst, rand.get("pl"), B // 2, scal, proj_terms=not (gather_proj or fuse_proj))
-        fused = None
-        if gather_proj:
-            # Proj.weight is 96 % of G's gradient bytes (268 MB fp32) and the last tensor backward produces.  It is a
-            # plain linear layer, so instead of all-reducing its gradient every rank gathers the tiny operands
-            # (z [B,nz] and dL/da0 [B,h0*w0*C], 8.4 MB per rank in bf16) and forms the GLOBAL-batch gradient locally:
-            # same sum, 3.5x less xGMI traffic, and the 268 MB never cross a link.
-            geng = self._mb[0]["geng"]
-            if not pl_on:
-                # started inside the backward pass (right after the data chain / the largest weight gradient)
-                zg, dg = self._gather_bufs(geng, B)
-                nloc = B
+                self._path_length(Gst, rand.get("pl"), B // 2, scal, proj_terms=not route.skips_backward)
+
+    def _proj_exchange(self, route, pl_on):
+        """G's gradient exchange and what `route` makes of Proj.weight's gradient in it.  Returns (operands, gscale,
+        tail_wait): the engine.ProjOperands the optimizer forms that gradient from (in-optimizer routes, which also set
+        `optim_G.regen_grad`; else None - the gradient is in the buffer), the factor Adam applies to the summed gradient,
+        and the wait for the tail bucket's exchange where it is still travelling (GATHER_FUSED without the path-length
+        block: the optimizer waits behind its Proj launch; else None)."""
+        B, Gst = self.local_batch, _backbone(self.G).store
+        geng, tail_wait = self._mb[0]["geng"], None
+        if route.gathers:
+            # Proj is a plain linear layer and its weight gradient the last tensor backward produces: instead of all-reducing
+            # its 268 MB every rank gathers the tiny operands (z [B,nz] and dL/da0 [B,h0*w0*C], 8.4 MB per rank in bf16) and
+            # forms the GLOBAL-batch gradient locally - same sum, 3.5x less xGMI traffic (SURVEY.md §7)
+            dp_loc, z_loc, nloc = self._local_proj_rows(geng, B)
+            zT, dp0 = self._gather_bufs(z_loc, dp_loc)
+            nb = self.world * nloc
+            if not pl_on:   # started inside the backward pass (right after the data chain / the largest weight gradient)
                 self._comm_wait("G.gather")
             else:
-                dp0, zT, nloc = self._proj_operands(geng, B)
-                if self._gather is None or self._gather[0].numel() != self.world * zT.numel():
-                    self._gather = (zT.new_empty(self.world * zT.numel()), self._like(dp0, self.world * dp0.numel()))
-                zg, dg = self._gather
-                self._coll(lambda: (D_.all_gather_into(zg, zT), D_.all_gather_into(dg, dp0)), name="all-gather Proj operands")
-            nbg = self.world * nloc
-            if fuse_gathered:
-                # ... and the global-batch gradient is not even written: the optimizer forms it tile by tile in the
-                # epilogue of the gradient GEMM (dg_adam_proj_fused -> MFMA path for nb > 64)
-                c = geng.cfg
-                Np = c.h0 * c.w0 * c.ch[3]
-                fused = (dg, zg, L.dtype_code(self.dtype), nbg, Np, c.nz, 1.0 / math.sqrt(Np))
-                self.optim_G.regen_grad = lambda: geng.proj_wgrad(Gst, dg, zg, nbg, False)
-            else:
-                geng.proj_wgrad(Gst, dg, zg, nbg)
-            if not pl_on:
-                if fused is None:
-                    self._comm_wait("G.tail")   # (no fused Proj optimizer to hide it behind)
-            else:
+                self._coll(lambda: (D_.all_gather_into(zT, z_loc), D_.all_gather_into(dp0, dp_loc)),
+                           name="all-gather Proj operands")
+            if route is ProjRoute.GATHER:
+                geng.proj_wgrad(Gst, dp0, zT, nb)
+            # (GATHER_FUSED: not even written - formed tile by tile in the epilogue of dg_adam_proj_fused's gradient GEMM, nb > 64)
+            if pl_on:
                 tail = Gst.grad[Gst.seg["proj_b"].off:]
                 E.WGRAD_WS.flush()
                 self._coll(lambda: D_.allreduce_grads(tail), name="all-reduce G tail")
+            elif route is ProjRoute.GATHER:
+                self._comm_wait("G.tail")   # (no fused Proj optimizer to hide it behind)
+            else:
+                tail_wait = lambda: self._comm_wait("G.tail")   # noqa: E731
             gscale = 1.0 / self.world
         else:
             gscale = self._allreduce(Gst)
-            if fuse_proj:
-                geng = self._mb[0]["geng"]
-                c = geng.cfg
-                Np = c.h0 * c.w0 * c.ch[3]
-                dp0, zT, nloc = self._proj_operands(geng, B)
-                op_dt = L.dtype_code(self.dtype)
-                if self.dtype == torch.float32:
-                    # the parity-class modes (round 6): fp32 rows - split-bf16 pairs (fp32x3 with split storage) through an fp32
-                    # copy, as the unfused GEMM takes them - on the fp32 matrix instructions or, fp32x3, as bf16 pairs in registers
-                    if E.is_x2(dp0):
-                        dp0 = E.x2_unpack(dp0, geng.ops._f32_copy("wa", dp0))
-                    if E.is_x2(zT):
-                        zT = E.x2_unpack(zT, geng.ops._f32_copy("wg", zT))
-                    if geng.ops.x3:
-                        op_dt |= L.DG_FORCE_FP32X3
-                fused = (dp0, zT, op_dt, nloc, Np, c.nz, 1.0 / math.sqrt(Np))
-                self.optim_G.regen_grad = lambda: geng.proj_wgrad(Gst, dp0, zT, nloc, False)
-        # Adam + EMA fused (:312, :316); single-GPU bf16 runs also fold Proj.weight's gradient GEMM into the kernel
-        tail_wait = (lambda: self._comm_wait("G.tail")) if (gather_proj and not pl_on and fused is not None) else None
-        ok = self.optim_G.step(gscale=gscale, ema_store=_backbone(self.G_ema).store, ema_decay=self.ema_decay,
-                               shadow_dtype=self.dtype, fused_proj=fused, between=tail_wait, sole=self.n_acc == 1 and not pl_on)
-        if not ok:  # shape the fused kernel does not take: materialise the gradient and run the plain optimizer
-            if tail_wait is not None:
-                tail_wait()
-            self.optim_G.regen_grad()
+            if route is ProjRoute.FUSED:
+                dp0, zT, nb = self._local_proj_rows(geng, B)
+                # the parity-class modes (round 6): fp32 rows - split-bf16 pairs (fp32x3 with split storage) through an fp32
+                # copy, as the unfused GEMM takes them - on the fp32 matrix instructions or, fp32x3, as bf16 pairs in registers
+                dp0, zT = geng.ops.gemm_rows_f32(dp0, zT)
+        if not route.in_optimizer:
             self.optim_G.regen_grad = None
-            self._fuse_proj_ok = False
-            self.optim_G.step(gscale=gscale, ema_store=_backbone(self.G_ema).store, ema_decay=self.ema_decay,
-                              shadow_dtype=self.dtype)
-        self._mb = []
-        return scal
+            return None, gscale, None
+        assert Gst.seg["proj_w"].off == 0   # (the optimizer's Proj launch takes flat[0 : rows * nz])
+        self.optim_G.regen_grad = lambda: geng.proj_wgrad(Gst, dp0, zT, nb, False)
+        op_dt = L.dtype_code(self.dtype) | (L.DG_FORCE_FP32X3 if geng.ops.x3 else 0)   # (x3: fp32 engines only)
+        return geng.proj_operands(dp0, zT, nb, op_dt), gscale, tail_wait
 
     @staticmethod
     def _like(src, n):
@@ -1044,11 +1058,11 @@ class Trainer:
         t = src.new_empty(n)
         return E.tag_x2(t) if E.is_x2(src) else t
 
-    def _gather_bufs(self, geng, B):
+    def _gather_bufs(self, zT, dp0):
         """static all-gather destinations for Proj's gradient operands (z rows, dL/da0 rows) of the global batch"""
-        n = self.world * geng.zT.numel()
+        n = self.world * zT.numel()
         if self._gather is None or self._gather[0].numel() != n:
-            self._gather = (geng.zT.new_empty(n), self._like(geng.dp[0], self.world * geng.dp[0].numel()))
+            self._gather = (zT.new_empty(n), self._like(dp0, self.world * dp0.numel()))
         return self._gather
 
     def launch_mode(self):
@@ -1088,7 +1102,7 @@ class Trainer:
             out[name] = out.get(name, 0.0) + e0.elapsed_time(e1) / steps
         return {k: round(v, 4) for k, v in out.items()}
 
-    def _proj_operands(self, geng, B):
+    def _local_proj_rows(self, geng, B):
         """(gradient rows, input rows, count) whose product is Proj.weight's gradient: the adversarial pair and, with
         the path-length term on, its two pairs (z_pl, tangent chain) and (v, first-order chain) - the three GEMMs share
         the output, so they are ONE GEMM over the concatenated rows.  Static buffers (graph replay, all-gather)."""

@@ -418,7 +418,7 @@ def fused_worker(rank, world, init_file, out_dir, fuse, pl=0.0):
     scal = [dict(tr.step(i).items()) for i in range(3)]
     used = tr.optim_G.regen_grad is not None  # set only while Proj.weight's gradient lives inside the optimizer kernel
     torch.save({"G": tr.G.store.flat.cpu(), "E": tr.G_ema.store.flat.cpu(), "V": tr.G.store.v.cpu(), "scal": scal,
-                "used": used}, os.path.join(out_dir, f"f{int(fuse)}_r{rank}.pt"))
+                "used": used, "route": tr.proj_route.name}, os.path.join(out_dir, f"f{int(fuse)}_r{rank}.pt"))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -435,6 +435,7 @@ def test_two_ranks_fused_proj_optimizer_matches_unfused(pl):
             mp.spawn(fused_worker, args=(2, os.path.join(td, "init"), td, fuse, pl), nprocs=2, join=True)
             res[fuse] = [torch.load(os.path.join(td, f"f{int(fuse)}_r{r}.pt")) for r in range(2)]
     assert all(o["used"] for o in res[True]) and not any(o["used"] for o in res[False])
+    assert all(o["route"] == "GATHER_FUSED" for o in res[True]) and all(o["route"] == "GATHER" for o in res[False])
     for r in range(2):
         a, b = res[True][r], res[False][r]
         # not bit-equal: atomics reorder fp32 sums from run to run, and a last-bit difference can flip a bf16 rounding of the

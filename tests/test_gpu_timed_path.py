@@ -132,6 +132,7 @@ def test_bench_configuration_step_vs_oracle(trace, amp):
     if amp:
         assert any(t[0] == "wgrad" and t[1] == DG_WGRAD_VARIANT_DMA for t in trace)    # ... and the LDS-DMA weight-gradient kernel
         assert tr.optim_G.regen_grad is not None                    # Proj.weight went through dg_adam_proj_fused
+        assert tr.proj_route.name == "FUSED"
     _check_step(res[0], tr, state, amp)
 
 
