@@ -1545,11 +1545,17 @@ class DEngine:
             WGRAD_WS.add(part, st.fptr("d4_b", st.grad), C4, nf // C4, 1)
         return True
 
-    def r1_fused_ok(self):
-        """whether dg_blur_bwd_r1 (BlurVH adjoint + R1 tangent + |g|^2 in one pass) takes this image shape
+    @staticmethod
+    def r1_fused_ok(H, W):
+        """whether dg_blur_bwd_r1 (BlurVH adjoint + R1 tangent + |g|^2 in one pass) takes an H x W image
         (blur_aug.hip: four pixels per thread, 1024-pixel blocks)"""
-        c = self.cfg
-        return c.W % 4 == 0 and (c.H * c.W) % 1024 == 0
+        return W % 4 == 0 and (H * W) % 1024 == 0
+
+    @staticmethod
+    def r1_turnaround_ok(H, W):
+        """whether dg_blur_r1_tangent (the one-launch R1 turn-around) takes an H x W image
+        (blur_aug.hip: bands of four rows, six image rows of floats in at most 60 KiB of LDS)"""
+        return W % 4 == 0 and H % 4 == 0 and 6 * W * 4 <= 60 * 1024
 
     def backward_input(self, st, slot, n, dx, r1=None):
         """Continue a chain from e1 to the image: Down1 backward-data + BlurVH adjoint -> dx [n,1,H,W] fp32.
@@ -1557,7 +1563,7 @@ class DEngine:
         Returns True when dx was written; False - with NOTHING launched - when r1 was asked for a shape the fused
         adjoint does not take (the caller then runs the plain form and its own sum / scale passes)."""
         c, o, lib = self.cfg, self.ops, L.lib()
-        if r1 is not None and not self.r1_fused_ok():
+        if r1 is not None and not self.r1_fused_ok(c.H, c.W):
             return False
         self._bwd_layer(st, 1, slot, n, None, False)
         if r1 is not None:
@@ -1576,7 +1582,7 @@ class DEngine:
         False - NOTHING launched - where that kernel does not take the image shape: the caller runs backward_input +
         forward(tangent_of=...)."""
         c, o, lib = self.cfg, self.ops, L.lib()
-        if c.W % 4 or c.H % 4 or 6 * c.W * 4 > 60 * 1024:
+        if not self.r1_turnaround_ok(c.H, c.W):
             return False
         self._bwd_layer(st, 1, slot, n, None, False)
         L.check(lib.dg_blur_r1_tangent(L.ptr(self.e[0]) + o.es * slot * self.per[0], o.dt,

@@ -14,9 +14,11 @@ What differs underneath:
   * scalars are gathered with ONE packed all-reduce and read back lazily.
 """
 import enum
+import gc
 import math
 import os
 import os.path as osp
+import warnings
 from collections import OrderedDict
 from collections.abc import Mapping
 
@@ -68,6 +70,21 @@ def proj_route(*, multi_rank_schedule, n_acc, dtype, proj_first, fuse_ok, fuse_f
         return ProjRoute.GATHER_FUSED if fusable and dtype == torch.bfloat16 else ProjRoute.GATHER
     local_ok = fusable and (dtype == torch.bfloat16 or (dtype == torch.float32 and fuse_fp32))
     return ProjRoute.FUSED if local_ok else ProjRoute.MATERIALISED
+
+
+class R1Form(enum.Enum):
+    """How the D phase gets from the real batch's chain at e1 to the R1 tangent's feature maps (`Trainer._r1_tangent`)."""
+    TURNAROUND = "turnaround"        # DEngine.r1_turnaround: adjoint, |g|^2 and the tangent's BlurVH in one launch; g never written
+    FUSED_ADJOINT = "fused_adjoint"  # backward_input(r1=): the BlurVH adjoint also scales g and sums |g|^2; then the tangent forward
+    THREE_PASS = "three_pass"        # backward_input, dg_sample_sum[_acc], dg_scale; then the tangent forward
+
+
+def r1_form(*, H, W, have_ssq):
+    """The R1 form of a D step at an H x W image, from plain values.  have_ssq: the step's arena had a slice left for the
+    per-sample |g|^2 sums, which the two fused kernels add into; without one the three passes sum into a fresh buffer."""
+    if have_ssq and E.DEngine.r1_turnaround_ok(H, W):
+        return R1Form.TURNAROUND
+    return R1Form.FUSED_ADJOINT if have_ssq and E.DEngine.r1_fused_ok(H, W) else R1Form.THREE_PASS
 
 
 class LazyScalars(Mapping):
@@ -138,6 +155,7 @@ class FlatAdam:
         self.net, self.lr, self.betas, self.eps = net, float(lr), (float(betas[0]), float(betas[1])), eps
         self.step_count = 0      # host mirror (checkpoints); the kernels read the device counter
         self._step_dev = None
+        self._last_gscale = None  # the factor of the last `step`: state_dict() rebuilds exp_avg from it at beta1 = 0
 
     @property
     def store(self):
@@ -146,7 +164,7 @@ class FlatAdam:
     def _param_views(self, buf):
         """views of `buf` (grad/m/v) shaped like the module's parameters, in named_parameters() order"""
         st = self.store
-        pairs = self.net.backbone._bind_pairs() if hasattr(self.net, "backbone") else self.net._bind_pairs()
+        pairs = _backbone(self.net)._bind_pairs()
         by_param = {id(p): mk for p, mk in pairs}
         views = []
         saved = st.flat
@@ -162,7 +180,7 @@ class FlatAdam:
         st = self.store
         state = {}
         if self.step_count > 0:
-            if self.betas[0] == 0.0 and getattr(self, "_last_gscale", None) is not None:
+            if self.betas[0] == 0.0 and self._last_gscale is not None:
                 if getattr(self, "regen_grad", None) is not None:
                     self.regen_grad()  # a gradient the fused optimizer kernel never materialised (Proj.weight)
                 st.m.copy_(st.grad * self._last_gscale)  # exp_avg of torch.optim.Adam at beta1 = 0
@@ -413,6 +431,7 @@ class Trainer:
 
         # data (reference :80-90): a device-resident synthetic pool for `dataset.name == synthetic`, the file datasets
         # through the device-side scan pipeline (datasets/scans.py), or any iterator of {"depth","mask"} batches
+        self._scan_loader = None   # the ScanLoader / ResidentScanLoader behind `loader` (file datasets only)
         if loader is not None:
             self.loader = loader
         elif str(self.cfg.dataset.name) == "synthetic":
@@ -487,8 +506,16 @@ class Trainer:
         if resume_extra is not None:
             self._restore_position(resume_extra)
         self._geng = None
-        self._pending = None
         self._dev_scal = None
+        self._mb = []               # the D phase's micro-batches, kept for the G phase: x_real, m_real, rand, synth, geng
+        self._arena_ready = False   # `_begin_step` has opened this step's arena (the graph path does, before its fetch)
+        self._grads_zeroed = set()  # "D" / "G": that network's gradient buffer was zero-filled with the arena
+        self._predrawn = None       # the first micro-batch's draws, made by the step's first launch (`_draw_jobs`)
+        self._drawn_ahead = 1       # batches `_step_graph` draws from the loader before the step fetches the first
+        self._rs3 = None            # [dLoss/dy_real | 1 | 1]: per-sample weights of the D weight gradients (`_r1_rowscale`)
+        self._cat = None            # Proj's gradient operands with the path-length rows appended (`_local_proj_rows`)
+        self._gc_was_on = None      # whether `_cap_open` switched the garbage collector off (None: no capture open)
+        self._buckets_checked = False   # `_bucketed` has checked the segment order its buckets rely on
         self._pool_ctr = None   # device-resident loader position of the synthetic pool or the resident store
         self._fetch_in_prologue = os.environ.get("DUSTY_GAN_FETCH_IN_PROLOGUE", "1") != "0"   # (A/B switch, tests)
         self._pool_host = 0     # its host mirror: checked against batches_drawn before every graph step
@@ -507,6 +534,7 @@ class Trainer:
         self._fuse_proj_ok = os.environ.get("DUSTY_GAN_FUSE_PROJ", "1") != "0"
         self._fuse_proj_fp32 = os.environ.get("DUSTY_GAN_FUSE_PROJ_FP32", "1") != "0"   # (A/B of the round-6 fp32 forms)
         self.proj_route = None   # the ProjRoute of the last G step (optimize_G)
+        self.r1_form = None      # the R1Form of the last D step (optimize_D); None without R1 (gp == 0)
         # Collectives INSIDE the captured step (nccl = RCCL only): the process group enqueues a captured collective on its
         # own stream behind an event of the capture stream, and work.wait() joins it back - fork / join edges of ONE hipGraph,
         # no host call and no stream hand-off between graph segments at replay.  "1": try it first and fall back to the
@@ -588,8 +616,7 @@ class Trainer:
     def _resident(self):
         """the resident scan store (datasets/resident.py), or None"""
         from ..datasets.resident import ResidentScanLoader
-        inner = getattr(self, "_scan_loader", None)
-        return inner if isinstance(inner, ResidentScanLoader) else None
+        return self._scan_loader if isinstance(self._scan_loader, ResidentScanLoader) else None
 
     def _pooled(self):
         """the loader is device-resident - the synthetic pool, or a resident scan store at a shape the prologue fetch takes (the
@@ -612,7 +639,7 @@ class Trainer:
             if self._pool_ctr is None:
                 # (the batch this call fetches: the last one drawn, or - an accumulated step draws its num_accumulation batches
                 #  up front - the first of those)
-                first = self.batches_drawn - (getattr(self, "_drawn_ahead", 1) or 1)
+                first = self.batches_drawn - self._drawn_ahead
                 self._pool_ctr = torch.full((1,), first, dtype=torch.int64, device=self.device)
                 self._pool_host = first
             L.Counters.flush_if(self._pool_ctr)
@@ -670,7 +697,7 @@ class Trainer:
 
     def _prep_rand(self, rand, B):
         if rand is None:
-            pre, self._predrawn = getattr(self, "_predrawn", None), None
+            pre, self._predrawn = self._predrawn, None
             if pre is not None and pre["B"] == B:
                 return pre                # drawn by the step's first launch (`_begin_step`)
             assert pre is None, "pre-drawn parameters for another batch size"
@@ -731,7 +758,6 @@ class Trainer:
         self._coll(wait, name="wait " + "+".join(keys))
 
     def _cap_open(self):
-        import gc
         # No cyclic garbage collection while a capture is open: a collection that starts in the middle of it may finalize objects
         # of EARLIER trainers - their hipGraphs, tensors of their private pools - and destroying a graph or freeing pool memory
         # from inside a capturing thread aborts the process (round 5: torch 2.10's graph context no longer collects on entry,
@@ -740,7 +766,7 @@ class Trainer:
         # picture: nothing can start a collection inside the capture, and the ~70 ms of a full collection here would idle the
         # GPU long enough to send its clock down right in front of the first replays (round 6: the capture step took 76 ms of
         # host time, 66 of them in gc.collect; scripts/probes/capture_idle.py).
-        if self._cap_cur is None and getattr(self, "_gc_was_on", None) is None:
+        if self._cap_cur is None and self._gc_was_on is None:
             self._gc_was_on = gc.isenabled()
             if self._gc_was_on:
                 gc.collect()
@@ -754,7 +780,6 @@ class Trainer:
         self._cap_cur = (g, ctx)
 
     def _cap_close(self):
-        import warnings
         g, ctx = self._cap_cur
         with warnings.catch_warnings(record=True) as caught:
             warnings.simplefilter("always")
@@ -766,8 +791,7 @@ class Trainer:
         self._gc_restore()
 
     def _gc_restore(self):
-        import gc
-        if getattr(self, "_gc_was_on", None):
+        if self._gc_was_on:
             gc.enable()
         self._gc_was_on = None
 
@@ -779,7 +803,7 @@ class Trainer:
     def _bucketed(self):
         """`_multi_rank_schedule`, with the segment order its buckets rely on checked once"""
         on = self._multi_rank_schedule
-        if on and not getattr(self, "_buckets_checked", False):
+        if on and not self._buckets_checked:
             # the buckets are cut by OFFSET in the flat gradient buffers and travel while later kernels still write other
             # offsets: that is only sound for this segment order (engine.g_segments / d_segments)
             dn, gn = list(self.D.store.seg), list(_backbone(self.G).store.seg)
@@ -811,112 +835,29 @@ class Trainer:
     # ------------------------------------------------------------------ D phase (reference :171-238)
     @_own_counters
     def optimize_D(self, reals=None, rands=None):
-        """One discriminator update over `num_accumulation` micro-batches.
+        """One discriminator update over `num_accumulation` micro-batches (`_d_micro_batch`), the gradient exchange, Adam.
         reals: optional list of (x_real, m_real) already through fetch_reals; rands: optional list of randomness
         bundles {"z", "noise", "aug":[4 parameter sets]} (parity tests); defaults draw from the loader / Philox."""
-        lib, sp = L.lib(), L.stream_ptr()
-        B = self.local_batch
-        Gb, D = _backbone(self.G), self.D
+        B, Dst = self.local_batch, self.D.store
         self.G.train()
-        gengs = self._g_engines()
-        deng = D.engine()
+        deng = self.D.engine()
         deng.alloc(3 * B, self.device)
-        Dst, Gst = D.store, Gb.store
         Dst.refresh_shadows(self.dtype)
-        Gst.refresh_shadows(self.dtype)
+        _backbone(self.G).store.refresh_shadows(self.dtype)
         gp = float(self.loss_weight.get("gp", 0.0)) if "gp" in self.criterion else 0.0
-        w_gan = float(self.loss_weight["gan"]) / self.n_acc
-        self._mb = []
-        extra_D = None
-        dev = self.device
+        self._mb, self.r1_form, extra_D = [], None, None
         # real, fake, adv, gp, G adv, path-length baseline, path-length penalty (sums over micro-batches)
         # every small accumulator of the step (these scalars, per-sample sums, logits) comes zeroed out of ONE arena
-        if not getattr(self, "_arena_ready", False):   # (the graph path opens it before its fetch_reals)
+        if not self._arena_ready:   # (the graph path opens it before its fetch_reals)
             self._begin_step(draw_B=B if rands is None else None)
         self._arena_ready = False
         if "D" in self._grads_zeroed:
             self._grads_zeroed.discard("D")
         else:
             self.optim_D.zero_grad()
-        scal = L.AccArena.take(16, dev)[:7]
-        f32 = dict(dtype=torch.float32, device=dev)
+        scal = L.AccArena.take(16, self.device)[:7]
         for j in gradient_accumulation(self.n_acc, True, (self.G, self.D)):
-            if reals is not None:
-                x_real, m_real = reals[j]
-            else:
-                x_real, m_real = self.fetch_reals(self._next_batch())
-            rand = self._prep_rand(rands[j] if rands is not None else None, B)
-            synth = gengs[j].forward(Gst, rand["z"], rand["noise"], training=True,   # :195 (graph kept = workspaces)
-                                     z_ready=bool(rand.get("z_ready")) and j == 0)
-            # :199-204  A(real) | A(fake) -> D, one pass; DiffAugment fused into BlurVH's pass where the sums exist
-            y = deng.forward_aug(Dst, self.A, [(x_real, rand["aug"][0]), (synth["depth"], rand["aug"][1])], 0)
-            # loss + dLoss/dy + the R1 schedule's per-sample vectors + scalar sums + final-bias gradient: one launch
-            # chain upstream `up`: 1 for the real half (that IS d sum(y_real)/dx, :218-223), dLoss/dy for the fake half;
-            # `rs`: the real half's ordinary backward is the same chain weighted per sample by dLoss/dy_real
-            dy = torch.empty(2 * B, **f32)
-            up = torch.empty(2 * B, **f32) if gp > 0 else None
-            rs = None
-            if gp > 0:
-                # per-sample weights of the weight-gradient sums over the 3B input slots real | fake | tangent: the kernel
-                # below writes [dLoss/dy_real | 1]; the tangent rows' 1s are written once, here
-                if getattr(self, "_rs3", None) is None or self._rs3.numel() != 3 * B or self._rs3.device != self.device:
-                    self._rs3 = torch.ones(3 * B, **f32)
-                rs = self._rs3
-            # the loss step, the final conv's backward-data and its weight gradient as one launch; three where the
-            # kernel does not take the shape
-            fused = deng.final_gan_bwd(Dst, 0, B, self.gan_code, False, float(self.criterion["gan"].smoothing), w_gan,
-                                       L.ptr(y), L.ptr(y) + 4 * B, gp > 0, dy, up, rs, L.ptr(scal), True, True)
-            if not fused:
-                L.check(lib.dg_gan_d_step(self.gan_code, float(self.criterion["gan"].smoothing), L.ptr(y),
-                                          L.ptr(y) + 4 * B, B, w_gan, L.ptr(dy), L.ptr(up), L.ptr(rs), L.ptr(scal),
-                                          Dst.fptr("final_b", Dst.grad), sp), "dg_gan_d_step")
-            # data-parallel runs (one micro-batch): the gradient exchange is cut into two buckets at d4_w (73 % of D's
-            # bytes live in [d4_w, end)) and the weight gradients are formed last layer first, so the large bucket
-            # travels while the three smaller layers' gradients are still being computed
-            bucketed = self._bucketed()
-            cut = Dst.seg["d4_w"].off
-            if gp > 0:
-                deng.backward_data(Dst, 0, 2 * B, up, rs, want_dbias=True, skip_final=fused)
-                # R1 (:218-235): g = d sum(y_real) / dx_real, penalty = gp / 2 * mean_b |g_b|^2, and its double backward's
-                # tangent v = d penalty / dg = (gp / B) g, pushed forward through D below
-                vscale = gp / self.n_acc / B
-                ssq = L.AccArena.take(B, dev)
-                # (:229: the penalty's logged mean rides on the same launch)
-                if ssq is None or not deng.r1_turnaround(Dst, 0, B, 2 * B, vscale, ssq, L.ptr(scal) + 12):
-                    g = torch.empty(B, 1, self.H, self.W, **f32)
-                    vg = torch.empty_like(g)
-                    if ssq is None or not deng.backward_input(Dst, 0, B, vg, r1=(vscale, ssq)):
-                        # (shapes the fused adjoint does not take - refused before anything is launched - or no arena:
-                        # three passes)
-                        deng.backward_input(Dst, 0, B, g)
-                        if ssq is None:
-                            ssq = torch.empty(B, **f32)
-                            L.check(lib.dg_sample_sum(L.ptr(g), B, self.H * self.W, 1, L.ptr(ssq), sp), "dg_sample_sum")
-                        else:
-                            L.check(lib.dg_sample_sum_acc(L.ptr(g), B, self.H * self.W, 1, L.ptr(ssq), sp), "dg_sample_sum_acc")
-                        L.check(lib.dg_scale(L.ptr(g), vscale, g.numel(), L.ptr(vg), sp), "dg_scale")
-                    # (:229: the penalty's logged mean rides on the tangent's BlurVH launch)
-                    deng.forward(Dst, vg, 2 * B, tangent_of=0, mean=(ssq, B, L.ptr(scal) + 12))
-            else:
-                deng.backward_data(Dst, 0, 2 * B, dy, None, want_dbias=True, skip_final=fused)
-            # weight gradients by layer group: bucketed, layer 4 first (its bucket travels beside the rest); else one group
-            for layers in (((4,), (3, 2, 1)) if bucketed else (((4, 3, 2, 1),) if gp > 0 else ((1, 2, 3, 4),))):
-                if gp > 0:
-                    # real (weighted by dLoss/dy_real) + fake halves and tangent (x) real chain, one launch per fat layer
-                    deng.wgrad_r1(Dst, B, rs, layers=layers)
-                else:
-                    deng.wgrad(Dst, 0, 0, 2 * B, None, layers=layers)
-                if 4 in layers:   # ... followed by the final conv's weight-gradient terms and the exchange of [d4_w, end)
-                    if not fused:
-                        deng.final_wgrad(Dst, 0, 2 * B, dy)
-                    if gp > 0 and not bucketed and self.n_acc == 1 and not deng.x2 and self.optim_D.will_fuse(self.dtype):
-                        # (round 6: the R1 term of the final conv's weight gradient is summed by the optimizer's launch)
-                        extra_D = {"final_w": deng.final_wgrad_term(2 * B, B)}
-                    elif gp > 0:
-                        deng.final_wgrad(Dst, 2 * B, B, None)
-                    if bucketed:
-                        self._allreduce_async("D.hi", Dst.grad[cut:])
-            self._mb.append({"x_real": x_real, "m_real": m_real, "rand": rand, "synth": synth, "geng": gengs[j]})
+            extra_D = self._d_micro_batch(j, deng, gp, scal, reals, rands)
         if self._bucketed():
             self._allreduce_async("D.lo", Dst.grad[:Dst.seg["d4_w"].off])
             self._comm_wait("D.hi", "D.lo")
@@ -926,6 +867,105 @@ class Trainer:
         self.optim_D.step(gscale=gscale, shadow_dtype=self.dtype, extra=extra_D, sole=self.n_acc == 1)  # :238
         self._dev_scal = scal
         return scal
+
+    def _d_micro_batch(self, j, deng, gp, scal, reals, rands):
+        """micro-batch j of the D phase: its batch and draws, G's forward, D on A(real) | A(fake), the loss step, the
+        backward-data chain, with R1 on the tangent pass (`_r1_tangent`), the weight gradients (`_d_weight_grads`, whose
+        return value this passes on); the micro-batch is kept in `self._mb` for the G phase"""
+        lib, sp, B = L.lib(), L.stream_ptr(), self.local_batch
+        Dst, Gst, geng = self.D.store, _backbone(self.G).store, self._g_engines()[j]
+        w_gan = float(self.loss_weight["gan"]) / self.n_acc
+        x_real, m_real = reals[j] if reals is not None else self.fetch_reals(self._next_batch())
+        rand = self._prep_rand(rands[j] if rands is not None else None, B)
+        synth = geng.forward(Gst, rand["z"], rand["noise"], training=True,   # :195 (graph kept = workspaces)
+                             z_ready=bool(rand.get("z_ready")) and j == 0)
+        # :199-204  A(real) | A(fake) -> D, one pass; DiffAugment fused into BlurVH's pass where the sums exist
+        y = deng.forward_aug(Dst, self.A, [(x_real, rand["aug"][0]), (synth["depth"], rand["aug"][1])], 0)
+        # loss + dLoss/dy + the R1 schedule's per-sample vectors + scalar sums + final-bias gradient: one launch
+        # chain upstream `up`: 1 for the real half (that IS d sum(y_real)/dx, :218-223), dLoss/dy for the fake half;
+        # `rs`: the real half's ordinary backward is the same chain weighted per sample by dLoss/dy_real
+        dy = torch.empty(2 * B, dtype=torch.float32, device=self.device)
+        up = torch.empty_like(dy) if gp > 0 else None
+        rs = self._r1_rowscale(B) if gp > 0 else None
+        # the loss step, the final conv's backward-data and its weight gradient as one launch; three where the
+        # kernel does not take the shape
+        fused = deng.final_gan_bwd(Dst, 0, B, self.gan_code, False, float(self.criterion["gan"].smoothing), w_gan,
+                                   L.ptr(y), L.ptr(y) + 4 * B, gp > 0, dy, up, rs, L.ptr(scal), True, True)
+        if not fused:
+            L.check(lib.dg_gan_d_step(self.gan_code, float(self.criterion["gan"].smoothing), L.ptr(y),
+                                      L.ptr(y) + 4 * B, B, w_gan, L.ptr(dy), L.ptr(up), L.ptr(rs), L.ptr(scal),
+                                      Dst.fptr("final_b", Dst.grad), sp), "dg_gan_d_step")
+        if gp > 0:
+            deng.backward_data(Dst, 0, 2 * B, up, rs, want_dbias=True, skip_final=fused)
+            ssq = L.AccArena.take(B, self.device)   # per-sample |g|^2; None: the arena is exhausted
+            self.r1_form = r1_form(H=self.H, W=self.W, have_ssq=ssq is not None)
+            self._r1_tangent(deng, Dst, B, scal, self.r1_form, ssq)
+        else:
+            deng.backward_data(Dst, 0, 2 * B, dy, None, want_dbias=True, skip_final=fused)
+        extra_D = self._d_weight_grads(deng, Dst, B, gp, rs, dy, fused)
+        self._mb.append({"x_real": x_real, "m_real": m_real, "rand": rand, "synth": synth, "geng": geng})
+        return extra_D
+
+    def _r1_rowscale(self, B):
+        """per-sample weights of the weight-gradient sums over the 3B input slots real | fake | tangent: the loss step's
+        kernel writes [dLoss/dy_real | 1]; the tangent rows' 1s are written once, here"""
+        if self._rs3 is None or self._rs3.numel() != 3 * B or self._rs3.device != self.device:
+            self._rs3 = torch.ones(3 * B, dtype=torch.float32, device=self.device)
+        return self._rs3
+
+    def _r1_tangent(self, deng, Dst, B, scal, form, ssq):
+        """R1 (:218-235): g = d sum(y_real) / dx_real, penalty = gp / 2 * mean_b |g_b|^2, and its double backward's tangent
+        v = d penalty / dg = (gp / B) g, pushed forward through D into slots [2B, 3B), in the step's `form`.  ssq: the arena
+        slice |g_b|^2 is added into (None: THREE_PASS sums into a buffer of its own).  Each engine call launches everything
+        or refuses with nothing launched; `r1_form` decides by the engine's own predicates, so a refusal is an error."""
+        lib, sp = L.lib(), L.stream_ptr()
+        vscale = float(self.loss_weight["gp"]) / self.n_acc / B
+        mean = L.ptr(scal) + 12   # (:229: the penalty's logged mean rides on the turn-around / the tangent's BlurVH launch)
+        img = dict(size=(B, 1, self.H, self.W), dtype=torch.float32, device=self.device)
+        if form is R1Form.TURNAROUND:
+            took = deng.r1_turnaround(Dst, 0, B, 2 * B, vscale, ssq, mean)
+        elif form is R1Form.FUSED_ADJOINT:
+            vg = torch.empty(**img)
+            took = deng.backward_input(Dst, 0, B, vg, r1=(vscale, ssq))
+        else:
+            g, vg = torch.empty(**img), torch.empty(**img)
+            took = deng.backward_input(Dst, 0, B, g)
+            if ssq is None:
+                ssq = torch.empty(B, dtype=torch.float32, device=self.device)
+                L.check(lib.dg_sample_sum(L.ptr(g), B, self.H * self.W, 1, L.ptr(ssq), sp), "dg_sample_sum")
+            else:
+                L.check(lib.dg_sample_sum_acc(L.ptr(g), B, self.H * self.W, 1, L.ptr(ssq), sp), "dg_sample_sum_acc")
+            L.check(lib.dg_scale(L.ptr(g), vscale, g.numel(), L.ptr(vg), sp), "dg_scale")
+        if not took:
+            raise RuntimeError(f"R1 form {form.name}: the engine does not take a {self.H}x{self.W} image in it")
+        if form is not R1Form.TURNAROUND:
+            deng.forward(Dst, vg, 2 * B, tangent_of=0, mean=(ssq, B, mean))
+
+    def _d_weight_grads(self, deng, Dst, B, gp, rs, dy, fused):
+        """D's weight gradients of one micro-batch by layer group, then the final conv's terms behind layer 4.  Data-parallel
+        runs (one micro-batch): the gradient exchange is cut into two buckets at d4_w (73 % of D's bytes live in [d4_w, end))
+        and the weight gradients are formed last layer first, so the large bucket ("D.hi", issued here) travels while the
+        three smaller layers' gradients are still being computed.  fused: the loss step's launch already formed the final
+        conv's loss term.  Returns the terms left to the optimizer's launch (`FlatAdam.step` extra), or None."""
+        bucketed, extra_D = self._bucketed(), None
+        # bucketed, layer 4 first (its bucket travels beside the rest); else one group
+        for layers in (((4,), (3, 2, 1)) if bucketed else (((4, 3, 2, 1),) if gp > 0 else ((1, 2, 3, 4),))):
+            if gp > 0:
+                # real (weighted by dLoss/dy_real) + fake halves and tangent (x) real chain, one launch per fat layer
+                deng.wgrad_r1(Dst, B, rs, layers=layers)
+            else:
+                deng.wgrad(Dst, 0, 0, 2 * B, None, layers=layers)
+            if 4 in layers:   # ... followed by the final conv's weight-gradient terms and the exchange of [d4_w, end)
+                if not fused:
+                    deng.final_wgrad(Dst, 0, 2 * B, dy)
+                if gp > 0 and not bucketed and self.n_acc == 1 and not deng.x2 and self.optim_D.will_fuse(self.dtype):
+                    # (round 6: the R1 term of the final conv's weight gradient is summed by the optimizer's launch)
+                    extra_D = {"final_w": deng.final_wgrad_term(2 * B, B)}
+                elif gp > 0:
+                    deng.final_wgrad(Dst, 2 * B, B, None)
+                if bucketed:
+                    self._allreduce_async("D.hi", Dst.grad[Dst.seg["d4_w"].off:])
+        return extra_D
 
     # ------------------------------------------------------------------ G phase (reference :240-316)
     @_own_counters
@@ -937,7 +977,7 @@ class Trainer:
         the next step on the route is GATHER or MATERIALISED."""
         Gst = _backbone(self.G).store
         pl_on = "pl" in self.criterion
-        if "G" in getattr(self, "_grads_zeroed", ()):
+        if "G" in self._grads_zeroed:
             self._grads_zeroed.discard("G")     # (filled with the step's arena: _begin_step)
         else:
             self.optim_G.zero_grad(skip=("proj_w",) if self.n_acc == 1 else ())
@@ -1111,7 +1151,7 @@ class Trainer:
         gp = self._geng_pl
         Bp = gp.ws_B
         n = B + 2 * Bp
-        if getattr(self, "_cat", None) is None or self._cat[0].numel() != n * geng.dp[0].numel() // B:
+        if self._cat is None or self._cat[0].numel() != n * geng.dp[0].numel() // B:
             self._cat = (self._like(geng.dp[0], n * geng.dp[0].numel() // B), geng.zT.new_empty(n * geng.zT.numel() // B))
         d, z = self._cat
         nd, nzv = geng.dp[0].numel(), geng.zT.numel()
@@ -1169,7 +1209,6 @@ class Trainer:
     SCALAR_RING = 64
 
     def _use_ring(self):
-        import os
         return self.world == 1 and self.n_acc == 1 and os.environ.get("DUSTY_GAN_SCALAR_RING", "1") != "0"
 
     def _ring_slot(self):
@@ -1216,8 +1255,6 @@ class Trainer:
         return scal[:end] if "gp" in self.criterion else torch.cat((scal[:3], scal[4:end]))
 
     def _graph_eligible(self, reals, rands):
-        import os
-        from .. import engine as E
         # world > 1: the step is replayed as hipGraph segments with the collectives issued between them (eager launches
         # cost more host time than the kernels take); DUSTY_GAN_GRAPH_DDP=0 falls back to eager launches
         if self.world > 1 and os.environ.get("DUSTY_GAN_GRAPH_DDP", "1") == "0":
@@ -1226,108 +1263,124 @@ class Trainer:
         return (reals is None and rands is None and self.use_graph and E.PROFILE is None
                 and getattr(getattr(self, "dataset", None), "graph_safe", False))
 
-    def _step_graph(self):
+    def _step_graph(self, batch=None):
         """hipGraph replay of the whole iteration (device-resident data): the ~180 kernel launches of a
         step cost ~5 ms of Python/ctypes time when issued one by one, more than the kernels themselves; captured once
         they replay from one host call.  Everything that changes between steps lives in device memory (Philox
-        counters, Adam step counts, the input batch in a static buffer), so replays draw fresh randomness."""
+        counters, Adam step counts, the input batch in a static buffer), so replays draw fresh randomness.
+        batch: what a first capture attempt drew, when this is its second one (hipGraph segments)."""
         # an eager draw between two steps (validation() / generate() call sample_latents on the trainer's generator)
         # leaves its counter advance queued: apply it now, outside the graph - a replay reads the device counters as
         # they are, and an advance still pending when the capture starts would be baked into the graph and re-added
         # on every replay
         L.Counters.flush()
         pooled = self._pooled()
-        batch = getattr(self, "_retry_batch", None)
         if batch is None:
-            # num_accumulation micro-batches per step (utils/context_manager.py:21-35): the host loader moves on by as many
-            # batches as the device-side pool index does inside the replay
-            batches = [self._next_batch() for _ in range(self.n_acc)]
-            self._drawn_ahead = self.n_acc
-            batch = batches[0] if self.n_acc == 1 else batches
-            if pooled and self._pool_ctr is not None and self._pool_host != self.batches_drawn - self.n_acc:
-                # another consumer of the loader (an eager step with injected draws, a script calling _next_batch) has moved
-                # the host position past the device-side pool index: the step fetches what the loader just yielded
-                L.Counters.flush_if(self._pool_ctr)
-                self._pool_host = self.batches_drawn - self.n_acc
-                self._pool_ctr.fill_(self._pool_host)
-            if pooled and self._resident() is not None:
-                # the flip tables of the epochs this step's micro-batches fall in, written before anything is launched
-                self._resident().ensure_tables(self.batches_drawn - self.n_acc, self.batches_drawn - 1)
+            batch = self._stage_batches(pooled)
         mbs = batch if isinstance(batch, list) else [batch]
-
-        def fetch_all(srcs):   # every micro-batch's fetch_reals at the head of the step (the first one opens the arena)
-            return [self._fetch_reals_in_step(b, pooled, begin=(j == 0)) for j, b in enumerate(srcs)]
         if self._graph is None:
             if self._eager_steps < 2:  # warm-up: workspaces, shadows and counters must exist before the capture
                 self._eager_steps += 1
-                return self._step_eager(reals=fetch_all(mbs))
-            if not pooled:  # any other fixed-shape device loader: the replay reads static copies of the batch
-                self._g_pol = batch["depth"].to(self.device).clone()
-                self._g_mask = batch["mask"].to(self.device).clone()
-            torch.cuda.synchronize()
-            # One hipGraph per stretch between collectives (world > 1: gradient all-reduce of D, operand gather and
-            # tail all-reduce of G); a single graph when world == 1.  The segments share one memory pool, so a
-            # workspace allocated while capturing one segment stays valid in the next.
-            self._cap, self._cap_pool = [], torch.cuda.graph_pool_handle()
+                return self._step_eager(reals=self._fetch_all(mbs, pooled))
             counts = (self.optim_D.step_count, self.optim_G.step_count)
-            in_graph, err = self._comm_in_graph, None
-            try:
-                self._cap_open()
-                src = mbs if pooled else [{"depth": self._g_pol, "mask": self._g_mask}]
-                self._g_out = self._step_eager(reals=fetch_all(src))
-                self._cap_close()
-            except BaseException as exc:
-                err = exc
-                if self._cap_cur is not None:
-                    # the split-K partials queued by the aborted capture were never written: forget them while the CAPTURE
-                    # stream is still current (E.WGRAD_WS is per stream - after __exit__ the default stream's workspace would be
-                    # the one reset, and the retry on this capture stream would reduce never-written memory into the gradients
-                    # on every replay).  The workspace itself goes too: its buffer was allocated inside the aborted capture's
-                    # memory pool, which dies with that capture - the retry allocates a fresh one in ITS pool.
-                    E.WGRAD_WS.discard()
-                    E.WGRAD_WS.drop_stream()
-                    try:
-                        self._cap_cur[1].__exit__(None, None, None)
-                    except BaseException:
-                        pass
-                else:
-                    E.WGRAD_WS.discard()
-                self._cap_cur = None
-                self._gc_restore()
-                L.Counters.pending.clear()  # (advances queued by the aborted capture were never going to run)
-                L.Counters.snap, L.Counters.ride = None, False
-                self._works.clear()
-                if not isinstance(exc, Exception):   # KeyboardInterrupt / SystemExit: not a refused capture
-                    self._cap = None
-                    raise
+            err, in_graph = self._capture_step(batch, mbs, pooled)
             # The ranks take ONE decision about collectives inside the graph: a rank that fell back to segments beside peers
             # replaying captured collectives would be the only one making host-side calls (and a mixed job has never run
             # anywhere).  Nothing has executed yet - the capture only recorded - so every rank reaches this exchange.
             everyone = D_.all_agree(err is None, self.device) if (in_graph and self.world > 1) else err is None
             what = D_.capture_decision(in_graph, err is None, everyone, self.world)
+            # the capture did not execute anything, but the host mirrors of the Adam step counts advanced with what it recorded
+            self.optim_D.step_count, self.optim_G.step_count = counts
             if what != "keep":
-                import warnings
                 self._cap = None
                 self._works.clear()
-                self.optim_D.step_count, self.optim_G.step_count = counts   # nothing was executed: restore the host mirrors
                 self._mb = []
                 if what == "segments":
                     why = f"{type(err).__name__}: {err}" if err is not None else "a peer rank could not capture them"
                     warnings.warn(f"capturing the step with its collectives failed ({why}); falling back to hipGraph segments")
                     self._comm_in_graph = False
                     torch.cuda.synchronize()
-                    return self._step_graph_retry(batch, pooled)
+                    return self._step_graph(batch)
                 if what == "raise":
                     raise err
                 # multi-rank: a runtime that refuses the capture must not take the job down - keep launching eagerly
                 warnings.warn("hipGraph capture of the training step failed; continuing with eager launches")
                 self.use_graph = False
-                return self._step_eager(reals=fetch_all(mbs))
+                return self._step_eager(reals=self._fetch_all(mbs, pooled))
             self._comm_captured = in_graph
             self._graph, self._cap = self._cap, None
-            # the capture did not execute anything, but the host mirrors of the Adam step counts advanced once
-            self.optim_D.step_count -= 1
-            self.optim_G.step_count -= 1
+        return self._replay(batch, pooled)
+
+    def _stage_batches(self, pooled):
+        """draw the step's batch(es) from the host loader and bring the device-side position in line with it"""
+        # num_accumulation micro-batches per step (utils/context_manager.py:21-35): the host loader moves on by as many
+        # batches as the device-side pool index does inside the replay
+        batches = [self._next_batch() for _ in range(self.n_acc)]
+        self._drawn_ahead = self.n_acc
+        if pooled and self._pool_ctr is not None and self._pool_host != self.batches_drawn - self.n_acc:
+            # another consumer of the loader (an eager step with injected draws, a script calling _next_batch) has moved
+            # the host position past the device-side pool index: the step fetches what the loader just yielded
+            L.Counters.flush_if(self._pool_ctr)
+            self._pool_host = self.batches_drawn - self.n_acc
+            self._pool_ctr.fill_(self._pool_host)
+        if pooled and self._resident() is not None:
+            # the flip tables of the epochs this step's micro-batches fall in, written before anything is launched
+            self._resident().ensure_tables(self.batches_drawn - self.n_acc, self.batches_drawn - 1)
+        return batches[0] if self.n_acc == 1 else batches
+
+    def _fetch_all(self, srcs, pooled):
+        """every micro-batch's fetch_reals at the head of the step (the first one opens the arena)"""
+        return [self._fetch_reals_in_step(b, pooled, begin=(j == 0)) for j, b in enumerate(srcs)]
+
+    def _capture_step(self, batch, mbs, pooled):
+        """record one `_step_eager` into `self._cap` (nothing executes).  Returns (err, in_graph): the exception that ended
+        the capture, cleaned up after (`_abort_capture`), or None; whether the collectives were to be nodes of the graph."""
+        if not pooled:  # any other fixed-shape device loader: the replay reads static copies of the batch
+            self._g_pol = batch["depth"].to(self.device).clone()
+            self._g_mask = batch["mask"].to(self.device).clone()
+        torch.cuda.synchronize()
+        # One hipGraph per stretch between collectives (world > 1: gradient all-reduce of D, operand gather and
+        # tail all-reduce of G); a single graph when world == 1.  The segments share one memory pool, so a
+        # workspace allocated while capturing one segment stays valid in the next.
+        self._cap, self._cap_pool = [], torch.cuda.graph_pool_handle()
+        in_graph = self._comm_in_graph
+        try:
+            self._cap_open()
+            src = mbs if pooled else [{"depth": self._g_pol, "mask": self._g_mask}]
+            self._g_out = self._step_eager(reals=self._fetch_all(src, pooled))
+            self._cap_close()
+        except BaseException as exc:
+            self._abort_capture(exc)
+            return exc, in_graph
+        return None, in_graph
+
+    def _abort_capture(self, exc):
+        """leave the capture that `exc` ended; re-raises what is not a refused capture (KeyboardInterrupt / SystemExit)"""
+        if self._cap_cur is not None:
+            # the split-K partials queued by the aborted capture were never written: forget them while the CAPTURE
+            # stream is still current (E.WGRAD_WS is per stream - after __exit__ the default stream's workspace would be
+            # the one reset, and the retry on this capture stream would reduce never-written memory into the gradients
+            # on every replay).  The workspace itself goes too: its buffer was allocated inside the aborted capture's
+            # memory pool, which dies with that capture - the retry allocates a fresh one in ITS pool.
+            E.WGRAD_WS.discard()
+            E.WGRAD_WS.drop_stream()
+            try:
+                self._cap_cur[1].__exit__(None, None, None)
+            except BaseException:
+                pass
+        else:
+            E.WGRAD_WS.discard()
+        self._cap_cur = None
+        self._gc_restore()
+        L.Counters.pending.clear()  # (advances queued by the aborted capture were never going to run)
+        L.Counters.snap, L.Counters.ride = None, False
+        self._works.clear()
+        if not isinstance(exc, Exception):
+            self._cap = None
+            raise exc
+
+    def _replay(self, batch, pooled):
+        """one step from the captured graph: the static batch, the graph (segments and the calls between them), the host mirrors"""
         if not pooled:
             self._g_pol.copy_(batch["depth"], non_blocking=True)
             self._g_mask.copy_(batch["mask"], non_blocking=True)
@@ -1372,14 +1425,6 @@ class Trainer:
                 if hip.hipGraphNodeGetType(C.c_void_p(nd), C.byref(t)) == 0 and t.value == 0:   # hipGraphNodeTypeKernel
                     total += 1
         return total
-
-    def _step_graph_retry(self, batch, pooled):
-        """second capture attempt of `_step_graph` (segments) on the batch the first one drew"""
-        self._retry_batch = batch
-        try:
-            return self._step_graph()
-        finally:
-            self._retry_batch = None
 
     @_own_counters
     def step(self, i=0, reals=None, rands=None):
@@ -1481,9 +1526,7 @@ class Trainer:
         reference); every rank's streams are `job seed + 7919 rank` and every rank makes the same number of draws per
         step, so rank r's position is the writer's with its own seed: same counter offsets, same loader position, and
         its fixed evaluation latents are the first draw of its own stream (what __init__ just made)."""
-        from ..utils.rng import Philox
         if int(st.get("world", 1)) != self.world:
-            import warnings
             warnings.warn("checkpoint position belongs to another world size; random streams and the loader restart")
             return
         shift = 7919 * (_rank() - int(st.get("rank", 0)))
@@ -1508,7 +1551,7 @@ class Trainer:
         src = getattr(self, "dataset", None)
         from ..datasets.resident import ResidentScanLoader
         from ..datasets.scans import ScanLoader
-        inner = getattr(self, "_scan_loader", None)
+        inner = self._scan_loader
         if isinstance(inner, (ScanLoader, ResidentScanLoader)):   # (either resumes the other's checkpoint: same position)
             per = len(inner)
             inner.epoch, inner.skip = n // per, n % per
@@ -1519,7 +1562,6 @@ class Trainer:
     @_own_counters
     def save_models(self, suffix, step, directory="models"):
         """reference :395-409 (same keys, reference-shaped tensors)"""
-        import os
         os.makedirs(directory, exist_ok=True)
         path = osp.join(directory, "checkpoint_{}.pth".format(str(suffix)))
         torch.save(self.state(step), path)

@@ -34,6 +34,7 @@ class DiffAugment(nn.Module):
         self.mask = L.policy_mask(self.policy)
         self._seed = seed
         self._rng = None
+        self._zeros_key = None   # the (B, device) `_args` built its zero stand-ins (`_zeros`) for
 
     # ---- parameter draws
     def rng(self, device):
@@ -80,7 +81,7 @@ class DiffAugment(nn.Module):
         # stand-ins for parameters a policy does not draw: zeros, allocated once per (B, device) - two fill kernels per
         # call were ~10 of the step's ~90 tiny launches
         key = (B, str(device))
-        if getattr(self, "_zeros_key", None) != key:
+        if self._zeros_key != key:
             self._zeros = (torch.zeros(B, dtype=torch.float32, device=device),
                            torch.zeros(B, dtype=torch.int32, device=device))
             self._zeros_key = key

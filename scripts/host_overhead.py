@@ -1,7 +1,7 @@
 import sys, time; sys.path.insert(0, ".")
 import torch, argparse
 import bench
-args = argparse.Namespace(arch=None, shape=[64,1024], batch=32, gp=1.0, precision="bf16", no_augment=False)
+args = argparse.Namespace(arch=None, shape=[64,1024], batch=32, gp=1.0, pl=0.0, precision="bf16", no_augment=False)
 tr, arch = bench.make_trainer(args, 0, 0, 1)
 for i in range(5): tr.step(i)
 torch.cuda.synchronize()
