@@ -196,6 +196,8 @@ PROTOTYPES = {
     "dg_chamfer_paired": [_P, _I, _P, _I, _I, _P, _P],
     "dg_chamfer_nn": [_P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _P, _P, _P],
     "dg_emd": [_P, _I, _I, _P, _I, _I, _I, _P, _P],
+    "dg_emd_grad": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P],
+    "dg_chamfer_backward": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "dg_grid_vote": [_P, _L, _P, _I, _P, _P],
     "dg_jsd": [_P, _P, _I, _P, _P],
     "dg_pyr_down": [_P, _L, _I, _I, _P, _P],

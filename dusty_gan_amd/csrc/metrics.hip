@@ -518,20 +518,30 @@ __global__ __launch_bounds__(256) void patches_kernel(const float* __restrict__ 
 // it, so the cost sum_{k,l} match[l][k] d^2(k,l) is accumulated while the mass is produced.  One workgroup per cloud
 // pair, both clouds and the four mass vectors in LDS.  (i, j) = (blockIdx.y, blockIdx.x), or the diagonal pairing
 // (i = j) when `paired`.
-__global__ __launch_bounds__(512) void emd_kernel(const float* __restrict__ A, int n, const float* __restrict__ Bc,
-                                                  int m, int Nb, int paired, float* __restrict__ out) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char emd_lds[];
-  float4* p1 = (float4*)emd_lds;            // [n]
+// The sweeps are one device body for dg_emd and dg_emd_grad.  GRAD adds the gradient of matchcost with `match` held constant
+// (matchcostgrad1 / matchcostgrad2, :305-388): match = sum over the levels of w, and both gradients are linear in it, so they
+// are accumulated while the mass is produced, like the cost:
+//   ga[k] = gscale * sum_levels sum_l w (A_k - B_l)      in the third sweep, by the thread that owns k;
+//   gb[l] = gscale * sum_levels sum_k w (B_l - A_k)      in a FOURTH sweep per level, where a thread owns l and forms w again
+//                                                        with the third sweep's product order (the same match bits).
+// The accumulators are the output rows themselves: one thread owns row k (row l) in every level, adds the level's share to it
+// and scales it after the last, so there are no atomics, no [m,n] buffer and no LDS beyond dg_emd's.  A level's share is
+// summed in registers from zero and added to the row once: the steep levels leave large entries, and the later levels' small
+// terms added to them one at a time would each be rounded at the row's magnitude (on 520 x 1030 points one running sum over
+// all levels lay 5e-6 from the float64 gradient, the per-level sums 6e-7, which is the error of `match` itself).  The fourth sweep
+// reads what the third leaves alone (the points, ratioL, ratioR), so it follows it without a barrier.
+// Returns the thread's share of the cost; GRAD = false is dg_emd's arithmetic, statement for statement.
+template <bool GRAD>
+__device__ __forceinline__ float emd_sweeps(const float* __restrict__ a, int n, const float* __restrict__ b, int m,
+                                            unsigned char* lds, float* __restrict__ ga, float* __restrict__ gb,
+                                            float gscale) {
+  float4* p1 = (float4*)lds;                // [n]
   float4* p2 = p1 + n;                      // [m]
   float* remainL = (float*)(p2 + m);        // [n]
   float* remainR = remainL + n;             // [m]
   float* ratioL = remainR + m;              // [n]
   float* ratioR = ratioL + n;               // [m]
-  __shared__ float red[16];
   const int tid = threadIdx.x, nt = blockDim.x;
-  const int j = blockIdx.x, i = paired ? blockIdx.x : blockIdx.y;
-  const float* a = A + (long)i * n * 3;
-  const float* b = Bc + (long)j * m * 3;
   const float multiL = n >= m ? 1.f : (float)(m / n), multiR = n >= m ? (float)(n / m) : 1.f;
   for (int k = tid; k < n; k += nt) { p1[k] = make_float4(a[k * 3], a[k * 3 + 1], a[k * 3 + 2], 0.f); remainL[k] = multiL; }
   for (int l = tid; l < m; l += nt) { p2[l] = make_float4(b[l * 3], b[l * 3 + 1], b[l * 3 + 2], 0.f); remainR[l] = multiR; }
@@ -569,19 +579,122 @@ __global__ __launch_bounds__(512) void emd_kernel(const float* __restrict__ A, i
       const float4 x = p1[k];
       const float rl = ratioL[k];
       float suml = 0.f;
+      float gx = 0.f, gy = 0.f, gz = 0.f;   // this level's share, summed on its own (see above)
       for (int l = 0; l < m; ++l) {
         const float4 q = p2[l];
         const float d = (q.x - x.x) * (q.x - x.x) + (q.y - x.y) * (q.y - x.y) + (q.z - x.z) * (q.z - x.z);
         const float w = __expf(level * d) * rl * ratioR[l];
         cost += w * d;       // matchcost (:218-262): match[l][k] * d, summed over levels
         suml += w;
+        if (GRAD) { gx += w * (x.x - q.x); gy += w * (x.y - q.y); gz += w * (x.z - q.z); }
       }
       remainL[k] = fmaxf(0.0f, remainL[k] - suml);
+      if (GRAD) {
+        if (lev != 7) { gx += ga[k * 3]; gy += ga[k * 3 + 1]; gz += ga[k * 3 + 2]; }
+        const float sc = lev == -2 ? gscale : 1.f;   // the reference scales after the sum
+        ga[k * 3] = gx * sc; ga[k * 3 + 1] = gy * sc; ga[k * 3 + 2] = gz * sc;
+      }
+    }
+    if (GRAD) {
+      for (int l = tid; l < m; l += nt) {
+        const float4 q = p2[l];
+        const float rr = ratioR[l];
+        float gx = 0.f, gy = 0.f, gz = 0.f;
+        for (int k = 0; k < n; ++k) {
+          const float4 x = p1[k];
+          const float d = (q.x - x.x) * (q.x - x.x) + (q.y - x.y) * (q.y - x.y) + (q.z - x.z) * (q.z - x.z);
+          const float w = __expf(level * d) * ratioL[k] * rr;
+          gx += w * (q.x - x.x); gy += w * (q.y - x.y); gz += w * (q.z - x.z);
+        }
+        if (lev != 7) { gx += gb[l * 3]; gy += gb[l * 3 + 1]; gz += gb[l * 3 + 2]; }
+        const float sc = lev == -2 ? gscale : 1.f;
+        gb[l * 3] = gx * sc; gb[l * 3 + 1] = gy * sc; gb[l * 3 + 2] = gz * sc;
+      }
     }
     __syncthreads();
   }
+  return cost;
+}
+
+__global__ __launch_bounds__(512) void emd_kernel(const float* __restrict__ A, int n, const float* __restrict__ Bc,
+                                                  int m, int Nb, int paired, float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char emd_lds[];
+  __shared__ float red[16];
+  const int j = blockIdx.x, i = paired ? blockIdx.x : blockIdx.y;
+  const float cost = emd_sweeps<false>(A + (long)i * n * 3, n, Bc + (long)j * m * 3, m, emd_lds, nullptr, nullptr, 0.f);
   const float tot = dg_block_sum(cost, red);
-  if (tid == 0) out[paired ? (long)i : (long)i * Nb + j] = tot;
+  if (threadIdx.x == 0) out[paired ? (long)i : (long)i * Nb + j] = tot;
+}
+
+// dg_emd_grad: pair i = blockIdx.x.  gscale = 2 grad_cost[i] (the 2 of d|p - q|^2, exact).
+__global__ __launch_bounds__(512) void emd_grad_kernel(const float* __restrict__ A, int n, const float* __restrict__ Bc, int m,
+                                                       const float* __restrict__ grad_cost, float* __restrict__ cost_out,
+                                                       float* __restrict__ gradA, float* __restrict__ gradB) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char emd_lds[];
+  __shared__ float red[16];
+  const long i = blockIdx.x;
+  const float gscale = 2.f * (grad_cost ? grad_cost[i] : 1.f);
+  const float cost = emd_sweeps<true>(A + i * n * 3, n, Bc + i * m * 3, m, emd_lds, gradA + i * n * 3, gradB + i * m * 3, gscale);
+  const float tot = dg_block_sum(cost, red);
+  if (threadIdx.x == 0 && cost_out) cost_out[i] = tot;
+}
+
+// --------------------------------------------------------------------------------------------------------------
+// The Chamfer extension's backward for packed clouds (chamfer_distance.cpp:82-140 / the .cu backward): point p of cloud 1 with
+// neighbour k = idx1[p] in cloud 2 contributes t = 2 g1[p] (A_p - B_k) to gradA[p] - the DIRECT term, one writer per element -
+// and -t to gradB[k] - the SCATTERED term, any number of writers; mirrored with g2 / idx2.  The scattered terms are summed in
+// 24.40 fixed point (dg_fix40) with integer atomics, so the total does not depend on the arrival order.
+// Range: unit-space points give |A_p - B_k| <= 2 per coordinate; g is the gradient of a reduction over the distances, 1 / n
+// under a mean and 1 under a sum, so |t| <= 4 with room to spare in the codec's per-term window of 2^22; a point is the
+// neighbour of at most 2^18 others (the entry refuses larger clouds), so |total| <= 2^20 and the word holds 2^22.
+// acc: 4 u64 words per point, cloud 1's [B,n] first, then cloud 2's [B,m]: x, y, z and a flag that a term did not fit the
+// window (or was not finite) - the finish then stores NaN instead of a sum with a term missing.  ZERO AT REST: the finish
+// zeroes what it reads.  An index outside its cloud contributes nothing, on either side.
+__global__ __launch_bounds__(256) void chamfer_bwd_scatter_kernel(const float* __restrict__ A, int n, const float* __restrict__ Bc,
+                                                                  int m, int B, const float* __restrict__ g1,
+                                                                  const float* __restrict__ g2, const int* __restrict__ idx1,
+                                                                  const int* __restrict__ idx2, float* __restrict__ gradA,
+                                                                  float* __restrict__ gradB,
+                                                                  unsigned long long* __restrict__ acc) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long per = (long)n + m;
+  if (t >= B * per) return;
+  const long b = t / per;
+  const int r = (int)(t - b * per);
+  const bool first = r < n;                                   // a point of cloud 1 (else of cloud 2)
+  const int p = first ? r : r - n, np = first ? n : m, nq = first ? m : n;
+  const long bp = b * np + p;
+  const float* P = (first ? A : Bc) + bp * 3;
+  float* gd = (first ? gradA : gradB) + bp * 3;
+  const int k = (first ? idx1 : idx2)[bp];
+  if (k < 0 || k >= nq) { gd[0] = 0.f; gd[1] = 0.f; gd[2] = 0.f; return; }
+  const float* Q = (first ? Bc : A) + (b * nq + k) * 3;
+  const float g = 2.f * (first ? g1 : g2)[bp];
+  unsigned long long* cell = acc + ((first ? (long)B * n : 0l) + b * nq + k) * 4;   // the neighbour's words
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float v = g * (P[c] - Q[c]);
+    gd[c] = v;
+    long long q;
+    if (!dg_fix40(-(double)v, q)) atomicOr(cell + 3, 1ull);
+    else if (q != 0) atomicAdd(cell + c, (unsigned long long)q);
+  }
+}
+
+// grad = direct + scattered, rounded to float once; the words go back to zero
+__global__ __launch_bounds__(256) void chamfer_bwd_finish_kernel(long points_a, long points, float* __restrict__ gradA,
+                                                                 float* __restrict__ gradB,
+                                                                 unsigned long long* __restrict__ acc) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= points) return;
+  float* gd = t < points_a ? gradA + t * 3 : gradB + (t - points_a) * 3;
+  unsigned long long* cell = acc + t * 4;
+  const unsigned long long w0 = cell[0], w1 = cell[1], w2 = cell[2], bad = cell[3];
+  if (w0 | w1 | w2 | bad) { cell[0] = 0ull; cell[1] = 0ull; cell[2] = 0ull; cell[3] = 0ull; }
+  const float nan = __builtin_nanf("");
+  gd[0] = bad ? nan : (float)((double)gd[0] + dg_fix40_value((long long)w0));
+  gd[1] = bad ? nan : (float)((double)gd[1] + dg_fix40_value((long long)w1));
+  gd[2] = bad ? nan : (float)((double)gd[2] + dg_fix40_value((long long)w2));
 }
 
 }  // namespace
@@ -721,6 +834,36 @@ int dg_emd(const float* A, int Na, int n, const float* Bc, int Nb, int m, int pa
   const dim3 grid(Nb, paired ? 1 : Na);
   if (grid.y > 65535) return DG_EUNSUPPORTED;
   emd_kernel<<<grid, 512, lds, (hipStream_t)s_>>>(A, n, Bc, m, Nb, paired, out);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
+
+int dg_emd_grad(const float* A, int n, const float* Bc, int m, int B, const float* grad_cost, float* cost, float* gradA,
+                float* gradB, void* s_) {
+  if (!A || !Bc || !gradA || !gradB || B <= 0 || n <= 0 || m <= 0) return DG_EINVAL;
+  const size_t lds = (size_t)(n + m) * (16 + 8);   // dg_emd's: the gradient rows are the accumulators
+  if (lds > 150 * 1024) return DG_EUNSUPPORTED;
+  static bool opted = false;
+  if (!opted) {
+    HIP_CHECK_RET(hipFuncSetAttribute((const void*)emd_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    opted = true;
+  }
+  emd_grad_kernel<<<B, 512, lds, (hipStream_t)s_>>>(A, n, Bc, m, grad_cost, cost, gradA, gradB);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
+
+int dg_chamfer_backward(const float* A, int n, const float* Bc, int m, int B, const float* g1, const float* g2, const int* idx1,
+                        const int* idx2, float* gradA, float* gradB, unsigned long long* acc, void* s_) {
+  if (!A || !Bc || !g1 || !g2 || !idx1 || !idx2 || !gradA || !gradB || !acc || B <= 0 || n <= 0 || m <= 0) return DG_EINVAL;
+  if (n > (1 << 18) || m > (1 << 18)) return DG_EUNSUPPORTED;   // the codec's range, as dg_chamfer_nn
+  const long points = (long)B * ((long)n + m);
+  const long blocks = (points + 255) / 256;
+  if (blocks > 0x7fffffffL) return DG_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)s_;
+  chamfer_bwd_scatter_kernel<<<(unsigned)blocks, 256, 0, s>>>(A, n, Bc, m, B, g1, g2, idx1, idx2, gradA, gradB, acc);
+  HIP_CHECK_RET(hipGetLastError());
+  chamfer_bwd_finish_kernel<<<(unsigned)blocks, 256, 0, s>>>((long)B * n, points, gradA, gradB, acc);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }

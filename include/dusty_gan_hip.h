@@ -516,6 +516,31 @@ int dg_chamfer_nn(const float* A, long a_sb, long a_sp, long a_sc, int n, const 
  * the extension's semantics); paired = 0: out [Na,Nb] for all pairs.  The value is the raw cost (compute_emd of
  * utils/metrics/cov_mmd_1nna.py:12-17 divides by the point count). */
 int dg_emd(const float* A, int Na, int n, const float* Bc, int Nb, int m, int paired, float* out, void* stream);
+/* dg_emd_grad: the gradient of dg_emd's paired cost, EarthMoverDistanceFunction.backward (matchcostgrad1 / matchcostgrad2,
+ * earth_mover_distance.cu:305-437), in ONE launch and without a stored match matrix.  The reference's semantics: `match` is a
+ * constant (nothing is differentiated through approxmatch),
+ *   gradA[i][k] = grad_cost[i] sum_l 2 match[l][k] (A_k - B_l)      gradB[i][l] = grad_cost[i] sum_k 2 match[l][k] (B_l - A_k)
+ * with match = the sum over the ten annealing levels of exp(level d^2) ratioL[k] ratioR[l].  Both are accumulated while the
+ * mass is produced (dg_emd's three sweeps, plus a fourth per level in which a thread owns l), in the output rows themselves:
+ * one writer per row, no atomics, no [B,m,n] buffer, deterministic.  Paired clouds only: A [B,n,3], Bc [B,m,3], grad_cost [B]
+ * (NULL = ones; the scale is applied after the sum, as the reference does), gradA [B,n,3], gradB [B,m,3]; cost [B] (nullable)
+ * = dg_emd(..., paired = 1), bit for bit.  One workgroup per pair with dg_emd's LDS footprint, so the same cap:
+ * n + m <= 6400, DG_EUNSUPPORTED above. */
+int dg_emd_grad(const float* A, int n, const float* Bc, int m, int B, const float* grad_cost, float* cost, float* gradA,
+                float* gradB, void* stream);
+/* dg_chamfer_backward: the Chamfer extension's backward (chamfer_distance.cpp:82-140 and the .cu backward) for packed clouds
+ * A [B,n,3], Bc [B,m,3], from the gradients g1 [B,n], g2 [B,m] of the two distance vectors and the neighbour indices
+ * idx1 [B,n], idx2 [B,m] that dg_chamfer_nn returned:
+ *   gradA[i][p] += 2 g1[i][p] (A_p - B_idx1[p]),  gradB[i][idx1[p]] -= the same;     mirrored with g2 / idx2.
+ * gradA [B,n,3] and gradB [B,m,3] are OVERWRITTEN.  The term a point gives itself has one writer; the terms it receives as a
+ * neighbour are summed in 24.40 fixed point with integer atomics (order-independent: two runs agree bit for bit) and a
+ * finishing pass adds the two and rounds once.  acc: B (n + m) * 4 u64 words, ZERO AT REST (the finishing pass zeroes what it
+ * reads).  The fixed point holds |term| < 2^22 per coordinate and |total| < 2^22 at a resolution of 2^-40: unit-space
+ * points (|A_p - B_k| <= 2) and |g| up to 1 - a sum over the distances; a mean over n points gives 1 / n - stay at |term| <= 4
+ * and, with at most 2^18 points per cloud, |total| <= 2^20.  A term outside the window, or not finite, turns the entries that
+ * should have received it into NaN.  An index outside its cloud contributes nothing.  n or m above 2^18: DG_EUNSUPPORTED. */
+int dg_chamfer_backward(const float* A, int n, const float* Bc, int m, int B, const float* g1, const float* g2, const int* idx1,
+                        const int* idx2, float* gradA, float* gradB, unsigned long long* acc, void* stream);
 int dg_grid_vote(const float* pts, long P, const float* grid, int Ng, float* counters, void* stream);
 int dg_jsd(const float* P, const float* Q, int n, float* out, void* stream);
 /* SWD descriptors  utils/metrics/swd.py:16-62.  dg_pyr_down: pyramid_down (:24-30) on `planes` = B*C images
