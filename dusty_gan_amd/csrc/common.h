@@ -242,13 +242,22 @@ __device__ __forceinline__ float dg_fix2_value(long long hi, long long lo) {
 // the window is |v| < 2^22 (q < 2^62); larger or non-finite: false, and the term is left out.  Resolution 2^-40, ABSOLUTE: the
 // smallest term that survives the rasterizer's 1e-3 weight cut times exp(-3 depth) (>= 5e-3 inside the unit cube) keeps 22 bits.
 // The total is not range-checked on the device: utils/render.py refuses |value| > 8 before it launches (ValueError), which with the
-// entry points' N <= 2^18 keeps every total inside the word.
+// entry points' N <= 2^18 keeps every total inside the word.  Every other user of the codec (the Chamfer scatters, points-to-depth)
+// sizes its sums by the same cap: DG_FIX40_MAX_TERMS contributors per cloud (or pixels per image) is what the entry points admit.
+#define DG_FIX40_MAX_TERMS (1l << 18)
 __device__ __forceinline__ bool dg_fix40(double v, long long& q) {
   if (!(fabs(v) < 4194304.0)) return false;
   q = __double2ll_rn(v * 1099511627776.0);
   return true;
 }
 __device__ __forceinline__ double dg_fix40_value(long long q) { return (double)q * (1.0 / 1099511627776.0); }
+// one term into one word with an integer atomic (none for a term that rounds to zero); false: the term did not fit and is left out
+__device__ __forceinline__ bool dg_fix40_add(unsigned long long* word, double v) {
+  long long q;
+  if (!dg_fix40(v, q)) return false;
+  if (q != 0) atomicAdd(word, (unsigned long long)q);
+  return true;
+}
 
 // ---- dg_acc_add: accumulators inside the registered arena (dg_det_arena: the step's AccArena, plus a shadow of DG_DET_STRIDE
 // bytes per float, zero at rest) are summed in 32.32 in the slot's 64-bit shadow word, the ticket in the word after it.  Anything

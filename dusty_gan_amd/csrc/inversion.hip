@@ -103,10 +103,7 @@ __global__ __launch_bounds__(256) void inv_chamfer_scatter_kernel(const float* _
   if (k < 0 || k >= HW) return;
   unsigned long long* cell = acc + (b * HW + k) * 4;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    long long q;
-    if (dg_fix40((double)R[(b * 3 + c) * HW + j], q) && q != 0) atomicAdd(cell + c, (unsigned long long)q);
-  }
+  for (int c = 0; c < 3; ++c) dg_fix40_add(cell + c, (double)R[(b * 3 + c) * HW + j]);
   atomicAdd(cell + 3, 1ull);
 }
 
@@ -408,7 +405,7 @@ int dg_inv_loss_grad_add(const float* gen, long gen_sb, int from_tanh, const flo
 
 int dg_inv_chamfer_scatter(const float* R, const int* idx1, int B, long HW, unsigned long long* acc, void* s_) {
   if (!R || !idx1 || !acc || B <= 0 || HW <= 0) return DG_EINVAL;
-  if (HW > (1l << 18)) return DG_EUNSUPPORTED;
+  if (HW > DG_FIX40_MAX_TERMS) return DG_EUNSUPPORTED;
   const long n = (long)B * HW;
   inv_chamfer_scatter_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)s_>>>(R, idx1, B, HW, acc);
   HIP_CHECK_RET(hipGetLastError());
@@ -429,7 +426,7 @@ int dg_inv_chamfer_grad(const float* P, const float* R, const float* d1, const f
   if (draw_pm && cp < nheads) return DG_EINVAL;
   if (nchunk < 1 || nchunk > 65535 || B > 65535) return DG_EINVAL;
   if (nchunk > 1 && (!parts || !tickets)) return DG_EINVAL;
-  if (HW > (1l << 18)) return DG_EUNSUPPORTED;
+  if (HW > DG_FIX40_MAX_TERMS) return DG_EUNSUPPORTED;
   ChamferGradArgs a;
   a.P = P; a.R = R; a.d1 = d1; a.d2 = d2; a.idx2 = idx2; a.acc = acc; a.depth = depth; a.angle = angle; a.gout = gout;
   a.noise_pixel = noise_pixel; a.mask = mask; a.arch = arch; a.nheads = nheads; a.cp = cp; a.add = add;

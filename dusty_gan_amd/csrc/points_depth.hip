@@ -17,9 +17,8 @@
 //     (4 waves, 1024 points) streams the grid's (U, V) pairs through double-buffered LDS chunks of PD_MC pixels, every lane reading
 //     the SAME address (broadcast).  The distance is formed from DIFFERENCES - 2 packed subtractions, a packed multiply, a packed
 //     fma, 2 minima per two pairs - never from the expanded |a|^2 + |b|^2 - 2ab, whose fp32 error with angles up to pi (~1e-6) is
-//     not small against a squared pixel pitch (9e-6 at W = 2048).  The loop tracks the minimum only; per point and chunk one strict
-//     compare notes the FIRST chunk that attains the final minimum, and the lane rescans that chunk (from global memory) for the
-//     first minimum, strict `<` over ascending indices: the project's tie rule (chamfer_nn_kernel, metrics.hip).  The same lane then
+//     not small against a squared pixel pitch (9e-6 at W = 2048).  The stream and the rescan of the first chunk that attains the
+//     minimum are nn_stream.h's, shared with chamfer_nn_kernel (point_chamfer.hip): the project's tie rule.  The same lane then
 //     adds (w d_u, w) to the two u64 words of pixel id in 24.40 fixed point (dg_fix40) with integer atomics.  d_u, not d_m: a term
 //     stays <= 1, inside dg_fix40's range analysis (<= 2^18 points per cloud: a total <= 2^58); the finish multiplies by
 //     max_depth.  Integer adds are associative, so the image is bit-identical for any permutation of the points and a graph
@@ -29,19 +28,16 @@
 //     discontinuity, and per point it is a few hundred flops against 5 H W in the search.
 //   * finish : ratio, valid, normalised depth, drop_value fill; zeroes the words (ZERO AT REST, as dg_splat_accum's).
 #include "common.h"
+#include "nn_stream.h"
 #include "points_body.h"
 
 namespace {
-
-typedef float f2 __attribute__((ext_vector_type(2)));
 
 constexpr int PD_THREADS = 256;
 constexpr int PD_PT = 4;                      // points per lane
 constexpr int PD_WPTS = 64 * PD_PT;           // points per wave
 constexpr int PD_BPTS = 4 * PD_WPTS;          // points per workgroup
 constexpr int PD_MC = 512;                    // pixels per LDS chunk (4 KB), two buffers
-constexpr int PD_LD = PD_MC / PD_THREADS;     // chunk pixels loaded per thread
-#define PD_MAX (1l << 18)                     // points per cloud (dg_fix40's range analysis) and pixels per image
 
 // (pd_point, the per-point body, lives in points_body.h: raydrop.hip's pixel winner shares it)
 
@@ -62,7 +58,7 @@ __global__ __launch_bounds__(PD_THREADS) void points_search_kernel(const float* 
         if (p0 + e < N) idx[(long)b * N + p0 + e] = -1;
     return;
   }
-  f2 pu[PD_PT / 2], pv[PD_PT / 2];
+  f2 pa[2][PD_PT / 2];   // (u, v)
   unsigned part = 0;   // bit e: point p0 + e takes part
 #pragma unroll
   for (int e = 0; e < PD_PT; ++e) {
@@ -70,63 +66,16 @@ __global__ __launch_bounds__(PD_THREADS) void points_search_kernel(const float* 
     double wd, w;
     if (p0 + e < nb && pd_point(cloud + (long)(p0 + e) * stride, min_depth, max_depth, tau, u, v, wd, w)) part |= 1u << e;
     else u = v = 0.f;   // an idle slot searches for (0, 0) and stores nothing
-    pu[e >> 1][e & 1] = u;
-    pv[e >> 1][e & 1] = v;
+    pa[0][e >> 1][e & 1] = u;
+    pa[1][e >> 1][e & 1] = v;
   }
   const float* U = angle;
   const float* V = angle + HW;
-  const int nchunk = (HW + PD_MC - 1) / PD_MC;
-  float r[PD_LD][2];
-  auto fetch = [&](int c) {
-#pragma unroll
-    for (int k = 0; k < PD_LD; ++k) {
-      const int p = c * PD_MC + k * PD_THREADS + tid;
-      const int pp = p < HW ? p : 0;   // the last chunk's tail repeats pixel 0: chunk 0 holds it first
-      r[k][0] = U[pp]; r[k][1] = V[pp];
-    }
-  };
-  auto commit = [&](int buf) {
-#pragma unroll
-    for (int k = 0; k < PD_LD; ++k) qbuf[buf][k * PD_THREADS + tid] = make_float2(r[k][0], r[k][1]);
-  };
+  auto load = [&](int k, float (&q)[2]) { q[0] = U[k]; q[1] = V[k]; };
   f2 rmin[PD_PT / 2];
   int wch[PD_PT];
-#pragma unroll
-  for (int h = 0; h < PD_PT / 2; ++h) {
-    rmin[h] = (f2){3.0e38f, 3.0e38f};
-    wch[2 * h] = 0; wch[2 * h + 1] = 0;
-  }
-  fetch(0);
-  commit(0);
-  __syncthreads();
-  for (int c = 0; c < nchunk; ++c) {
-    const int buf = c & 1;
-    if (c + 1 < nchunk) fetch(c + 1);
-    f2 was[PD_PT / 2];
-#pragma unroll
-    for (int h = 0; h < PD_PT / 2; ++h) was[h] = rmin[h];
-#pragma unroll 4
-    for (int t = 0; t < PD_MC; ++t) {
-      const float2 q = qbuf[buf][t];
-      const f2 qu = (f2){q.x, q.x}, qv = (f2){q.y, q.y};
-#pragma unroll
-      for (int h = 0; h < PD_PT / 2; ++h) {
-        const f2 du = qu - pu[h], dv = qv - pv[h];
-        f2 d = du * du;
-        d = __builtin_elementwise_fma(dv, dv, d);
-        rmin[h][0] = __builtin_fminf(rmin[h][0], d[0]);
-        rmin[h][1] = __builtin_fminf(rmin[h][1], d[1]);
-      }
-    }
-#pragma unroll
-    for (int h = 0; h < PD_PT / 2; ++h) {
-      if (rmin[h][0] < was[h][0]) wch[2 * h] = c;
-      if (rmin[h][1] < was[h][1]) wch[2 * h + 1] = c;
-    }
-    if (c + 1 < nchunk) commit(buf ^ 1);
-    __syncthreads();
-  }
-  // the first minimum inside the winning chunk (the same operations as the stream: the same distances, bit for bit), then the sums
+  nn_stream_first<2, PD_PT, PD_MC, PD_THREADS, 4>(load, HW, qbuf, pa, rmin, wch);
+  // the first minimum inside the winning chunk, then the sums
   unsigned long long* img = acc + (long)b * HW * 2;
 #pragma unroll
   for (int e = 0; e < PD_PT; ++e) {
@@ -134,16 +83,8 @@ __global__ __launch_bounds__(PD_THREADS) void points_search_kernel(const float* 
     if (p >= N) continue;
     int id = -1;
     if (part >> e & 1) {
-      const int k0 = wch[e] * PD_MC, k1 = min(HW, k0 + PD_MC);
-      const float u = pu[e >> 1][e & 1], v = pv[e >> 1][e & 1];
-      float best = 3.0e38f;
-      id = k0;
-      for (int k = k0; k < k1; ++k) {
-        const float du = U[k] - u, dv = V[k] - v;
-        float d = du * du;
-        d = __builtin_fmaf(dv, dv, d);
-        if (d < best) { best = d; id = k; }
-      }
+      const float x[2] = {pa[0][e >> 1][e & 1], pa[1][e >> 1][e & 1]};
+      id = nn_first_in_chunk<2, PD_MC>(load, HW, wch[e], x);
       float uu, vv;
       double wd, w;
       pd_point(cloud + (long)p * stride, min_depth, max_depth, tau, uu, vv, wd, w);
@@ -180,7 +121,7 @@ extern "C" int dg_points_to_depth(const float* rec, long rec_sb, int stride, con
   if ((stride != 3 && stride != 4) || rec_sb < (long)N * stride) return DG_EINVAL;
   if (!(min_depth >= 0.0 && max_depth > min_depth && max_depth < INFINITY) || !(tau >= 0.0 && tau <= 16.0)) return DG_EINVAL;
   const long hw = (long)H * W;
-  if (hw > PD_MAX || N > PD_MAX) return DG_EUNSUPPORTED;
+  if (hw > DG_FIX40_MAX_TERMS || N > DG_FIX40_MAX_TERMS) return DG_EUNSUPPORTED;   // points per cloud and pixels per image
   hipStream_t s = (hipStream_t)s_;
   points_search_kernel<<<dim3((N + PD_BPTS - 1) / PD_BPTS, B), PD_THREADS, 0, s>>>(rec, rec_sb, stride, counts, N, angle, (int)hw,
                                                                                  min_depth, max_depth, tau, acc, idx);

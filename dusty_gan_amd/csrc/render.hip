@@ -21,8 +21,6 @@
 
 namespace {
 
-#define SPLAT_MAX_POINTS (1l << 18)   // per cloud: the range analysis of dg_fix40
-
 inline int nblk(long n) { return (int)((n + 255) / 256); }
 
 // one corner: value[c] x wt into the C words of cell (hs, ws); wt = 0 where the clamp moved the index or wt < 1e-3
@@ -30,10 +28,7 @@ __device__ __forceinline__ void splat_corner(double wt, double hs, double ws, co
                                              unsigned long long* __restrict__ img) {
   if (!(wt >= 1e-3)) return;
   unsigned long long* cell = img + ((long)hs * W + (long)ws) * C;
-  for (int c = 0; c < C; ++c) {
-    long long q;
-    if (dg_fix40(val[c] * wt, q) && q != 0) atomicAdd(cell + c, (unsigned long long)q);
-  }
+  for (int c = 0; c < C; ++c) dg_fix40_add(cell + c, val[c] * wt);
 }
 
 // bilinear_rasterizer's body for one point (render.py:79-124); img = this sample's [H,W,C] words
@@ -146,7 +141,7 @@ extern "C" {
 int dg_splat_accum(const float* coords, const float* values, int B, long N, int C, int H, int W, unsigned long long* acc,
                    void* s_) {
   if (!coords || !values || !acc || B <= 0 || N <= 0 || C < 1 || C > 4 || H <= 0 || W <= 0) return DG_EINVAL;
-  if (N > SPLAT_MAX_POINTS || (long)H * W > 0x7FFFFFFFl) return DG_EUNSUPPORTED;
+  if (N > DG_FIX40_MAX_TERMS || (long)H * W > 0x7FFFFFFFl) return DG_EUNSUPPORTED;
   const long total = (long)B * N;
   splat_accum_kernel<<<nblk(total), 256, 0, (hipStream_t)s_>>>(coords, values, total, N, C, H, W, acc);
   HIP_CHECK_RET(hipGetLastError());
@@ -156,7 +151,7 @@ int dg_splat_accum(const float* coords, const float* values, int B, long N, int 
 int dg_render_points(const float* xyz, const float* normals, int B, long N, int L, const float* R, int R_batched, const float* t,
                      int t_batched, double focal, unsigned long long* acc, void* s_) {
   if (!xyz || !normals || !acc || B <= 0 || N <= 0 || L < 2 || L > 32768) return DG_EINVAL;
-  if (N > SPLAT_MAX_POINTS) return DG_EUNSUPPORTED;
+  if (N > DG_FIX40_MAX_TERMS) return DG_EUNSUPPORTED;
   const long total = (long)B * N;
   render_points_kernel<<<nblk(total), 256, 0, (hipStream_t)s_>>>(xyz, normals, total, N, L, R, R_batched ? 9 : 0, t,
                                                                  t_batched ? 3 : 0, focal, acc);

@@ -94,7 +94,7 @@ class ChamferState:
         dev = inv_ref.device
         B, _, H, W = inv_ref.shape
         HW = H * W
-        if HW > (1 << 18):
+        if HW > (1 << 18):   # csrc/common.h DG_FIX40_MAX_TERMS
             raise ValueError("the Chamfer term holds at most 2^18 points per scan")
         assert (H, W) == (lidar.H, lidar.W)
         self.tol = float(tol)

@@ -1472,7 +1472,7 @@ class Trainer:
         """reference :342-393: real (validation split) vs synthetic (G_ema) sets of equal size N ->
         SWD on the 2-D inverse-depth maps, JSD on the halved point clouds, COV / MMD / 1-NNA with the Chamfer distance
         on clouds downsampled to `solver.validation.num_points` by furthest point sampling.  Every stage runs on the
-        GPU (csrc/lidar_io.hip, csrc/metrics.hip); returns dict[str,float] with the reference's keys."""
+        GPU (csrc/lidar_io.hip, csrc/metrics.hip, csrc/point_fps.hip, csrc/point_chamfer.hip); returns dict[str,float] with the reference's keys."""
         from ..utils.metrics import compute_cov_mmd_1nna, compute_jsd, compute_swd
         from ..utils.sampling import downsample_point_clouds
         num_points = int(self.cfg.solver.validation.num_points)

@@ -18,7 +18,7 @@ from .. import _lib as L
 from .render import _workspace   # zero-at-rest u64 words per (device, stream, size), shared with the renderers
 
 TAU_MAX = 16.0          # dg_points_to_depth: exp(-tau) stays 17 bits above the sums' 2^-40 quantum
-MAX_POINTS = 1 << 18    # its points per cloud and pixels per image (dg_fix40's range analysis)
+MAX_POINTS = 1 << 18    # its points per cloud and pixels per image (csrc/common.h DG_FIX40_MAX_TERMS)
 
 
 class LiDAR:

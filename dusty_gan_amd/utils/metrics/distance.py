@@ -1,6 +1,6 @@
 """Chamfer distance between sets of point clouds -- reference: utils/metrics/distance/cd/ (CUDA extension) as used by
 utils/metrics/cov_mmd_1nna.py:20-52.  The reference evaluates one row of the distance matrix per Python iteration;
-here a whole [Na,Nb] matrix of directed means is one launch (csrc/metrics.hip chamfer_dir_kernel).
+here a whole [Na,Nb] matrix of directed means is one launch (csrc/point_chamfer.hip chamfer_dir_kernel).
 The two distances are also differentiable, under the reference's names (utils/metrics/distance/__init__.py):
 chamfer_distance / ChamferDistanceFunction / ChamferDistance and earth_mover_distance / EarthMoverDistanceFunction /
 EarthMoverDistance, with the explicit forms chamfer_backward and earth_mover_distance_grad underneath."""
@@ -57,7 +57,7 @@ def _emd_cost(a, b):
 
 def earth_mover_distance(xyz1, xyz2):
     """cost[b] of the approximate matching between xyz1[b] and xyz2[b] (reference: utils/metrics/distance/emd/,
-    EarthMoverDistanceFunction.forward): approxmatch + matchcost in one kernel (csrc/metrics.hip emd_kernel).  With an input
+    EarthMoverDistanceFunction.forward): approxmatch + matchcost in one kernel (csrc/point_emd.hip emd_kernel).  With an input
     that requires grad the cost is a node of the autograd graph (EarthMoverDistanceFunction); otherwise the launch is the same
     and nothing is recorded."""
     a, b = _prep(xyz1), _prep(xyz2)

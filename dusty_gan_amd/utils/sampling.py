@@ -1,5 +1,5 @@
 """Furthest point sampling -- reference: utils/sampling/fps/furthest_point_sampling.py:21-93 (CUDA extension
-furthest_point_sampling.cu).  One kernel (csrc/metrics.hip fps_kernel) selects and gathers.
+furthest_point_sampling.cu).  One kernel (csrc/point_fps.hip fps_kernel) selects and gathers.
 Point maps ([B,3,H,W], what dg_inv_to_xyz writes and what a scan's "xyz" is) are sampled where they lie by dg_fps_map:
 the same selection, bit for bit, without the transposed [B,HW,3] copy and, up to 65 536 points, without a workspace."""
 import torch

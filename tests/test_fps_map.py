@@ -1,4 +1,4 @@
-"""dg_fps_map (csrc/metrics.hip): furthest point sampling on strided clouds - planar point maps with the running minima on
+"""dg_fps_map (csrc/point_fps.hip): furthest point sampling on strided clouds - planar point maps with the running minima on
 chip (16 and 64 slots per thread), everything else through the workspace - must return what dg_fps returns on the packed
 copy of the same points, bit for bit, and with it what the reference's own kernel recorded (tests/golden/fps_emd.npz)."""
 import numpy as np

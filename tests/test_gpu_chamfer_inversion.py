@@ -81,6 +81,28 @@ def test_search_refuses_oversized_clouds():
     assert L.lib().dg_chamfer_nn(L.ptr(x), 0, 3, 1, 1, L.ptr(x), 0, 3, 1, n, 1, L.ptr(x), L.ptr(i), L.stream_ptr()) == L.DG_EUNSUPPORTED
 
 
+@pytest.mark.parametrize("planar", (False, True))
+def test_search_lowest_index_across_chunks_and_the_repeated_tail(planar):
+    """The streamed search's tie rule (csrc/nn_stream.h), where only the chunk walk can get it wrong: m = 1025 targets are three
+    LDS chunks of 512, the last holding ONE real entry and 511 repeats of entry 0.  Chunk 1 repeats chunk 0 point for point and
+    B[1024] = B[3], so every query has its minimum in two or three chunks: the first chunk must win, and inside it the lowest
+    index.  All coordinates are multiples of 2^-10 below 1, so every squared distance (a multiple of 2^-20 below 4) is exact in
+    float32: idx equals the float64 first minimum and dist its value, bit for bit."""
+    k = torch.arange(512)
+    first = torch.stack([k & 255, k >> 8, (k * 37) & 255], dim=1).double() / 256.0   # distinct: (x, y) determines k
+    b = torch.cat([first, first, first[3:4]])
+    assert b.shape[0] == 1025 and len({tuple(p) for p in first.tolist()}) == 512
+    a = torch.stack([b[0], b[3], b[511], b[300] + torch.tensor([2.0 ** -10, 0.0, 0.0], dtype=torch.float64),
+                     torch.tensor([0.9990234375, 0.5, 0.25], dtype=torch.float64)])
+    best, want = U.nn_first(a, b)
+    assert want[:4].tolist() == [0, 3, 511, 300] and int(want.max()) < 512         # the restatement itself
+    dist, idx = search(a[None].float(), b[None].float(), planar=planar)
+    print(f"planar={planar}: idx {idx[0].tolist()} (float64 first minimum {want.tolist()}), dist {dist[0].tolist()}")
+    assert idx[0].tolist() == want.tolist()
+    assert idx[0, :4].tolist() == [0, 3, 511, 300] and int(idx.max()) < 512
+    assert torch.equal(dist[0], best.float()) and torch.equal(dist[0].double(), best)
+
+
 def head_inputs(g, name, arch):
     """the forward pass's buffers as dg_head_post_fwd leaves them in eval mode, from the recorded step-0 head output"""
     params, gumbel, inv_ref, mask, latent0, noise, S = U.fixture_case(g, name)

@@ -1,5 +1,5 @@
-"""GPU parity tests for the validation-metric kernels: csrc/metrics.hip through the C ABI and the
-host glue of dusty_gan_amd/utils/metrics against oracle/metrics_oracle.py and tests/golden/metrics.npz."""
+"""GPU parity tests for the validation-metric kernels: csrc/metrics.hip, point_fps.hip,
+point_chamfer.hip and point_emd.hip through the C ABI and the host glue of dusty_gan_amd/utils/metrics against oracle/metrics_oracle.py and tests/golden/metrics.npz."""
 import math
 
 import numpy as np

@@ -1,4 +1,4 @@
-"""GPU tests of the differentiable point-set distances: dg_emd_grad and dg_chamfer_backward (csrc/metrics.hip) through
+"""GPU tests of the differentiable point-set distances: dg_emd_grad and dg_chamfer_backward (csrc/point_emd.hip, csrc/point_chamfer.hip) through
 dusty_gan_amd.utils.metrics, against tests/golden/emd_grad.npz and the float64 restatements of tests/emd_grad_util.py."""
 import numpy as np
 import pytest

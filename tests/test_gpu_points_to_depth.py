@@ -68,6 +68,35 @@ def test_a_tie_goes_to_the_lower_index(g):
     assert (err <= 1e-6).all()   # (float64 arithmetic on the same inputs, rounded once: the floor alone)
 
 
+def test_a_tie_across_chunks_goes_to_the_first_chunk(g):
+    """The streamed search's tie rule (csrc/nn_stream.h) across LDS chunks: a 3 x 512 grid is three chunks of 512 pixels, and
+    rows 0 and 2 hold the SAME angles, so a point aimed at row 0 is exactly as far from pixel j as from pixel 1024 + j (the same
+    bits, in any precision).  Every index must lie below 1024.  1030 points: a second workgroup, with six of them."""
+    from dusty_gan_amd.utils.lidar import LiDAR
+    lo, hi, tau = float(g["meta/min_depth"]), float(g["meta/max_depth"]), float(g["meta/tau"])
+    yaw = np.linspace(np.pi, -np.pi, 513)[:512]
+    grid = np.stack([np.repeat(np.array([0.05, -0.2, 0.05])[:, None], 512, axis=1), np.repeat(yaw[None], 3, axis=0)]).astype(np.float32)
+    rng = np.random.default_rng(23)
+    N = 1030
+    pix = rng.integers(0, 1024, N)                                   # pixels of rows 0 and 1
+    u, v = grid[0].reshape(-1)[pix].astype(np.float64), grid[1].reshape(-1)[pix].astype(np.float64)
+    xyz = (0.3 * np.stack([np.cos(u) * np.cos(v), np.cos(u) * np.sin(v), np.sin(u)], -1)).astype(np.float32)[None]
+    rd, rv, ri = PU.points_to_depth(xyz, grid, lo, hi, tau)
+    # the restatement itself (np.argmin's rule).  (A point aimed at column 0 lands across the +-pi seam, in column 511.)
+    assert ri.min() >= 0 and ri.max() < 1024 and (ri < 512).sum() > 100 and (ri[0] != pix).sum() <= 8
+    lidar = LiDAR(3, 512, lo, hi)
+    lidar.angle = torch.from_numpy(grid)[None].contiguous()
+    lidar = lidar.to(DEV)
+    depth, valid, idx = lidar.points_to_depth(torch.from_numpy(xyz).to(DEV), tau=tau, return_index=True)
+    idx = idx.cpu().numpy()
+    err = np.abs(depth[:, 0].double().cpu().numpy() - rd)
+    bound = 2 * float(g["e_ref"]) + 1e-6
+    print(f"3 x 512 grid: max idx {idx.max()}, indices off {(idx != ri).sum()}, max err {err.max():.3e}, bound {bound:.3e}")
+    assert np.array_equal(idx, ri) and idx.max() < 1024
+    assert np.array_equal(valid[:, 0].cpu().numpy(), rv) and not bool(valid[0, 0, 2].any())
+    assert (err <= bound).all()
+
+
 def test_the_order_of_the_points_does_not_matter(g, first):
     lidar, xyz, (depth, valid, idx) = first
     tau = float(g["meta/tau"])
