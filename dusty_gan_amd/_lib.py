@@ -1,10 +1,16 @@
 """ctypes binding of libdustygan_hip.so (the C ABI declared in include/dusty_gan_hip.h).
 
+The header is the one statement of that boundary: at import `read_header` takes every prototype, struct and integer code
+from it (PROTOTYPES, DgConv ... DgOptSeg, DG_*), so a new entry point is declared there and nowhere else.  The module
+imports without torch and without the built library.
+
 There is deliberately NO fallback: if the HIP library is missing, importing the product path raises.
 PyTorch is used only as the owner of device memory and of the HIP stream.
 """
 import ctypes as C
+import keyword
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -13,245 +19,134 @@ LIB_PATH = os.path.join(CSRC, "libdustygan_hip.so")
 if os.environ.get("DUSTY_GAN_LIB_DIAG"):  # kernel-development aid: `make -C csrc diag` (ablation switches, stamps);
     _d = os.environ["DUSTY_GAN_LIB_DIAG"]  # "1" or the suffix of a renamed copy (libdustygan_hip_diag<suffix>.so)
     LIB_PATH = os.path.join(CSRC, "libdustygan_hip_diag%s.so" % ("" if _d == "1" else _d))
-
-DG_OK, DG_EINVAL, DG_EUNSUPPORTED, DG_EHIP = 0, 1, 2, 3
-DG_F32, DG_BF16 = 0, 1
-DG_BF16X2 = 2   # split-bf16 pairs (hi | lo per 64 channels), 4 bytes per element: include/dusty_gan_hip.h
-MODE_S2, MODE_UP, MODE_GEMM = 0, 1, 2
-EPI_LINEAR, EPI_LRELU, EPI_MASK = 0, 1, 2
-# include/dusty_gan_hip.h: the request codes of `force` (| DG_FORCE_FP32X3), then what ran (DgConvPlan.family, DgWgradPlan.variant)
-DG_FORCE_AUTO, DG_FORCE_DIRECT, DG_FORCE_MFMA, DG_FORCE_THIN, DG_FORCE_LOCKSTEP, DG_FORCE_PINGPONG = 0, 1, 2, 3, 4, 5
-DG_FORCE_WG_REGSTAGED, DG_FORCE_WG_DMA_PAIRS, DG_FORCE_WG_DMA_NOPAIRS, DG_FORCE_PINGPONG_SINGLE, DG_FORCE_PROJ_STREAM = 6, 7, 8, 9, 10
-DG_FORCE_FP32X3 = 0x100
-DG_CONV_FAMILY_DIRECT, DG_CONV_FAMILY_MFMA, DG_CONV_FAMILY_THIN, DG_CONV_FAMILY_LOCKSTEP, DG_CONV_FAMILY_PINGPONG = 1, 2, 3, 4, 5
-DG_CONV_FAMILY_PROJ_STREAM = 6
-DG_WGRAD_VARIANT_DIRECT, DG_WGRAD_VARIANT_MFMA, DG_WGRAD_VARIANT_THIN, DG_WGRAD_VARIANT_DMA, DG_WGRAD_VARIANT_THIN_MFMA = 1, 2, 3, 5, 7
-POLICY_BITS = {"brightness": 1, "saturation": 2, "contrast": 4, "translation": 8, "cutout": 16}
-
-_ERR = {1: "DG_EINVAL (bad argument)", 2: "DG_EUNSUPPORTED (shape not supported by the requested kernel)",
-        3: "DG_EHIP (HIP runtime error)"}
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "dusty_gan_hip.h")
 
 
 class DgError(RuntimeError):
     pass
 
 
-class DgConv(C.Structure):
-    _fields_ = [
-        ("mode", C.c_int), ("adj", C.c_int), ("ring", C.c_int),
-        ("B", C.c_int), ("Hc", C.c_int), ("Wc", C.c_int),
-        ("K", C.c_int), ("N", C.c_int),
-        ("in_", C.c_void_p), ("in_sb", C.c_long), ("in_sp", C.c_long), ("in_sk", C.c_long),
-        ("out", C.c_void_p), ("out_sb", C.c_long), ("out_sp", C.c_long), ("out_sn", C.c_long),
-        ("w", C.c_void_p), ("w_st", C.c_long), ("w_sk", C.c_long), ("w_sn", C.c_long),
-        ("scale", C.c_float), ("epi", C.c_int),
-        ("bias", C.c_void_p), ("bias_mod", C.c_int),
-        ("aux", C.c_void_p), ("dbias", C.c_void_p), ("rowscale", C.c_void_p),
-        ("in_dtype", C.c_int), ("out_dtype", C.c_int), ("w_dtype", C.c_int),
-        ("nscale", C.c_void_p),
-        ("up_frag", C.c_void_p),
-        ("dbias_ws", C.c_void_p),
-        ("dbias_part", C.c_void_p),
-        ("mask_out", C.c_void_p),
-        ("mask_in", C.c_void_p),
-        ("tanh_sum_parts", C.c_void_p),
-    ]
+# C type of a by-value argument or struct field -> ctypes type; every pointer is a c_void_p, but for an ARGUMENT that points
+# to a struct of the header: POINTER(that struct)
+_SCALARS = {"int": C.c_int, "long": C.c_long, "long long": C.c_longlong, "unsigned": C.c_uint,
+            "unsigned long long": C.c_ulonglong, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "float": C.c_float,
+            "double": C.c_double, "unsigned char": C.c_ubyte}
+_C_WORDS = frozenset("const void char short int long unsigned signed float double struct enum".split())
 
 
-UP_FRAG_BYTES = 3 * 18 * 1024
-DBIAS_WS_FLOATS = 32 * 1024
+def read_header(text):
+    """(constants, structs, prototypes) of a C header written like include/dusty_gan_hip.h:
+    constants   {name: int} of every `#define DG_<NAME> <integer expression>` (earlier constants in scope) and of the entries
+                of `enum { ... }` blocks
+    structs     {name: ctypes.Structure subclass} of every `typedef struct X { ... } X;`, fields in the header's order, a
+                field named like a Python keyword with a trailing underscore (`in` -> `in_`)
+    prototypes  {name: (restype, [argtypes])} of every `int dg_x(...);` / `const char* dg_x(void);`
+    Strict: DgError, naming the declaration, for anything it does not understand - it never guesses a type."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text.replace("\\\n", " "), flags=re.S)
+    constants, structs, prototypes = {}, {}, {}
+
+    def integer(expr, what):
+        """a C integer expression of literals, operators and earlier constants (nothing else passes the character check)"""
+        src = re.sub(r"\b(0[xX][0-9a-fA-F]+|\d+)[uUlL]*\b", r"\1", expr).replace("/", "//")
+        try:
+            if not src.strip() or re.search(r"[^\w\s()+\-*/%<>|&^~]", src):
+                raise ValueError("not an integer expression")
+            value = eval(src, {"__builtins__": {}}, dict(constants))
+            if type(value) is not int:
+                raise ValueError("not an integer")
+        except Exception as e:
+            raise DgError(f"{what}: cannot evaluate `{expr.strip()}` ({e})") from None
+        return value
+
+    def declared(decl, what, arg):
+        """[(name, ctypes type)] of `type declarator {, declarator}`: one argument (arg) or one field declaration"""
+        dims = r"((?:\[\s*\w+\s*\]\s*)*)"
+        shown = " ".join(decl.split())
+        first, *more = [d.strip() for d in decl.split(",")]
+        m = re.fullmatch(r"(.*?)(\w+)\s*" + dims, first, flags=re.S)
+        rest = [re.fullmatch(r"(\**)\s*(\w+)\s*" + dims, d) for d in more]
+        if not m or None in rest:
+            raise DgError(f"{what}: cannot read `{shown}`")
+        base = " ".join(w for w in m.group(1).replace("*", " ").split() if w != "const")
+        items = [(m.group(1).count("*"), m.group(2), m.group(3))] + [(len(r.group(1)), r.group(2), r.group(3)) for r in rest]
+        if not base or any(name in _C_WORDS for _, name, _ in items) or (arg and items[0][2]):
+            raise DgError(f"{what}: cannot read `{shown}`")
+        if base not in _SCALARS and base not in structs and base != "void":
+            raise DgError(f"{what}: the type `{base}` of `{shown}` is not one the binding knows")
+        out = []
+        for stars, name, dim in items:
+            if stars:
+                t = C.POINTER(structs[base]) if arg and stars == 1 and base in structs else C.c_void_p
+            elif base in _SCALARS:
+                t = _SCALARS[base]
+            else:
+                raise DgError(f"{what}: `{base}` by value in `{shown}` is not a type the binding knows")
+            for n in reversed(re.findall(r"\w+", dim)):
+                t = t * integer(n, what)
+            out.append((name + "_" if keyword.iskeyword(name) else name, t))
+        return out
+
+    for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(DG_\w+)(.*)$|\benum\s*\w*\s*\{([^{}]*)\}", text, flags=re.M):
+        entries, nxt = [], 0
+        if m.group(1):
+            if m.group(2).startswith("("):
+                raise DgError(f"#define {m.group(1)}: a macro with arguments is not a constant")
+            entries.append((m.group(1), integer(m.group(2), "#define " + m.group(1))))
+        for ent in (m.group(3) or "").split(","):
+            name, eq, expr = (s.strip() for s in ent.partition("="))
+            if name:
+                nxt = integer(expr, "enum entry " + name) if eq else nxt
+                entries.append((name, nxt))
+                nxt += 1
+        for name, value in entries:
+            if not re.fullmatch(r"DG_\w+", name) or constants.setdefault(name, value) != value:
+                raise DgError(f"constant {name}: not a DG_ name, or defined twice with different values")
+
+    for m in re.finditer(r"\btypedef\s+struct\s*(\w*)\s*\{(.*?)\}\s*(\w*)\s*;", text, flags=re.S):
+        name, body, alias = m.groups()
+        where = f"struct {name or alias}"
+        fields = [f for decl in body.split(";") if decl.strip() for f in declared(decl, where, False)]
+        if not name or alias != name or not fields or name in structs:
+            raise DgError(f"{where}: cannot split `typedef struct {name} {{...}} {alias};` into fields")
+        structs[name] = type(name, (C.Structure,), {"_fields_": fields})
+
+    def function(m):
+        ret, name, params = " ".join(m.group(1).split()), m.group(2), m.group(3).strip()
+        restype = C.c_char_p if ret.replace(" ", "") == "constchar*" else _SCALARS.get(ret)
+        if restype is None:
+            raise DgError(f"{name}: the return type `{ret}` is not one the binding knows")
+        args = [] if params in ("", "void") else [declared(p, name, True)[0][1] for p in params.split(",")]
+        if prototypes.setdefault(name, (restype, args)) != (restype, args):
+            raise DgError(f"{name}: declared twice with different prototypes")
+        return " "
+
+    rest = re.sub(r"\b([\w \t]+?\**)\s*\b(dg_\w+)\s*\(([^()]*)\)\s*;", function, text)
+    m = re.search(r"\bdg_\w+\s*\([^;]*", rest)
+    if m:
+        raise DgError(f"`{' '.join(m.group(0).split())[:120]}`: a dg_ declaration the binding cannot read")
+    return constants, structs, prototypes
 
 
-class DgUpFrag(C.Structure):
-    _fields_ = [("off", C.c_longlong), ("frag", C.c_void_p), ("m_st", C.c_longlong), ("m_sn", C.c_longlong),
-                ("m_sk", C.c_longlong), ("N", C.c_int), ("Hc", C.c_int), ("adj", C.c_int)]
+try:
+    with open(HEADER) as _f:
+        _CONSTANTS, _STRUCTS, _SIGNATURES = read_header(_f.read())
+except OSError as _e:
+    raise DgError(f"{HEADER}: the header that declares the C ABI cannot be read ({_e})") from None
+globals().update(_CONSTANTS)   # every DG_* of the header
+globals().update(_STRUCTS)     # DgConv ... DgOptSeg
+PROTOTYPES = {_name: _argtypes for _name, (_, _argtypes) in _SIGNATURES.items()}   # name -> argtypes
 
+MODE_S2, MODE_UP, MODE_GEMM = DG_MODE_S2, DG_MODE_UP, DG_MODE_GEMM
+EPI_LINEAR, EPI_LRELU, EPI_MASK = DG_EPI_LINEAR, DG_EPI_LRELU, DG_EPI_MASK
+UP_FRAG_BYTES = DG_UP_FRAG_BYTES
+DBIAS_WS_FLOATS = DG_DBIAS_SLOTS * DG_DBIAS_SLOT_FLOATS
+XSUM_PARTS = DG_XSUM_PARTS       # partial sums per sample where a producer leaves them un-summed
+EXPORT_CHUNK = DG_EXPORT_CHUNK   # the pixels per workgroup of dg_export_points (sizes its chunk_counts workspace)
+OPT_MAX_SEG = DG_OPT_MAX_SEG
+POLICY_BITS = {"brightness": 1, "saturation": 2, "contrast": 4, "translation": 8, "cutout": 16}   # a comment in the header
 
-class DgDraw(C.Structure):
-    _fields_ = [("kind", C.c_int), ("fill_kind", C.c_int), ("seed", C.c_uint64), ("stream_id", C.c_uint64),
-                ("offset_dev", C.c_void_p), ("base", C.c_ulonglong), ("lo", C.c_float), ("hi", C.c_float),
-                ("eps", C.c_float), ("ilo", C.c_int), ("ihi", C.c_int), ("n", C.c_long), ("out", C.c_void_p),
-                ("out_bf16", C.c_void_p), ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("uf", C.c_void_p),
-                ("qi", C.c_void_p)]
-
-
-class DgWgrad(C.Structure):
-    _fields_ = [
-        ("wmode", C.c_int), ("ring", C.c_int),
-        ("B", C.c_int), ("Hc", C.c_int), ("Wc", C.c_int),
-        ("Ci", C.c_int), ("Co", C.c_int),
-        ("a", C.c_void_p), ("a_sb", C.c_long), ("a_sp", C.c_long), ("a_sc", C.c_long),
-        ("g", C.c_void_p), ("g_sb", C.c_long), ("g_sp", C.c_long), ("g_sc", C.c_long),
-        ("dw", C.c_void_p), ("scale", C.c_float), ("rowscale", C.c_void_p),
-        ("a_dtype", C.c_int), ("g_dtype", C.c_int),
-        ("ws", C.c_void_p), ("g_mod", C.c_int),
-    ]
-
-
-XSUM_PARTS = 8   # DG_XSUM_PARTS of include/dusty_gan_hip.h
-EXPORT_CHUNK = 1024   # DG_EXPORT_CHUNK: the pixels per workgroup of dg_export_points (sizes its chunk_counts workspace)
-
-
-class DgFetch(C.Structure):
-    _fields_ = [("pol", C.c_void_p), ("mask", C.c_void_p), ("pool_ctr", C.c_void_p), ("npool", C.c_int),
-                ("min_depth", C.c_float), ("max_depth", C.c_float), ("drop_const", C.c_float), ("B", C.c_int), ("HW", C.c_long),
-                ("out", C.c_void_p), ("parts", C.c_void_p), ("nslab", C.c_long), ("flip_tab", C.c_void_p)]
-
-
-class DgAugSet(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("xsum", C.c_void_p), ("xsum_parts", C.c_int), ("u_b", C.c_void_p), ("u_c", C.c_void_p), ("t_h", C.c_void_p),
-                ("t_w", C.c_void_p), ("o_x", C.c_void_p), ("o_y", C.c_void_p)]
-
-
-class DgOptSeg(C.Structure):
-    _fields_ = [("off", C.c_longlong), ("numel", C.c_longlong), ("part", C.c_void_p), ("splits", C.c_int), ("accumulate", C.c_int),
-                ("kind", C.c_int), ("ci", C.c_int), ("co", C.c_int), ("shadow_t", C.c_void_p), ("ws_src", C.c_void_p),
-                ("ws_coef", C.c_void_p), ("ws_stride", C.c_longlong), ("ws_n", C.c_int), ("ws_bf16", C.c_int),
-                ("ws_scale", C.c_float), ("first_block", C.c_int)]
-
-
-OPT_MAX_SEG = 20   # DG_OPT_MAX_SEG
-
-
-class DgWgradPlan(C.Structure):
-    _fields_ = [("variant", C.c_int), ("splits", C.c_int), ("ws_floats", C.c_long), ("tap_pairs", C.c_int)]
-
-
-class DgWgradReduce(C.Structure):
-    _fields_ = [("ws", C.c_void_p), ("dw", C.c_void_p), ("numel", C.c_long), ("splits", C.c_int), ("accumulate", C.c_int)]
-
-
-class DgConvPlan(C.Structure):
-    _fields_ = [("family", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("tiles", C.c_int), ("workgroups", C.c_int),
-                ("tiles_per_wg", C.c_int), ("thin_mfma", C.c_int), ("mask_bits", C.c_int), ("dbias_rows", C.c_int),
-                ("sum_parts", C.c_int)]
-
-
-_P, _I, _L, _F, _D, _U64 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_double, C.c_uint64
-
-# name -> argtypes (all return int except dg_version); mirrors include/dusty_gan_hip.h one to one
-PROTOTYPES = {
-    "dg_conv": [C.POINTER(DgConv), _I, _P],
-    "dg_conv_ex": [C.POINTER(DgConv), _I, _I, _P],
-    "dg_conv_plan": [C.POINTER(DgConv), _I, _I, C.POINTER(DgConvPlan)],
-    "dg_conv_mfma_supported": [C.POINTER(DgConv)],
-    "dg_wgrad": [C.POINTER(DgWgrad), _I, _I, _P],
-    "dg_wgrad_plan": [C.POINTER(DgWgrad), _I, _I, C.POINTER(DgWgradPlan)],
-    "dg_wgrad_group": [C.POINTER(DgWgrad), _I, _I, _I, _P],
-    "dg_wgrad_group_plan": [C.POINTER(DgWgrad), _I, _I, _I, C.POINTER(DgWgradPlan)],
-    "dg_wgrad_reduce": [C.POINTER(DgWgradReduce), _I, _P],
-    "dg_wgrad_mfma_supported": [C.POINTER(DgWgrad)],
-    "dg_wgrad_kernel_variant": [C.POINTER(DgWgrad), _I],
-    "dg_wgrad_has_sample_map": [C.POINTER(DgWgrad), _I],
-    "dg_blur_fwd": [_P, _P, _I, _I, _I, _I, _I, _P],
-    "dg_blur_fwd_mean": [_P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P],
-    "dg_blur_bwd": [_P, _I, _P, _I, _I, _I, _I, _P],
-    "dg_blur_bwd_r1": [_P, _I, _P, _F, _P, _I, _I, _I, _I, _P],
-    "dg_blur_r1_tangent": [_P, _I, _P, _F, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dg_final_fwd": [_P, _I, _P, _P, _F, _I, _L, _P, _P],
-    "dg_final_fwd_acc": [_P, _I, _P, _P, _F, _I, _L, _P, _P],
-    "dg_final_bwd_data": [_P, _I, _P, _P, _P, _F, _I, _L, _I, _P, _P, _P],
-    "dg_batch_wsum": [_P, _I, _P, _F, _I, _L, _P, _P],
-    "dg_head_post_fwd": [_P, _P, _P, _I, _I, _F, _F, _I, _L, _P, _P, _P],
-    "dg_head_post_fwd_sum": [_P, _P, _P, _I, _I, _F, _F, _I, _L, _P, _P, _P, _P],
-    "dg_head_post_bwd": [_P, _P, _P, _P, _P, _I, _F, _F, _I, _L, _F, _F, _P, _P, _P, _I, _P, _P],
-    "dg_logistic_noise": [_P, _P, _F, _L, _P, _P],
-    "dg_diffaug_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "dg_diffaug_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "dg_diffaug_fwd_acc": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "dg_diffaug_fwd_pre": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "dg_diffaug_bwd_acc": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "dg_diffaug_blur_fwd": [C.POINTER(DgAugSet), _I, _I, _I, _I, _I, _I, _P, _I, _P],
-    "dg_blur_bwd_augsum": [_P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P],
-    "dg_diffaug_bwd_pre": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "dg_head_post_bwd_aug": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _F, _F, _I, _I, _I, _F, _F, _P, _P, _P,
-                             _I, _P, _P],
-    "dg_fetch_reals_pool_sum": [_P, _P, _P, _I, _F, _F, _F, _I, _L, _P, _P, _P],
-    "dg_fetch_reals_resident_sum": [_P, _P, _L, _P, _F, _F, _F, _I, _L, _P, _P, _P],
-    "dg_resident_gather": [_P, _L, _I, _L, _L, _P, _P, _P, _P],
-    "dg_gan_d_step": [_I, _F, _P, _P, _I, _F, _P, _P, _P, _P, _P, _P],
-    "dg_gan_g_step": [_I, _P, _P, _I, _F, _P, _P, _P],
-    "dg_final_gan_bwd": [_I, _I, _F, _P, _P, _I, _F, _I, _P, _P, _P, _P, _P, _P, _I, _P, _F, _L, _I, _P, _P, _P, _P, _P],
-    "dg_det_arena": [_P, _L, _P],
-    "dg_mean_acc": [_P, _I, _P, _P],
-    "dg_fetch_reals": [_P, _P, _F, _F, _F, _L, _P, _P],
-    "dg_fetch_reals_sum": [_P, _P, _F, _F, _F, _I, _L, _P, _P, _P],
-    "dg_pl_penalty": [_P, _I, _I, _F, _P, _P, _P, _P],
-    "dg_head_post_bwd2": [_P, _P, _P, _P, _P, _P, _I, _F, _F, _I, _L, _F, _F, _P, _P, _P, _I, _P],
-    "dg_scan_to_polar": [_P, _I, _I, _I, _I, _I, _I, _P, _D, _D, _F, _P, _P, _P, _P, _P],
-    "dg_inv_to_xyz": [_P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P],
-    "dg_unit_map": [_P, _L, _I, _P, _P],
-    "dg_normals": [_P, _I, _I, _I, _I, _P, _P],
-    "dg_scan_project": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
-    "dg_angle_accum": [_P, _I, _I, _I, _I, _D, _D, _P, _P, _P],
-    "dg_angle_finish": [_P, _P, _I, _I, _P, _P],
-    "dg_splat_accum": [_P, _P, _I, _L, _I, _I, _I, _P, _P],
-    "dg_render_points": [_P, _P, _I, _L, _I, _P, _I, _P, _I, _D, _P, _P],
-    "dg_splat_finish": [_P, _I, _I, _I, _I, _I, _P, _P],
-    "dg_image_grid": [_P, _L, _I, _I, _I, _I, _F, _I, _P, _P],
-    "dg_turbo_lut": [_P],
-    "dg_fps": [_P, _I, _I, _I, _P, _P, _P, _P],
-    "dg_fps_map": [_P, _L, _L, _L, _I, _I, _I, _P, _P, _P, _P],
-    "dg_chamfer_dir": [_P, _I, _I, _P, _I, _I, _P, _P],
-    "dg_chamfer_paired": [_P, _I, _P, _I, _I, _P, _P],
-    "dg_chamfer_nn": [_P, _L, _L, _L, _I, _P, _L, _L, _L, _I, _I, _P, _P, _P],
-    "dg_emd": [_P, _I, _I, _P, _I, _I, _I, _P, _P],
-    "dg_emd_grad": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P],
-    "dg_chamfer_backward": [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
-    "dg_grid_vote": [_P, _L, _P, _I, _P, _P],
-    "dg_jsd": [_P, _P, _I, _P, _P],
-    "dg_pyr_down": [_P, _L, _I, _I, _P, _P],
-    "dg_pyr_up_sub": [_P, _P, _L, _I, _I, _P],
-    "dg_extract_patches": [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P],
-    "dg_sample_sum": [_P, _I, _L, _I, _P, _P],
-    "dg_sample_sum_acc": [_P, _I, _L, _I, _P, _P],
-    "dg_scale": [_P, _F, _L, _P, _P],
-    "dg_zero": [_P, _L, _P],
-    "dg_zero_multi": [_P, _P, _I, _P],
-    "dg_adam_ema_step": [_P, _P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _F, _F, _I, _F, _P],
-    "dg_cast": [_P, _P, _I, _L, _P],
-    "dg_uncast": [_P, _I, _P, _L, _P],
-    "dg_cast_x2_multi": [_P, _P, _P, _I, _P],
-    "dg_transpose_shadow": [_P, _P, _I, _I, _I, _P],
-    "dg_transpose_shadow_multi": [_P, _P, _I, _I, _I, _P],
-    "dg_transpose_shadow_multi_frags": [_P, _P, _I, _I, _I, C.POINTER(DgUpFrag), _I, _P],
-    "dg_transpose_shadow_multi_tail": [_P, _P, _I, _I, _I, C.POINTER(DgUpFrag), _I, _P, _P, _I, _I, _P, _I, _P, _I, _P],
-    "dg_philox_bits": [_U64, _U64, _U64, _L, _P, _P],
-    "dg_philox_fill": [_U64, _U64, _U64, _I, _F, _F, _I, _I, _L, _P, _P],
-    "dg_aug_draw": [_U64, _U64, _U64, _I, _I, _I, _P, _P, _P],
-    "dg_counter_add": [_P, _U64, _P],
-    "dg_step_prologue": [_P, _P, _I, C.POINTER(DgDraw), _I, _P],
-    "dg_step_prologue_fetch": [_P, _P, _I, C.POINTER(DgDraw), _I, C.POINTER(DgFetch), _P],
-    "dg_counter_add_multi": [_P, _P, _I, _P],
-    "dg_counter_add_multi_snap": [_P, _P, _I, _I, _P, _I, _P, _I, _P],
-    "dg_philox_fill_dev": [_U64, _U64, _P, _I, _F, _F, _I, _I, _L, _P, _P],
-    "dg_aug_draw_dev": [_U64, _U64, _P, _I, _I, _I, _P, _P, _P],
-    "dg_philox_logistic_dev": [_U64, _U64, _P, _F, _L, _P, _P],
-    "dg_adam_ema_step_dev": [_P, _P, _P, _P, _P, _P, _I, _L, _F, _F, _F, _F, _F, _P, _F, _P],
-    "dg_adam_fused": [_P, _P, _P, _P, _P, _I, C.POINTER(DgOptSeg), _I, _F, _F, _F, _F, _P, _F, _P],
-    "dg_adam_proj_fused": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _L, _I, _F, _F, _F, _F, _F, _P, _F, _P],
-    "dg_inv_loss_grad": [_P, _L, _I, _P, _P, _P, _I, _I, _L, _F, _P, _I, _P, _I, _P, _P, _I, _P, _P],
-    "dg_inv_loss_grad_add": [_P, _L, _I, _P, _P, _P, _I, _I, _L, _F, _P, _I, _P, _I, _P, _P, _I, _P, _P],
-    "dg_inv_chamfer_scatter": [_P, _P, _I, _L, _P, _P],
-    "dg_inv_chamfer_grad": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _L, _F, _F, _I, _P, _I, _P,
-                            _I, _P, _P, _I, _P, _P],
-    "dg_sphere_adam": [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _I, _U64, _U64, _I, _P],
-    "dg_sphere_adam_rows": [_P, _L, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _F, _F, _F, _I, _U64, _U64, _I, _I, _P],
-    "dg_depth_metrics": [_P, _P, _P, _P, _I, _I, _F, _I, _L, _F, _F, _P, _P],
-    "dg_feat_compose": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
-    "dg_feat_compose_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
-    "dg_alpha_adam": [_P, _P, _P, _P, _P, _P, _I, _F, _F, _F, _L, _P],
-    "dg_corrupt_mask": [_P, _P, _P, _P, _F, _I, _I, _I, _P, _P],
-    "dg_additive_noise": [_P, _P, _F, _L, _P, _P],
-    "dg_median3x3": [_P, _I, _I, _I, _P, _P],
-    "dg_hole_fill": [_P, _P, _I, _I, _I, _F, _P, _P, _P],
-    "dg_latent_walk": [_P, _P, _I, _I, _I, _P, _P],
-    "dg_export_points": [_P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _P, _P, _P, _P],
-    "dg_points_to_depth": [_P, _L, _I, _P, _I, _I, _P, _I, _I, _D, _D, _D, _F, _P, _P, _P, _P, _P],
-    "dg_pixel_winner": [_P, _L, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P],
-    "dg_raydrop_keep": [_P, _I, _P, _P, _U64, _U64, _U64, _F, _F, _I, _I, _I, _I, _P, _P, _P],
-    "dg_raydrop_gather": [_P, _L, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
-}
+_ERR = {DG_EINVAL: "DG_EINVAL (bad argument)", DG_EUNSUPPORTED: "DG_EUNSUPPORTED (shape not supported by the requested kernel)",
+        DG_EHIP: "DG_EHIP (HIP runtime error)"}
 
 _lib = None
 
@@ -288,12 +183,10 @@ def lib():
             "(run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C dusty_gan_amd/csrc`). "
             "There is no CPU or PyTorch fallback for the hot path.")
     h = C.CDLL(LIB_PATH)
-    for name, argtypes in PROTOTYPES.items():
+    for name, (restype, argtypes) in _SIGNATURES.items():
         fn = getattr(h, name)  # AttributeError if the symbol is not exported
         fn.argtypes = argtypes
-        fn.restype = C.c_int
-    h.dg_version.restype = C.c_char_p
-    h.dg_version.argtypes = []
+        fn.restype = restype
     _lib = h
     return h
 

@@ -29,10 +29,10 @@ class GANLoss(nn.Module):
 
     @property
     def code(self):
-        """DG_GAN_* of include/dusty_gan_hip.h (= position in models/loss.py's if-chain)"""
+        """DG_GAN_<METRIC> of include/dusty_gan_hip.h"""
         if self.metric not in METRICS:
             raise NotImplementedError
-        return METRICS.index(self.metric)
+        return getattr(L, "DG_GAN_" + self.metric.upper())
 
     @property
     def relativistic(self):

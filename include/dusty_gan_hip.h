@@ -554,7 +554,6 @@ int dg_extract_patches(const float* img, int B, int C, int H, int W, int ph, int
 
 /* ---- small reductions / helpers --------------------------------------------------------------------------- */
 int dg_sample_sum(const float* x, int B, long n, int sq, float* out, void* stream); /* out[b] = sum x or x^2 */
-int dg_scale(const float* x, float a, long n, float* y, void* stream);
 int dg_sample_sum_acc(const float* x, int B, long n, int sq, float* out, void* stream); /* out[b] = sum x or x^2 */
 int dg_scale(const float* x, float a, long n, float* y, void* stream);
 /* p[0..n) = 0 as a kernel launch (optim.zero_grad, trainers/dcgan_amp.py:177,246, and the step's accumulators).  The

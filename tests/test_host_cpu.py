@@ -1,6 +1,7 @@
 """CPU-side checks (no GPU): the C-ABI library loads and exports every symbol include/dusty_gan_hip.h declares,
-the ctypes structs match the header, the config tree loads, the model mirrors keep the reference's state_dict
-layout, and the host-side helpers behave."""
+the binding's header reader (_lib.read_header: prototypes, structs and codes come from the header, none is restated in
+Python) gives known answers, refuses what it does not understand and lays the structs out as the C compiler does, the config
+tree loads, the model mirrors keep the reference's state_dict layout, and the host-side helpers behave."""
 import ctypes as C
 import os
 import re
@@ -81,8 +82,8 @@ def _check_against_c(cname, cls, structs, lay, where):
 
 
 def test_ctypes_structs_match_header(built, tmp_path):
-    """every struct of include/dusty_gan_hip.h has a ctypes mirror in _lib.py with the same field names, order, offsets
-    and size as the C compiler's layout"""
+    """every struct of include/dusty_gan_hip.h has a ctypes class in _lib.py (made by its header reader) with the same field
+    names, order, offsets and size as the C compiler's layout"""
     structs, lay = _c_layout(tmp_path)
     assert set(structs) >= {"DgConv", "DgWgrad", "DgConvPlan", "DgWgradPlan", "DgWgradReduce", "DgAugSet", "DgUpFrag", "DgDraw"}
     for cname in structs:
@@ -98,6 +99,102 @@ def test_kernel_codes_match_header(built):
     codes = {n: int(v, 0) for n, v in re.findall(rf"^#define\s+({pat})\s+(0x[0-9a-fA-F]+|\d+)\b", h, flags=re.M)}
     assert len(codes) == 23 and codes["DG_FORCE_FP32X3"] == 0x100, codes
     assert {n: getattr(built, n) for n in dir(built) if re.fullmatch(pat, n)} == codes
+
+
+_KINDS = {"P": C.c_void_p, "I": C.c_int, "L": C.c_long, "LL": C.c_longlong, "U": C.c_uint, "ULL": C.c_ulonglong,
+          "U32": C.c_uint32, "U64": C.c_uint64, "F": C.c_float, "D": C.c_double, "UB": C.c_ubyte}
+
+_TOY_HEADER = """
+/* a comment that names dg_nothing(int) and #define DG_NOT 1 */
+#define DG_A 3
+#define DG_B (DG_A * 2 + 0x10)   /* 22 */
+enum { DG_E0 = 5, DG_E1, DG_E2 = DG_B };
+typedef struct DgToy {
+  int mode;               // line comment
+  const void* in;
+  long in_sb, in_sp;
+  const float *u, *v;
+  unsigned char tab[DG_A];
+  uint64_t seed;
+} DgToy;
+int dg_scalars(int a, long b, long long c, unsigned d, unsigned long long e, uint32_t f, uint64_t g, float h, double i,
+               unsigned char j);
+int dg_pointers(const DgToy* p, DgToy* const* pp, float* const* ptrs, const unsigned long long* ctr, void* stream);
+const char* dg_name(void);
+int dg_pointers(const DgToy *p, DgToy *const *pp, float *const *ptrs, const unsigned long long *ctr, void *stream);
+"""
+
+
+def test_read_header_on_a_synthetic_header():
+    """the header reader of _lib.py on a header small enough to know every answer by hand"""
+    from dusty_gan_amd import _lib
+    consts, structs, protos = _lib.read_header(_TOY_HEADER)
+    assert consts == {"DG_A": 3, "DG_B": 22, "DG_E0": 5, "DG_E1": 6, "DG_E2": 22}
+    assert list(structs) == ["DgToy"]
+    toy = structs["DgToy"]
+    assert issubclass(toy, C.Structure) and toy.__name__ == "DgToy"
+    assert [(n, t) for n, t in toy._fields_ if n != "tab"] == [
+        ("mode", C.c_int), ("in_", C.c_void_p), ("in_sb", C.c_long), ("in_sp", C.c_long), ("u", C.c_void_p), ("v", C.c_void_p),
+        ("seed", C.c_uint64)]
+    tab = dict(toy._fields_)["tab"]
+    assert [n for n, _ in toy._fields_].index("tab") == 6 and tab._type_ is C.c_ubyte and tab._length_ == 3
+    assert C.sizeof(toy) == 64 and toy.tab.offset == 48 and toy.seed.offset == 56
+    assert protos == {
+        "dg_scalars": (C.c_int, [_KINDS[k] for k in "I L LL U ULL U32 U64 F D UB".split()]),
+        "dg_pointers": (C.c_int, [C.POINTER(toy), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "dg_name": (C.c_char_p, [])}
+
+
+@pytest.mark.parametrize("bad, named", [
+    ("int dg_f(int a, short b);", "short"),                              # a scalar type outside the table
+    ("int dg_f(const DgElsewhere* p);", "DgElsewhere"),                  # a pointer to a type the header does not declare
+    ("typedef struct DgS { int a; int (*cb)(int); } DgS;", "DgS"),       # a struct it cannot split into fields
+    ("typedef struct DgS { int a : 3; } DgS;", "DgS"),
+    ("int dg_f(int a, long n);\nint dg_f(int a, int n);", "dg_f"),        # two declarations that differ
+    ("int dg_f(int a);\nint dg_g(int (*cb)(int), int b);", "dg_g"),       # a dg_ declaration the function pattern leaves
+    ("int dg_f(int a);\nstatic inline int dg_h(int a) { return a; }", "dg_h"),
+    ("#define DG_X (1 << )\n", "DG_X"),                                   # a constant that is no integer expression
+    ("#define DG_X 1.5\n", "DG_X"),
+])
+def test_read_header_refuses_what_it_does_not_understand(bad, named):
+    from dusty_gan_amd import _lib
+    with pytest.raises(_lib.DgError, match=named):
+        _lib.read_header(bad)
+
+
+def test_binding_without_its_header_names_the_path(tmp_path):
+    """a copy of _lib.py with no include/dusty_gan_hip.h beside its package refuses to import, naming the file it wants"""
+    import importlib.util
+    import shutil
+    from dusty_gan_amd import _lib
+    (tmp_path / "pkg").mkdir()
+    shutil.copy(_lib.__file__, tmp_path / "pkg" / "_lib_copy.py")
+    spec = importlib.util.spec_from_file_location("_lib_copy", tmp_path / "pkg" / "_lib_copy.py")
+    with pytest.raises(Exception) as e:
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+    assert type(e.value).__name__ == "DgError" and str(tmp_path / "include" / "dusty_gan_hip.h") in str(e.value)
+
+
+def test_binding_reads_the_real_header():
+    """on include/dusty_gan_hip.h: the reader binds exactly the names a crude independent pattern finds, and five
+    prototypes with the rare argument types are pinned kind by kind"""
+    from dusty_gan_amd import _lib as L
+    h = open(os.path.join(ROOT, "include", "dusty_gan_hip.h")).read()
+    crude = re.findall(r"^(?:int|const char\*)\s+(dg_\w+)\s*\(", h, flags=re.M)
+    assert len(crude) == len(set(crude)) >= 119, "a function is declared twice"
+    assert set(L.PROTOTYPES) == set(crude) == set(L._SIGNATURES)
+    assert L._SIGNATURES["dg_version"] == (C.c_char_p, [])
+    assert all(r is C.c_int for n, (r, _) in L._SIGNATURES.items() if n != "dg_version")
+
+    def kinds(s):
+        return [_KINDS[k] for k in s.split()]
+    assert L.PROTOTYPES["dg_points_to_depth"] == kinds("P L I P I I P I I D D D F P P P P P")
+    assert L.PROTOTYPES["dg_philox_fill"] == kinds("U64 U64 U64 I F F I I L P P")
+    assert L.PROTOTYPES["dg_conv_ex"] == [C.POINTER(L.DgConv)] + kinds("I I P")
+    assert L.PROTOTYPES["dg_wgrad_group"] == [C.POINTER(L.DgWgrad)] + kinds("I I I P")
+    assert L.PROTOTYPES["dg_sphere_adam_rows"] == kinds("P L L P P P P P P P I I I P I F F F I U64 U64 I I P")
+    assert L.DBIAS_WS_FLOATS == 32 * 1024 and L.UP_FRAG_BYTES == 3 * 18 * 1024 and L.MODE_GEMM == 2 and L.EPI_MASK == 2
+    assert (L.DG_OK, L.DG_EINVAL, L.DG_EUNSUPPORTED, L.DG_EHIP) == (0, 1, 2, 3)
 
 
 def test_integration_md_stubs_match_header(built, tmp_path):
