@@ -13,10 +13,15 @@
 //                            with chamfer_distance.cpp:82-140): the target-to-generated matches of dg_chamfer_nn scattered
 //                            onto the generated pixels in 24.40 fixed point, then per sample the loss and, chained through
 //                            inv_to_xyz and the EVAL-mode head post-processing, the head gradient.
+//   * points_gather_kernel / inv_points_grad_kernel : the earth mover's term on K furthest-point-sampled rays of the target:
+//                            the generated points read at the sampled pixels (the cloud dg_emd_grad matches against the
+//                            target's sample), and dg_emd_grad's gradA taken from those K pixels through the same pixel chain
+//                            (inv_chain.h) into the head gradient.
 // Every per-sample sum is a fixed-order reduction (block sums, then the partials of a sample in chunk order): an inversion
 // is bit-reproducible run to run.
 #include "adam.h"
 #include "head_post.h"
+#include "inv_chain.h"
 
 namespace {
 
@@ -152,41 +157,7 @@ __global__ __launch_bounds__(IL_THREADS) void inv_chamfer_grad_kernel(const Cham
     const float gx = w * (x - Rb[k2]) + w * (cnt * x - sx);
     const float gy = w * (y - Rb[HW + k2]) + w * (cnt * y - sy);
     const float gz = w * (z - Rb[2 * HW + k2]) + w * (cnt * z - sz);
-    const float pitch = a.angle[p], yaw = a.angle[HW + p];
-    const float cpt = cosf(pitch), spt = sinf(pitch), cy = cosf(yaw), sy_ = sinf(yaw);
-    const float dot = gx * (cpt * cy) + gy * (cpt * sy_) + gz * spt;
-    const float tm = a.depth[bp];                       // the masked depth, tanh domain
-    const float raw01 = (tm + 1.f) / 2.f;
-    const float inv = fminf(fmaxf(raw01, 0.f), 1.f);
-    const bool pass = raw01 >= 0.f && raw01 <= 1.f;     // clamp(0, 1) passes the gradient on the closed interval
-    const bool valid = fabsf(inv - 0.f) > a.tol;        // the LiDAR's drop_const is 0 (utils/lidar.py:12)
-    const float dep = 1.f / (inv * span + 1.f / a.max_d);
-    const float g = (valid && pass) ? 0.5f * (-(span * dep * dep) / a.max_d) * dot : 0.f;
-    const float* go = a.gout + (long)b * a.nheads * HW + p;
-    const float t = go[0];
-    float d0, d1, d2;
-    if (a.arch == 0) {
-      head_px_bwd<0>(t, g, 0.f, 0.f, 1.f, 1.f, a.inv_tau, a.drop_const, d0, d1, d2);
-    } else if (a.arch == 1) {
-      head_px_bwd<1>(t, g, go[HW] + a.noise_pixel[bp], 0.f, a.mask[bp], 1.f, a.inv_tau, a.drop_const, d0, d1, d2);
-    } else {
-      const float* mk = a.mask + (long)b * 2 * HW + p;
-      head_px_bwd<2>(t, g, go[HW] + a.noise_pixel[bp], 0.f, mk[0], mk[HW], a.inv_tau, a.drop_const, d0, d1, d2);
-      d2 = 0.f;
-    }
-    float v[3] = {d0 * a.s_depth, d1 * a.s_conf, d2 * a.s_conf};
-    if (a.add) {
-      const float* q = a.draw + (long)b * a.nheads * HW + p;
-      for (int c = 0; c < a.nheads && c < 3; ++c) v[c] += q[c * HW];
-    }
-    if (a.draw) {
-      float* q = a.draw + (long)b * a.nheads * HW + p;
-      for (int c = 0; c < a.nheads; ++c) q[c * HW] = c < 3 ? v[c] : 0.f;
-    }
-    if (a.draw_pm) {
-      bf16* q = a.draw_pm + bp * a.cp;
-      for (int c = 0; c < a.cp; ++c) q[c] = (bf16)((c < 3 && c < a.nheads) ? v[c] : 0.f);
-    }
+    inv_point_chain(a, b, p, bp, span, gx, gy, gz);
   }
   const float s = dg_block_sum(acc, red);
   if (threadIdx.x != 0) return;
@@ -201,8 +172,61 @@ __global__ __launch_bounds__(IL_THREADS) void inv_chamfer_grad_kernel(const Cham
   a.loss[b] = a.add ? a.loss[b] + val : val;
 }
 
+// ---- the earth mover's term on K sampled rays.  out[b][s][c] = X[b x_sb + idx[b][s] x_sp + c x_sc] (strides as
+// dg_chamfer_nn's); an index outside [0, n) gives the origin.
+__global__ __launch_bounds__(256) void points_gather_kernel(const float* __restrict__ X, long x_sb, long x_sp, long x_sc, int n,
+                                                            const int* __restrict__ idx, long BK, int K, float* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= BK) return;
+  const long b = i / K;
+  const int k = idx[i];
+  const bool in = k >= 0 && k < n;
+  const float* x = X + b * x_sb + (in ? k : 0) * x_sp;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[i * 3 + c] = in ? x[c * x_sc] : 0.f;
+}
+
+struct PointsGradArgs {
+  const float* gP;
+  const int* slot;
+  const float* term;
+  float scale;
+  int K;
+  const float *depth, *angle, *gout, *noise_pixel, *mask;
+  int arch, nheads, cp, add;
+  float inv_tau, drop_const, min_d, max_d, tol, s_depth, s_conf;
+  long HW;
+  float* draw;
+  bf16* draw_pm;
+  float* loss;
+};
+
+// The dense pixel pass of a term whose point gradient lives on K sampled pixels: gP [B,K,3] = d loss_b / d P at the sampled
+// pixels (dg_emd_grad's gradA), slot [B,HW] the sample a pixel is (-1: none, its gP is 0), then the chain of inv_chain.h on
+// EVERY pixel (one writer each).  loss[b] (+)= term[b] scale: the cost is a per-sample scalar already, so one thread writes it.
+__global__ __launch_bounds__(IL_THREADS) void inv_points_grad_kernel(const PointsGradArgs a) {
+  const int b = blockIdx.y, nch = gridDim.x;
+  const long HW = a.HW;
+  const long chunk = (HW + nch - 1) / nch;
+  const long p0 = blockIdx.x * chunk, p1 = min(HW, p0 + chunk);
+  const float span = 1.f / a.min_d - 1.f / a.max_d;
+  for (long p = p0 + threadIdx.x; p < p1; p += IL_THREADS) {
+    const long bp = (long)b * HW + p;
+    const int s = a.slot[bp];
+    float gx = 0.f, gy = 0.f, gz = 0.f;
+    if (s >= 0 && s < a.K) {
+      const float* q = a.gP + ((long)b * a.K + s) * 3;
+      gx = q[0]; gy = q[1]; gz = q[2];
+    }
+    inv_point_chain(a, b, p, bp, span, gx, gy, gz);
+  }
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const float val = __fmul_rn(a.term[b], a.scale);   // (rounded on its own: the sum below is prior + val exactly)
+  a.loss[b] = a.add ? a.loss[b] + val : val;
+}
+
 constexpr int SA_THREADS = 256;
-constexpr int SA_PER = 4;   // latent elements per thread: nz <= 1024
+constexpr int SA_PER = 4;  // latent elements per thread: nz <= 1024
 
 // standard normal of latent element (b, j) for step k: Box-Muller on the Philox words of counter
 // (k ceil(nz / 4) + j / 4, stream | b << 32) - the same word pairing as dg_philox_fill's kind 1, one counter stream per row
@@ -434,6 +458,37 @@ int dg_inv_chamfer_grad(const float* P, const float* R, const float* d1, const f
   a.s_depth = s_depth; a.s_conf = s_conf; a.HW = HW; a.draw = draw; a.draw_pm = (bf16*)draw_pm; a.parts = parts;
   a.tickets = tickets; a.loss = loss;
   inv_chamfer_grad_kernel<<<dim3(nchunk, B), IL_THREADS, 0, (hipStream_t)s_>>>(a);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
+
+int dg_points_gather(const float* X, long x_sb, long x_sp, long x_sc, int n, const int* idx, int B, int K, float* out,
+                     void* s_) {
+  if (!X || !idx || !out || n <= 0 || B <= 0 || K <= 0 || x_sb < 0 || x_sp <= 0 || x_sc <= 0) return DG_EINVAL;
+  const long BK = (long)B * K;
+  if ((BK + 255) / 256 > 0x7fffffffL) return DG_EUNSUPPORTED;
+  points_gather_kernel<<<(unsigned)((BK + 255) / 256), 256, 0, (hipStream_t)s_>>>(X, x_sb, x_sp, x_sc, n, idx, BK, K, out);
+  HIP_CHECK_RET(hipGetLastError());
+  return DG_OK;
+}
+
+int dg_inv_points_grad(const float* gP, const int* slot, const float* term, float scale, int K, const float* depth,
+                       const float* angle, const float* gout, const float* noise_pixel, const float* mask, int arch, float tau,
+                       float drop_const, float min_depth, float max_depth, float tol, int B, long HW, float s_depth, float s_conf,
+                       int add, float* draw, int nheads, void* draw_pm, int cp, int nchunk, float* loss, void* s_) {
+  if (!gP || !slot || !term || !depth || !angle || !gout || !loss || B <= 0 || HW <= 0 || K <= 0) return DG_EINVAL;
+  if (arch < 0 || arch > 2 || nheads != arch + 1 || (arch && (!noise_pixel || !mask)) || !(tau > 0.f)) return DG_EINVAL;
+  if (!(min_depth > 0.f && min_depth < max_depth)) return DG_EINVAL;
+  if (!draw && !draw_pm) return DG_EINVAL;
+  if (add && !draw) return DG_EINVAL;
+  if (draw_pm && cp < nheads) return DG_EINVAL;
+  if (nchunk < 1 || nchunk > 65535 || B > 65535) return DG_EINVAL;
+  PointsGradArgs a;
+  a.gP = gP; a.slot = slot; a.term = term; a.scale = scale; a.K = K; a.depth = depth; a.angle = angle; a.gout = gout;
+  a.noise_pixel = noise_pixel; a.mask = mask; a.arch = arch; a.nheads = nheads; a.cp = cp; a.add = add;
+  a.inv_tau = 1.f / tau; a.drop_const = drop_const; a.min_d = min_depth; a.max_d = max_depth; a.tol = tol;
+  a.s_depth = s_depth; a.s_conf = s_conf; a.HW = HW; a.draw = draw; a.draw_pm = (bf16*)draw_pm; a.loss = loss;
+  inv_points_grad_kernel<<<dim3(nchunk, B), IL_THREADS, 0, (hipStream_t)s_>>>(a);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }

@@ -1264,7 +1264,8 @@ class GEngine:
         allocated before the loop): forward in eval mode on self.zT (latent + this step's perturbation, written by the previous
         step's optimizer launch) -> dg_inv_loss_grad (per-sample masked loss and the head gradient, in place of
         dg_head_post_bwd) and / or the Chamfer term (dg_inv_to_xyz, two dg_chamfer_nn searches, dg_inv_chamfer_scatter,
-        dg_inv_chamfer_grad: demo.py:508-515) -> the data-only backward-data chain -> grad_z into its fixed buffer -> dg_sphere_adam (Adam,
+        dg_inv_chamfer_grad: demo.py:508-515) and / or the earth mover's term on sampled rays (dg_points_gather, dg_emd_grad,
+        dg_inv_points_grad) -> the data-only backward-data chain -> grad_z into its fixed buffer -> dg_sphere_adam (Adam,
         renormalisation, the next step's perturbed latent into self.zT).  No parameter, gradient or counter of the model is
         touched: the step's only state is S's.  Returns the forward's output dict (views of engine workspaces)."""
         if S.num_code > 1:
@@ -1282,10 +1283,10 @@ class GEngine:
         c, lib = self.cfg, L.lib()
         B, sp = S.B, L.stream_ptr()
         pm = self.draw_pm is not None   # bf16: the chain reads the pixel-major copy only
-        C = S.chamfer
-        nterm = len(S.terms) + (C is not None)
+        C, M = S.chamfer, S.emd
+        nterm = len(S.terms) + (C is not None) + (M is not None)
         # one term: it writes the head gradient where the chain reads it.  Several (demo.py:509-519): summed in a fixed order
-        # (l1, l2, chamfer) in the planar fp32 gradient; the last one also writes the sum's bf16 pixel-major copy
+        # (l1, l2, chamfer, emd) in the planar fp32 gradient; the last one also writes the sum's bf16 pixel-major copy
         for i, code in enumerate(S.terms):
             fn, what = (lib.dg_inv_loss_grad, "dg_inv_loss_grad") if i == 0 else (lib.dg_inv_loss_grad_add, "dg_inv_loss_grad_add")
             draw = L.ptr(self.draw) if (nterm > 1 or not pm) else None
@@ -1293,22 +1294,40 @@ class GEngine:
             L.check(fn(L.ptr(self.gout), c.nheads * self.HW, 1, L.ptr(S.ref), L.ptr(S.mask), L.ptr(S.msum), code, B, self.HW,
                        self.head_scales[0], draw, c.nheads, draw_pm, self.cp, L.ptr(S.parts), L.ptr(S.tickets), S.nchunk,
                        L.ptr(S.loss), sp), what)
+        if C is None and M is None:
+            return
+        HW, arch = self.HW, ARCH_ID[c.arch]
+        depth = out["depth"]   # the MASKED depth: the 3-D terms' gradients reach the confidence head through it
+        X = C if C is not None else M.maps   # the point maps: one dg_inv_to_xyz per step, whichever terms read P
+        L.check(lib.dg_inv_to_xyz(L.ptr(depth), L.ptr(X.angle), B, c.H, c.W, 1, X.min_depth, X.max_depth, 0.0, X.tol, None,
+                                  L.ptr(X.P), sp), "dg_inv_to_xyz")
+        cloud = (3 * HW, 1, HW, HW)   # planar point maps: sample, point and channel strides, points
+        nprior = len(S.terms)
         if C is not None:
-            HW, arch = self.HW, ARCH_ID[c.arch]
-            depth = out["depth"]   # the MASKED depth: this term's gradient reaches the confidence head through it
-            L.check(lib.dg_inv_to_xyz(L.ptr(depth), L.ptr(C.angle), B, c.H, c.W, 1, C.min_depth, C.max_depth, 0.0, C.tol, None,
-                                      L.ptr(C.P), sp), "dg_inv_to_xyz")
-            cloud = (3 * HW, 1, HW, HW)   # planar point maps: sample, point and channel strides, points
             L.check(lib.dg_chamfer_nn(L.ptr(C.R), *cloud, L.ptr(C.P), *cloud, B, L.ptr(C.d1), L.ptr(C.idx1), sp), "dg_chamfer_nn")
             L.check(lib.dg_chamfer_nn(L.ptr(C.P), *cloud, L.ptr(C.R), *cloud, B, L.ptr(C.d2), L.ptr(C.idx2), sp), "dg_chamfer_nn")
             L.check(lib.dg_inv_chamfer_scatter(L.ptr(C.R), L.ptr(C.idx1), B, HW, L.ptr(C.acc), sp), "dg_inv_chamfer_scatter")
-            add = int(nterm > 1)
+            add, last = int(nprior > 0), M is None
+            nprior += 1
             L.check(lib.dg_inv_chamfer_grad(L.ptr(C.P), L.ptr(C.R), L.ptr(C.d1), L.ptr(C.d2), L.ptr(C.idx2), L.ptr(C.acc),
                                             L.ptr(depth), L.ptr(C.angle), L.ptr(self.gout),
                                             L.ptr(self.noise_pixel) if arch else None, L.ptr(self.mask) if arch else None, arch,
                                             c.tau, c.drop_const, C.min_depth, C.max_depth, C.tol, B, HW, *self.head_scales, add,
-                                            L.ptr(self.draw) if (add or not pm) else None, c.nheads, L.ptr(self.draw_pm), self.cp,
+                                            L.ptr(self.draw) if (nterm > 1 or not pm) else None, c.nheads,
+                                            L.ptr(self.draw_pm) if last else None, self.cp,
                                             L.ptr(S.parts), L.ptr(S.tickets), S.nchunk, L.ptr(S.loss), sp), "dg_inv_chamfer_grad")
+        if M is not None:
+            # the generated cloud on the target's K sampled rays -> cost and d cost / d (generated points) / K -> the pixel chain
+            K, add = M.K, int(nprior > 0)
+            L.check(lib.dg_points_gather(L.ptr(X.P), *cloud, L.ptr(M.idx), B, K, L.ptr(M.Ps), sp), "dg_points_gather")
+            L.check(lib.dg_emd_grad(L.ptr(M.Ps), K, L.ptr(M.Rs), K, B, L.ptr(M.grad_cost), L.ptr(M.cost), L.ptr(M.gradA),
+                                    L.ptr(M.gradB), sp), "dg_emd_grad")
+            L.check(lib.dg_inv_points_grad(L.ptr(M.gradA), L.ptr(M.slot), L.ptr(M.cost), 1.0 / K, K, L.ptr(depth), L.ptr(X.angle),
+                                           L.ptr(self.gout), L.ptr(self.noise_pixel) if arch else None,
+                                           L.ptr(self.mask) if arch else None, arch, c.tau, c.drop_const, X.min_depth,
+                                           X.max_depth, X.tol, B, HW, *self.head_scales, add,
+                                           L.ptr(self.draw) if (add or not pm) else None, c.nheads, L.ptr(self.draw_pm), self.cp,
+                                           S.nchunk, L.ptr(S.loss), sp), "dg_inv_points_grad")
 
     def compose_geometry(self, layer):
         """(P pixels, C channels) of a[layer], the feature map a multi-code inversion composes at"""

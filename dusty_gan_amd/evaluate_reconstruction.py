@@ -1,7 +1,8 @@
 """Reconstruction evaluation by GAN inversion -- reference: evaluate_reconstruction.py (same flags, same CSV).
 
     python -m dusty_gan_amd.evaluate_reconstruction --model-path <ckpt.pth> --config-path <config.yaml>
-        [--save-dir-path .] [--tol 0] [--batch-size 512] [--distance l1|l2|chamfer|l1+chamfer|...] [--num-step 1000]
+        [--save-dir-path .] [--tol 0] [--batch-size 512] [--distance l1|l2|chamfer|emd|l1+emd|...] [--emd-points 2048]
+        [--num-step 1000]
         [--num-code N --composition-layer NAME] [--corruption NAME [--corruption-seed 0]]
 
 Every test scan is reconstructed by optimising the latent of the EMA generator (dusty_gan_amd.inversion.invert), then
@@ -22,7 +23,7 @@ COLUMNS = ["cd", "accuracy_1", "accuracy_2", "accuracy_3", "rmse", "rmse_log", "
            "drop_ref"]
 
 
-TERMS = ("l1", "l2", "chamfer")
+TERMS = ("l1", "l2", "chamfer", "emd")
 
 
 def split_distance(text):
@@ -55,7 +56,11 @@ def add_inversion_arguments(parser, batch_size=512):
     parser.add_argument("--distance", default="l1", type=_distance_arg,
                         help="the inversion loss: l1 or l2 (the reference's command), or - beyond the reference's command, "
                              "which offers those two only - chamfer (the third loss of the reference's demo, demo.py:508-519) "
-                             "and '+'-joined sums such as l1+chamfer")
+                             "emd (the earth mover's distance of the evaluation on --emd-points furthest-point-sampled rays "
+                             "of the target) and '+'-joined sums such as l1+chamfer or l1+emd")
+    parser.add_argument("--emd-points", type=int, default=2048,
+                        help="with emd in --distance: the rays sampled per scan, 1..3200 and at most H W; every scan needs that "
+                             "many points beyond about 3.8 m (at a max depth of 120 m)")
     parser.add_argument("--num-step", type=int, default=1000)
     parser.add_argument("--num-code", type=int, default=1,
                         help="latents per scan; above 1 (up to 64) the multi-code inversion of the reference's demo (mGANprior, "
@@ -72,7 +77,9 @@ def add_inversion_arguments(parser, batch_size=512):
 
 
 def check_inversion_arguments(parser, args):
-    from .inversion import MAX_CODES, parse_composition_layer
+    from .inversion import EMD_MAX_POINTS, MAX_CODES, parse_composition_layer
+    if not 1 <= args.emd_points <= EMD_MAX_POINTS:
+        parser.error(f"--emd-points: 1..{EMD_MAX_POINTS}")
     if not 1 <= args.num_code <= MAX_CODES:
         parser.error(f"--num-code: 1..{MAX_CODES}")
     if (args.num_code > 1) != (args.composition_layer is not None):
@@ -126,7 +133,8 @@ def evaluate_batch(G, lidar, arch, item, args, first_index=0, outputs=None):
     names = split_distance(args.distance)
     multi = dict(num_code=args.num_code, composition_layer=args.composition_layer) if args.num_code > 1 else {}
     res = invert(G, tgt_ref, tgt_mask, num_step=args.num_step, distance=names[0] if len(names) == 1 else names,
-                 lidar=lidar if "chamfer" in names else None, **multi)
+                 lidar=lidar if ("chamfer" in names or "emd" in names) else None,
+                 **({"emd_points": args.emd_points} if "emd" in names else {}), **multi)
     out = postprocess(res["out"], lidar, tol=args.tol)
     if outputs is not None:
         outputs.update(out, inv_gen=res["inv_gen"], target_inv=tgt_ref, target_mask=tgt_mask)

@@ -4,7 +4,9 @@ evaluate_reconstruction.py:32-164 (the loop) with utils/__init__.py:224-246 (Sph
 Every step is forward (eval mode) -> dg_inv_loss_grad -> the generator's backward-data chain -> grad_z ->
 dg_sphere_adam (GEngine.inversion_step).  The reference's demo adds a third loss, "chamfer" (demo.py:508-519): the symmetric
 Chamfer distance between the target's points and postprocess(out)["points"], the one term whose gradient reaches the
-measurability head - dg_inv_to_xyz -> two dg_chamfer_nn searches -> dg_inv_chamfer_scatter -> dg_inv_chamfer_grad.  The step index, the Adam moments and the latent live on the device, so one
+measurability head - dg_inv_to_xyz -> two dg_chamfer_nn searches -> dg_inv_chamfer_scatter -> dg_inv_chamfer_grad.  A fourth,
+"emd", is this project's: the earth mover's distance of the evaluation on K furthest-point-sampled rays of the target, the
+second 3-D term - dg_inv_to_xyz -> dg_points_gather -> dg_emd_grad -> dg_inv_points_grad (EmdState).  The step index, the Adam moments and the latent live on the device, so one
 step is captured in a hipGraph and replayed; the scalars are read back once, after the loop.
 
 num_code > 1 is the demo's multi-code mode (mGANprior, demo.py:353-366, 466-488, 523-530): N latents per scan run through the
@@ -64,38 +66,48 @@ def _draw_logistic(seed, stream_id, n, eps, device):
     return out
 
 
-DISTANCES = ("l1", "l2", "chamfer")   # the order the terms are evaluated and summed in
+DISTANCES = ("l1", "l2", "chamfer", "emd")   # the order the terms are evaluated and summed in
+POINT_TERMS = ("chamfer", "emd")             # the 3-D terms: they need the LiDAR's angle grid
+EMD_MAX_POINTS = 3200                        # dg_emd_grad holds n + m <= 6400 points per pair
 
 
 def check_distance(distance, lidar=None):
     """`distance` of invert - one of DISTANCES or a sequence of them (demo.py:509-519: the loss is their sum) - as a tuple
-    in DISTANCES' order.  ValueError for an empty selection or "chamfer" without a LiDAR; needs no device."""
+    in DISTANCES' order.  ValueError for an empty selection or a 3-D term ("chamfer", "emd") without a LiDAR; needs no device."""
     names = (distance,) if isinstance(distance, str) else tuple(distance)
     if len(names) == 0:
         raise ValueError("no distance selected: give at least one of " + ", ".join(DISTANCES))
     for n in names:
         if n not in DISTANCES:
             raise NotImplementedError(n)
-    if "chamfer" in names:
+    for n in POINT_TERMS:
+        if n not in names:
+            continue
         if lidar is None:
-            raise ValueError('distance "chamfer" needs lidar= (dusty_gan_amd.utils.lidar.LiDAR with its angle grid)')
+            raise ValueError(f'distance "{n}" needs lidar= (dusty_gan_amd.utils.lidar.LiDAR with its angle grid)')
         if getattr(lidar, "angle", None) is None:
-            raise ValueError('distance "chamfer" needs a LiDAR with an angle grid (angles.pt or use_nominal_angles)')
+            raise ValueError(f'distance "{n}" needs a LiDAR with an angle grid (angles.pt or use_nominal_angles)')
         if float(lidar.drop_const) != 0.0:
-            raise ValueError("the Chamfer term is built for the LiDAR's own drop_const of 0 (utils/lidar.py:12)")
+            raise ValueError(f"the {n} term is built for the LiDAR's own drop_const of 0 (utils/lidar.py:12)")
     return tuple(n for n in DISTANCES if n in names)
 
 
-class ChamferState:
-    """The Chamfer term's buffers: the target's points R (made once), the generated points, both searches' results and the
-    scatter words (zero at rest)."""
+def check_emd_points(emd_points, HW):
+    """K of the earth mover's term: an integer in 1..min(EMD_MAX_POINTS, HW) (ValueError); needs no device"""
+    K = int(emd_points)
+    if K != emd_points or not 1 <= K <= min(EMD_MAX_POINTS, HW):
+        raise ValueError(f"emd_points must be an integer in 1..min({EMD_MAX_POINTS}, H W = {HW}), got {emd_points!r}: "
+                         f"dg_emd_grad holds at most {2 * EMD_MAX_POINTS} points per pair")
+    return K
+
+
+class PointMaps:
+    """What the 3-D terms share: the angle grid, the target's point map R (made once) and the generated one P (every step)"""
 
     def __init__(self, inv_ref, lidar, tol):
         dev = inv_ref.device
         B, _, H, W = inv_ref.shape
         HW = H * W
-        if HW > (1 << 18):   # csrc/common.h DG_FIX40_MAX_TERMS
-            raise ValueError("the Chamfer term holds at most 2^18 points per scan")
         assert (H, W) == (lidar.H, lidar.W)
         self.tol = float(tol)
         self.min_depth, self.max_depth = lidar.min_depth, lidar.max_depth
@@ -105,11 +117,61 @@ class ChamferState:
         L.check(L.lib().dg_inv_to_xyz(L.ptr(ref), L.ptr(self.angle), B, H, W, 0, self.min_depth, self.max_depth, 0.0, self.tol,
                                       None, L.ptr(self.R), L.stream_ptr()), "dg_inv_to_xyz")
         self.P = torch.empty_like(self.R)
+
+
+class ChamferState(PointMaps):
+    """The Chamfer term's buffers: the target's points R (made once), the generated points, both searches' results and the
+    scatter words (zero at rest)."""
+
+    def __init__(self, inv_ref, lidar, tol):
+        dev = inv_ref.device
+        B, _, H, W = inv_ref.shape
+        HW = H * W
+        if HW > (1 << 18):   # csrc/common.h DG_FIX40_MAX_TERMS
+            raise ValueError("the Chamfer term holds at most 2^18 points per scan")
+        super().__init__(inv_ref, lidar, tol)
         self.d1 = torch.empty(B, HW, dtype=torch.float32, device=dev)
         self.d2 = torch.empty_like(self.d1)
         self.idx1 = torch.empty(B, HW, dtype=torch.int32, device=dev)
         self.idx2 = torch.empty_like(self.idx1)
         self.acc = torch.zeros(B, HW, 4, dtype=torch.int64, device=dev)
+
+
+class EmdState:
+    """The earth mover's term on K rays of the target: the sample T (dg_fps_map on the target's point map, drawn once), its
+    inverse `slot` [B,HW] (-1: not a sample), the target's sampled cloud Rs, and per step the generated cloud on the same rays
+    Ps, dg_emd_grad's cost, gradA (the point gradient) and gradB (scratch).  maps: the PointMaps whose R and P it reads.
+    ValueError - after ONE host read, before any step - for a scan with fewer than K furthest-point candidates (pixels with
+    |R|^2 >= 1e-3 in unit space: the reference's sampler never selects the others) or with a repeated index."""
+
+    def __init__(self, maps, K):
+        from .utils.sampling import _run_map
+        self.maps = maps
+        R = maps.R
+        dev = R.device
+        B, HW = R.shape[0], R.shape[2] * R.shape[3]
+        self.K = K = check_emd_points(K, HW)
+        self.idx, self.Rs = _run_map(R, K, True)
+        self.slot = torch.full((B, HW), -1, dtype=torch.int32, device=dev)
+        order = torch.arange(K, dtype=torch.int32, device=dev).expand(B, K)
+        self.slot.scatter_(1, self.idx.long(), order)
+        flat = R.flatten(2)
+        mag = (flat[:, 0] * flat[:, 0]) + (flat[:, 1] * flat[:, 1]) + (flat[:, 2] * flat[:, 2])
+        cand = (mag >= 1e-3).sum(dim=1)   # (float32(1e-3) itself is a candidate: csrc/point_fps.hip fps_skipped)
+        distinct = (self.slot.gather(1, self.idx.long()) == order).all(dim=1)
+        cand, distinct = torch.stack([cand, distinct.long()]).tolist()   # the one host read
+        short = [b for b in range(B) if cand[b] < K]
+        if short:
+            raise ValueError(f"emd_points = {K}: scan(s) {short} of the batch have only {[cand[b] for b in short]} furthest-point "
+                             "candidates (points at 1e-3 or more of squared unit range): lower emd_points")
+        twice = [b for b in range(B) if not distinct[b]]
+        if twice:
+            raise ValueError(f"emd_points = {K}: the sample of scan(s) {twice} repeats a pixel")
+        self.Ps = torch.empty_like(self.Rs)
+        self.gradA = torch.empty_like(self.Rs)
+        self.gradB = torch.empty_like(self.Rs)
+        self.cost = torch.empty(B, dtype=torch.float32, device=dev)
+        self.grad_cost = torch.full((B,), 1.0 / K, dtype=torch.float32, device=dev)
 
 
 def _backbone(G):
@@ -211,7 +273,7 @@ class InvState:
     num_code = 1
 
     def __init__(self, inv_ref, mask_ref, latent, gumbel, *, num_step, distance, lr, perturb_latent, noise_ratio,
-                 noise_sigma, lr_rampup_ratio, lr_rampdown_ratio, seed, lidar=None, tol=1e-8, row0=0):
+                 noise_sigma, lr_rampup_ratio, lr_rampdown_ratio, seed, lidar=None, tol=1e-8, row0=0, emd_points=2048):
         dev = inv_ref.device
         self.row0 = int(row0)   # the perturbation's row key of latent row 0
         B, _, H, W = inv_ref.shape
@@ -220,8 +282,11 @@ class InvState:
         self.mask = mask_ref.detach().float().contiguous()
         self.msum = self.mask.sum(dim=(1, 2, 3)).contiguous()   # integers: exact in any order
         names = check_distance(distance, lidar)
-        self.terms = tuple({"l1": 0, "l2": 1}[n] for n in names if n != "chamfer")   # dg_inv_loss_grad's distance codes
+        self.terms = tuple({"l1": 0, "l2": 1}[n] for n in names if n not in POINT_TERMS)   # dg_inv_loss_grad's distance codes
         self.chamfer = ChamferState(inv_ref, lidar, tol) if "chamfer" in names else None
+        self.emd = None
+        if "emd" in names:   # (R and P are the Chamfer term's where both are selected: one dg_inv_to_xyz per step)
+            self.emd = EmdState(self.chamfer if self.chamfer is not None else PointMaps(inv_ref, lidar, tol), emd_points)
         self.latent = latent
         self.m = torch.zeros_like(latent)
         self.v = torch.zeros_like(latent)
@@ -280,12 +345,16 @@ class InvState:
 def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, perturb_latent=True, noise_ratio=0.75,
            noise_sigma=1.0, lr_rampup_ratio=0.05, lr_rampdown_ratio=0.25, seed=0, latent=None, graph=True,
            noise_fn=None, gumbel_noise=None, on_step=None, lidar=None, tol=1e-8, num_code=1, composition_layer=None,
-           alpha=None, alpha_lr=1e-3, first_index=0):
+           alpha=None, alpha_lr=1e-3, first_index=0, emd_points=2048):
     """Reconstruct inv_ref [B,1,H,W] (inverse depth in [0,1]) under mask_ref [B,1,H,W] by optimising G's latent
     (evaluate_reconstruction.py:84-118).  G: what utils.setup returns (the bare 'none' generator or a DUSty1 / DUSty2
     wrapper), run in eval mode at its own precision; nothing of G is modified.
-    distance: "l1", "l2", "chamfer" or a sequence of them; the per-sample loss is their sum (demo.py:509-519).  "chamfer"
-    needs lidar= (utils.lidar.LiDAR with its angle grid) and takes tol, postprocess's validity threshold.
+    distance: "l1", "l2", "chamfer", "emd" or a sequence of them; the per-sample loss is their sum (demo.py:509-519).  "chamfer"
+    and "emd" need lidar= (utils.lidar.LiDAR with its angle grid) and take tol, postprocess's validity threshold.
+    "emd" (beyond the reference's demo): the earth mover's distance the evaluation reports (compute_emd), between the target's
+    emd_points furthest-point samples - drawn once, by the evaluation's own sampler - and the generated points on the same
+    rays, divided by emd_points; 1 <= emd_points <= min(3200, H W), and every scan needs that many points at 1e-3 or more of
+    squared unit range (ValueError before the first step).  Without "emd" the argument is not looked at.
     latent: the initial latent [B,nz] (default: Philox normal draws of `seed`, rows normalised as the reference does).
     Test hooks: noise_fn(k) -> the perturbation [B,nz] added to the latent at step k (replaces the Philox draws; eager
     loop), gumbel_noise [1,1,H,W] the fixed pixel-level logistic noise of the dusty archs, on_step(k, loss [B],
@@ -311,7 +380,8 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
     bf16, 15.7 MB in fp32) plus the head's buffers (gout, draw, mask, depth, in bf16 the pixel-major gradient and a3's mask bits:
     2.4 - 3.0 MB with three heads) - roughly 10 MB in bf16 and 17 MB in fp32.  fp32x3 split storage is not built for it."""
     from .utils.lidar import unit_map
-    check_distance(distance, lidar)
+    if "emd" in check_distance(distance, lidar):
+        check_emd_points(emd_points, inv_ref.shape[2] * inv_ref.shape[3])
     bb = _backbone(G)
     layer = check_multi_code(num_code, composition_layer, alpha, alpha_lr, inv_ref.shape[0], wrapped=bb is not G)
     N = int(num_code)
@@ -342,7 +412,7 @@ def invert(G, inv_ref, mask_ref, *, num_step=1000, distance="l1", lr=0.1, pertur
     S = InvState(inv_ref, mask_ref, latent, _fixed_gumbel(G, B, H, W, seed, dev, gumbel_noise), num_step=num_step,
                  distance=distance, lr=lr, perturb_latent=perturb_latent, noise_ratio=noise_ratio, noise_sigma=noise_sigma,
                  lr_rampup_ratio=lr_rampup_ratio, lr_rampdown_ratio=lr_rampdown_ratio, seed=seed,
-                 lidar=lidar, tol=tol, row0=first_index * N)
+                 lidar=lidar, tol=tol, row0=first_index * N, emd_points=emd_points)
     # every buffer of the loop exists before it, allocated on the caller's stream
     eng.alloc(B, dev)
     low = eng   # the engine the latents enter: the generator's own, or the lower one of a multi-code inversion

@@ -152,7 +152,7 @@ def transfer(G, lidar, records_unit, counts, *, records_raw=None, labels=None, r
     records_unit; the command passes the records in metres); labels [B,N] optional.
       1. LiDAR.points_to_depth(tau=tau, return_index=True) -> the inversion's target, mask = the pixels a point fell in
          (corruption: one of corruption.CORRUPTIONS applied to it first - "closing" pre-fills a sparse simulator frame);
-      2. inversion.invert against it (invert_kwargs: num_step, distance, num_code ... - "chamfer" gets lidar=) and the raw
+      2. inversion.invert against it (invert_kwargs: num_step, distance, num_code ... - "chamfer" and "emd" get lidar=) and the raw
          confidence logits of the optimised latent;
       3. pixel_winner -> sample_keep -> gather.  noise="sample": `realisations` Philox draws keyed by (seed, first_index + b,
          k); "fixed": the inversion's own fixed Gumbel noise (what G's head applied in the last step; realisations == 1).
@@ -187,7 +187,7 @@ def transfer(G, lidar, records_unit, counts, *, records_raw=None, labels=None, r
     fixed = _fixed_gumbel(G, 1, H, W, seed, x.device, invert_kwargs.pop("gumbel_noise", None))["pixel"]
     names = invert_kwargs.get("distance", "l1")
     names = (names,) if isinstance(names, str) else tuple(names)
-    if "chamfer" in names:
+    if "chamfer" in names or "emd" in names:
         invert_kwargs.setdefault("lidar", lidar)
     res = invert(G, inv_ref, mask_t, seed=seed, gumbel_noise=fixed, first_index=first_index, **invert_kwargs)
     conf = res["out"]["confidence"]

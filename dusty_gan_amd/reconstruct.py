@@ -2,7 +2,7 @@
 
     python -m dusty_gan_amd.reconstruct --model-path <ckpt.pth> --config-path <config.yaml> --points PATH [PATH ...]
         [--save-dir-path .] [--batch-size 32] [--tau 2] [--no-images] [--no-bins]
-        [--distance l1] [--num-step 1000] [--tol 0] [--num-code N --composition-layer NAME]
+        [--distance l1] [--emd-points 2048] [--num-step 1000] [--tol 0] [--num-code N --composition-layer NAME]
         [--corruption NAME [--corruption-seed 0]]
 
 PATH is a cloud file - a KITTI `.bin` (N x 4 float32, metres) or a `.npy` of shape N x 3 or N x 4 - or a directory, whose

@@ -3,7 +3,7 @@
     python -m dusty_gan_amd.transfer_raydrop --model-path <ckpt.pth> --config-path <config.yaml> --points PATH [PATH ...]
         [--labels DIR] [--realisations 1] [--drop-noise sample|fixed] [--seed 0] [--tau 2] [--batch-size 32]
         [--save-dir-path .] [--no-maps]
-        [--distance l1] [--num-step 1000] [--num-code N --composition-layer NAME] [--corruption NAME [--corruption-seed 0]]
+        [--distance l1] [--emd-points 2048] [--num-step 1000] [--num-code N --composition-layer NAME] [--corruption NAME [--corruption-seed 0]]
 
 The use the DUSty paper trains the measurability head for (the reference's repository holds no code for it): every cloud -
 files and stems as dusty_gan_amd.reconstruct takes them - is projected onto the model's angle grid, inverted through G's
@@ -108,6 +108,8 @@ def main(argv=None):
         os.makedirs(osp.join(out_dir, sub), exist_ok=True)
     names = split_distance(args.distance)
     inv = dict(num_step=args.num_step, distance=names[0] if len(names) == 1 else names)   # (as evaluate_batch calls invert)
+    if "emd" in names:
+        inv.update(emd_points=args.emd_points)
     if args.num_code > 1:
         inv.update(num_code=args.num_code, composition_layer=args.composition_layer)
     written, table = [], []

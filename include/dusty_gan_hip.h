@@ -785,6 +785,27 @@ int dg_inv_chamfer_grad(const float* P, const float* R, const float* d1, const f
                         float max_depth, float tol, int B, long HW, float s_depth, float s_conf, int add, float* draw,
                         int nheads, void* draw_pm, int cp, float* parts, unsigned* tickets, int nchunk, float* loss,
                         void* stream);
+/* The earth mover's term of the inversion loss, on K rays of the target (beyond the reference's demo, which has no EMD loss;
+ * the distance is the one its evaluation reports: compute_emd, utils/metrics/cov_mmd_1nna.py:12-17, on a furthest-point
+ * sample).  T_b = the K pixels dg_fps_map selects on the target's point map R_b, drawn once; each step the generated point
+ * map P_b is read on the SAME pixels, loss_b = dg_emd(P_b[T_b], R_b[T_b]) / K, and dg_emd_grad's gradA (grad_cost = 1 / K,
+ * the match a constant as in the reference's backward) is the point gradient at the sampled pixels, zero elsewhere.
+ * dg_points_gather: out [B,K,3] packed, out[b][s][c] = X[b x_sb + idx[b][s] x_sp + c x_sc] for idx [B,K] int32 - strides as
+ * dg_chamfer_nn's: a planar point map [B,3,n] is (3 n, 1, n), a packed cloud [B,n,3] is (3 n, 3, 1).  An index outside
+ * [0, n) writes zeros.  One writer per element.
+ * dg_inv_points_grad: the dense pixel pass.  gP [B,K,3] the point gradient of the K samples; slot [B,HW] int32 the inverse of
+ * T_b (slot[b][T_b[s]] = s, -1 for a pixel that is no sample: its point gradient is 0; a value >= K counts as -1);
+ * term [B] and scale: loss[b] = (add ? loss[b] : 0) + term[b] scale, the product rounded on its own, written by one thread per
+ * sample (no parts, no tickets: the cost is a per-sample scalar already).  Per pixel the point gradient is chained exactly as
+ * dg_inv_chamfer_grad chains its own - one device body, csrc/inv_chain.h - with that entry's depth, angle, gout, noise_pixel,
+ * mask, arch, tau, drop_const, min_depth, max_depth, tol, s_depth, s_conf and outputs draw / draw_pm / add / nheads / cp.  EVERY
+ * pixel is written, by one writer, without atomics: bit-reproducible.  nchunk workgroups per sample (1..65535). */
+int dg_points_gather(const float* X, long x_sb, long x_sp, long x_sc, int n, const int* idx, int B, int K, float* out,
+                     void* stream);
+int dg_inv_points_grad(const float* gP, const int* slot, const float* term, float scale, int K, const float* depth,
+                       const float* angle, const float* gout, const float* noise_pixel, const float* mask, int arch, float tau,
+                       float drop_const, float min_depth, float max_depth, float tol, int B, long HW, float s_depth, float s_conf,
+                       int add, float* draw, int nheads, void* draw_pm, int cp, int nchunk, float* loss, void* stream);
 int dg_sphere_adam(const float* grad, long g_sb, long g_sk, float* latent, float* m, float* v, unsigned long long* step_dev,
                    unsigned* ticket, const float* noise_in, void* zT, int z_dtype, int B, int nz, const float* sched,
                    int num_step, float beta1, float beta2, float eps, int perturb, uint64_t seed, uint64_t stream_id, int prime,

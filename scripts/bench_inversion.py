@@ -1,7 +1,7 @@
 """GAN inversion step time (dusty_gan_amd.inversion.invert) on the full-width generator: 64x1024, nz 512, ch_base 64,
 dusty2, bf16 and fp32, B = 32 and 512, the step captured once and replayed.  Device events around two inversions of
 different length: the difference per extra step is the replayed step's time (warm-up, capture and read-back cancel).
-    python scripts/bench_inversion.py [--batches 32 512] [--dtypes bf16 fp32] [--steps 200] [--distance l1 chamfer l1+chamfer]
+    python scripts/bench_inversion.py [--batches 32 512] [--dtypes bf16 fp32] [--steps 200] [--distance l1 chamfer l1+chamfer emd l1+emd] [--emd-points 1024 2048]
 --nn N: also time dg_chamfer_nn against dg_chamfer_paired (the index-free floor) on B = 32 pairs of N-point clouds
 (--batches or --dtypes with no value: skip the step benchmark and time the search only).
 --num-code N [N ...] with --composition-layer L [L ...]: the multi-code inversion (mGANprior) at every (N, L); N = 1 is the
@@ -120,7 +120,8 @@ def main():
     ap.add_argument("--dtypes", nargs="*", default=["bf16", "fp32"], help="no value: skip the step benchmark")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--short", type=int, default=20)
-    ap.add_argument("--distance", nargs="+", default=["l1"], help="'+'-joined terms out of l1, l2, chamfer; one run each")
+    ap.add_argument("--distance", nargs="+", default=["l1"], help="'+'-joined terms out of l1, l2, chamfer, emd; one run each")
+    ap.add_argument("--emd-points", type=int, nargs="+", default=[2048], help="K of the emd term; one run each")
     ap.add_argument("--nn", type=int, default=0)
     ap.add_argument("--num-code", type=int, nargs="+", default=[1], help="latents per scan; above 1: multi-code inversion")
     ap.add_argument("--composition-layer", type=int, nargs="+", default=[], help="0..3, with --num-code above 1")
@@ -151,10 +152,13 @@ def main():
         for B in a.batches:
             ref = torch.rand(B, 1, 64, 1024, device="cuda")
             mask = (torch.rand(B, 1, 64, 1024, device="cuda") > 0.1).float()
-            for dist, (ncode, layer) in ((d, c) for d in a.distance for c in combos):
+            runs = ((d, k, c) for d in a.distance for k in (a.emd_points if "emd" in d.split("+") else [None]) for c in combos)
+            for dist, K, (ncode, layer) in runs:
                 names = tuple(dist.split("+"))
                 kw = dict(gumbel_noise=gum, distance=names[0] if len(names) == 1 else names,
-                          lidar=lidar if "chamfer" in names else None)
+                          lidar=lidar if ("chamfer" in names or "emd" in names) else None)
+                if K is not None:
+                    kw.update(emd_points=K)
                 if ncode > 1:
                     kw.update(num_code=ncode, composition_layer=layer)
                 invert(G, ref, mask, num_step=a.short, **kw)   # warm-up: shadows, workspaces, clocks
@@ -169,7 +173,7 @@ def main():
                     ms[n] = e0.elapsed_time(e1)
                 step_ms = (ms[a.steps] - ms[a.short]) / (a.steps - a.short)
                 print(json.dumps({"what": "inversion step (graph replay)", "arch": "dusty2", "shape": [64, 1024], "nz": 512,
-                                  "dtype": dt, "B": B, "distance": dist, "num_code": ncode, "composition_layer": layer, "sclk_mhz": gpu_clock(), "ms_per_step": round(step_ms, 4),
+                                  "dtype": dt, "B": B, "distance": dist, "emd_points": K, "num_code": ncode, "composition_layer": layer, "sclk_mhz": gpu_clock(), "ms_per_step": round(step_ms, 4),
                                   "s_per_1000_steps": round(step_ms, 4),
                                   "ms_total": {str(k): round(v, 2) for k, v in ms.items()}}), flush=True)
             del ref, mask
