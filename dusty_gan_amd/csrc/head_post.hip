@@ -385,6 +385,7 @@ int dg_head_post_bwd2(const float* gout, const float* noise_pixel, const float* 
   if (!gout || !ddepth || !thead || !draw || B <= 0 || HW <= 0 || arch < 0 || arch > 2) return DG_EINVAL;
   if (arch >= 1 && (!noise_pixel || !mask)) return DG_EINVAL;
   if (arch == 2 && !noise_image) return DG_EINVAL;
+  if (draw_pm && (cp < 1 || cp > 4)) return DG_EINVAL;   // (the kernel's element-wise store writes channels 0..3)
   const long n = (long)B * HW;
   const int hb = (int)min((long)1024, (n + 255) / 256);
   head_post_bwd2_kernel<<<hb, 256, 0, (hipStream_t)s_>>>(gout, noise_pixel, noise_image, mask, ddepth, thead, arch,

@@ -378,7 +378,8 @@ int dg_det_arena(float* arena, long n, void* shadow);
  * reverse pass ends with dz^T = W^T dp0^T, a dg_wgrad of wmode 2) plus these two.  dg_pl_penalty: lengths |dz_b|, the running baseline pl_ema (device scalar,
  * updated: lerp(.., 0.01) :297), the penalty (:300) and v [B][K] = w * d penalty / d dz; acc[0] += baseline,
  * acc[1] += penalty.  dg_head_post_bwd2: tangent of dg_head_post_bwd along the head tangent `thead` [B,1+k,H,W] (the
- * Hessian of tanh / Gumbel straight-through maskout, models/dusty.py:77-91,107-127), same outputs as dg_head_post_bwd. */
+ * Hessian of tanh / Gumbel straight-through maskout, models/dusty.py:77-91,107-127), same outputs as dg_head_post_bwd; with draw_pm, cp must be 1..4 (else DG_EINVAL,
+ * nothing launched). */
 int dg_pl_penalty(const float* dz, int B, int K, float w, float* pl_ema, float* v, float* acc, void* stream);
 int dg_head_post_bwd2(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
                       const float* ddepth, const float* thead, int arch, float tau, float drop_const, int B, long HW,
