@@ -303,10 +303,12 @@ __device__ __forceinline__ void dg_acc_add(float* dst, float v, unsigned contrib
 //   thin_smallk_kernel       u64 word i < 64 = channel n_base + i in 32.32; the ticket in u64 word 64
 //   thin_s2_mfma_kernel      per slot of DG_DBIAS_SLOT_FLOATS floats: floats 0..63 = float channel sums, the ticket at float 64
 // head_post_bwd_kernel<.., PX = 4>'s bias_ws (DG_BIAS_WS_SAMPLE_FLOATS per sample): u64 word h < 3 = head h in 32.32, the ticket in u64
-// word 3; the launch's accumulators, in the same form, at float DG_BIAS_WS_ACC (the upper half of sample 0's slot).
+// word 3; the launch's accumulators, in the same form, at float DG_BIAS_WS_ACC (the upper half of sample 0's slot).  The
+// learnable-temperature form adds u64 words DG_BIAS_WS_TAU, + 1 = the temperature sums G_pixel, G_image, in both places.
 #define DG_DBIAS_WS_WORDS (DG_DBIAS_SLOTS * DG_DBIAS_SLOT_FLOATS / 2)
 #define DG_BIAS_WS_SAMPLE_FLOATS 1024
 #define DG_BIAS_WS_ACC 512
+#define DG_BIAS_WS_TAU 4
 __device__ __forceinline__ unsigned* dg_dbias_ws_ticket(float* ws) { return (unsigned*)((unsigned long long*)ws + DG_DBIAS_WS_WORDS - 1); }
 __device__ __forceinline__ unsigned* dg_thin_ws_ticket(float* ws) { return (unsigned*)((unsigned long long*)ws + 64); }
 __device__ __forceinline__ unsigned* dg_dbias_slot_ticket(float* slot) { return (unsigned*)(slot + 64); }

@@ -72,6 +72,61 @@ __device__ __forceinline__ void head_px_bwd(float t, float go, float l1, float l
   }
 }
 
+// ---- the learnable temperature (models/dusty.py:25-26, 38-43: tau = None).  Each Gumbel sigmoid k owns a scalar weight w_k and
+//      its slope is inv_k = softplus(w_k) + 1 / tau_max, formed in the kernel from the fp32 MASTER weight (a replayed step graph
+//      follows the training).  HeadTau<false> is the by-value slope of the fixed-tau kernels - one float, their argument as before;
+//      HeadTau<true> carries the weights (pixel, image), 1 / tau_max and the weights' gradient accumulators.
+//      d loss / d w_k = sigma(w_k) G_k with G_k = sum over pixels of pre_k s_k (1 - s_k) l_k: the term is taken from the
+//      intermediate ((pre s)(1 - s)) hp_dsigmoid forms before its last multiply, so d1 / d2 round as in the fixed-tau form.
+template <bool LT> struct HeadTau;
+template <> struct HeadTau<false> { float inv_tau; };
+template <> struct HeadTau<true> { const float* w; float inv_min; float* dw; };
+__device__ __forceinline__ float hp_inv_tau_lt(float w, float inv_min) { return log1pf(__expf(w)) + inv_min; }
+__device__ __forceinline__ float hp_dinv_tau_lt(float w) { return 1.f / (1.f + __expf(-w)); }   // d inv / d w = sigma(w)
+
+// head_px_fwd with a slope per sigmoid (dusty2's eval-mode image mask stays the sign of the logit)
+template <int arch>
+__device__ __forceinline__ HeadPx head_px_fwd_lt(float raw, float l1, float g2, float ni, int training, float inv_p, float inv_i,
+                                                 float drop_const) {
+  HeadPx o;
+  o.t = dg_tanh(raw);
+  o.mp = 1.f; o.mi = 1.f; o.depth = o.t;
+  if (arch == 0) return o;
+  o.mp = hp_sigmoid(l1, inv_p) > 0.5f ? 1.f : 0.f;
+  if (arch == 2) {
+    if (training) o.mi = hp_sigmoid(g2 + ni, inv_i) > 0.5f ? 1.f : 0.f;
+    else o.mi = g2 > 0.f ? 1.f : 0.f;
+  }
+  const float m = arch == 2 ? o.mp * o.mi : o.mp;
+  o.depth = m * o.t + (1.f - m) * drop_const;
+  return o;
+}
+
+// head_px_bwd with a slope per sigmoid, plus the pixel's terms of G_pixel (g1) and G_image (g2): 0 where the arch has none
+template <int arch>
+__device__ __forceinline__ void head_px_bwd_lt(float t, float go, float l1, float l2, float mp, float mi, float inv_p, float inv_i,
+                                               float drop_const, float& d0, float& d1, float& d2, float& g1, float& g2) {
+  const float dt = hp_dtanh(t);
+  d1 = 0.f; d2 = 0.f; g1 = 0.f; g2 = 0.f;
+  if (arch == 0) { d0 = go * dt; return; }
+  const float sp = hp_sigmoid(l1, inv_p);
+  const float dmask = go * (t - drop_const);
+  if (arch == 1) {
+    d0 = mp * go * dt;
+    const float q1 = dmask * sp * (1.f - sp);
+    d1 = q1 * inv_p;
+    g1 = q1 * l1;
+  } else {
+    const float si = hp_sigmoid(l2, inv_i);
+    d0 = mp * mi * go * dt;
+    const float q1 = dmask * mi * sp * (1.f - sp), q2 = dmask * mp * si * (1.f - si);
+    d1 = q1 * inv_p;
+    d2 = q2 * inv_i;
+    g1 = q1 * l1;
+    g2 = q2 * l2;
+  }
+}
+
 // ---- the pixel-major / channel-minor bf16 copy [B,H,W,cp] of the scaled gradients, channels zero-padded: the operand layout
 //      of the MFMA backward-data kernel (thin_s2_mfma).  A pixel is two 32-bit words: (d0 s_depth | d1 s_conf << 16, d2 s_conf).
 __device__ __forceinline__ uint2 head_pm_words(int arch, float d0, float d1, float d2, float s_depth, float s_conf) {

@@ -15,16 +15,19 @@
 
 // PX pixels whose head outputs are in registers: stores tanh (in place: g), the masks (m: the pixel mask's plane, the image
 // mask's one plane further) and the depth; returns the pixels' depth sum
-template <int arch, int PX>
+// LT (the learnable temperature, head_post.h): inv_tau is the pixel sigmoid's slope, inv_i the image sigmoid's
+template <int arch, int PX, bool LT = false>
 __device__ __forceinline__ float head_fwd_store(const float (&g0)[PX], const float (&g1)[PX], const float (&np)[PX],
-                                                const float (&g2)[PX], float ni, int training, float inv_tau,
+                                                const float (&g2)[PX], float ni, int training, float inv_tau, float inv_i,
                                                 float drop_const, long HW, float* __restrict__ g, float* __restrict__ m,
                                                 float* __restrict__ depth) {
   float t[PX], mp[PX], mi[PX], dv[PX];
 #pragma unroll
   for (int q = 0; q < PX; ++q) {
-    const HeadPx o = head_px_fwd<arch>(g0[q], arch >= 1 ? g1[q] + np[q] : 0.f, arch == 2 ? g2[q] : 0.f, ni, training,
-                                       inv_tau, drop_const);
+    const HeadPx o = LT ? head_px_fwd_lt<arch>(g0[q], arch >= 1 ? g1[q] + np[q] : 0.f, arch == 2 ? g2[q] : 0.f, ni, training,
+                                               inv_tau, inv_i, drop_const)
+                        : head_px_fwd<arch>(g0[q], arch >= 1 ? g1[q] + np[q] : 0.f, arch == 2 ? g2[q] : 0.f, ni, training,
+                                            inv_tau, drop_const);
     t[q] = o.t; mp[q] = o.mp; mi[q] = o.mi; dv[q] = o.depth;
   }
   st_px<PX>(g, t);
@@ -34,13 +37,27 @@ __device__ __forceinline__ float head_fwd_store(const float (&g0)[PX], const flo
   return px_sum<PX>(dv);
 }
 
-template <int arch, int PX>   // compile-time: the pixel function is then straight-line code and the unrolled trips batch their loads
+// the slopes of a launch: the by-value one, or (LT) formed from the master weights - one load per thread, uniform
+template <int arch, bool LT>
+__device__ __forceinline__ void head_slopes(const HeadTau<LT>& tau, float& inv_p, float& inv_i) {
+  if constexpr (LT) {
+    inv_p = arch >= 1 ? hp_inv_tau_lt(tau.w[0], tau.inv_min) : tau.inv_min;
+    inv_i = arch == 2 ? hp_inv_tau_lt(tau.w[1], tau.inv_min) : inv_p;
+  } else {
+    inv_p = inv_i = tau.inv_tau;
+  }
+}
+
+// compile-time: the pixel function is then straight-line code and the unrolled trips batch their loads.  LT: the learnable temperature
+template <int arch, int PX, bool LT = false>
 __global__ __launch_bounds__(256) void head_post_fwd_kernel(float* __restrict__ gout, const float* __restrict__ noise_pixel,
-                                     const float* __restrict__ noise_image, int training, float inv_tau,
+                                     const float* __restrict__ noise_image, int training, const HeadTau<LT> tau,
                                      float drop_const, int B, long HW, float* __restrict__ mask,
                                      float* __restrict__ depth, float* __restrict__ dsum, int chunk, const DgDet det) {
   __shared__ float red[16];
   constexpr int nch = 1 + arch;
+  float inv_tau, inv_i;
+  head_slopes<arch, LT>(tau, inv_tau, inv_i);
   // the head outputs of PX pixels: g = the first one's raw depth, np = its noise
   auto load = [&](const float* g, const float* np_, float (&g0)[PX], float (&g1)[PX], float (&np)[PX], float (&g2)[PX]) {
     ld_px<PX>(g, g0);
@@ -55,8 +72,8 @@ __global__ __launch_bounds__(256) void head_post_fwd_kernel(float* __restrict__ 
       float* g = gout + (long)b * nch * HW + p;
       float g0[PX], g1[PX], np[PX], g2[PX];
       load(g, noise_pixel + idx, g0, g1, np, g2);
-      head_fwd_store<arch, PX>(g0, g1, np, g2, (arch == 2 && training) ? noise_image[b] : 0.f, training, inv_tau, drop_const,
-                               HW, g, arch >= 1 ? mask + (long)b * arch * HW + p : nullptr, depth + idx);
+      head_fwd_store<arch, PX, LT>(g0, g1, np, g2, (arch == 2 && training) ? noise_image[b] : 0.f, training, inv_tau, inv_i,
+                                   drop_const, HW, g, arch >= 1 ? mask + (long)b * arch * HW + p : nullptr, depth + idx);
     }
     return;
   }
@@ -84,8 +101,8 @@ __global__ __launch_bounds__(256) void head_post_fwd_kernel(float* __restrict__ 
     for (int u = 0; u < U; ++u) {
       const int k = k0 + u * STEP;
       if (k >= chunk) break;
-      acc += head_fwd_store<arch, PX>(g0[u], g1[u], np[u], g2[u], ni, training, inv_tau, drop_const, HW, g + k, m + k,
-                                      depth + i0 + k);
+      acc += head_fwd_store<arch, PX, LT>(g0[u], g1[u], np[u], g2[u], ni, training, inv_tau, inv_i, drop_const, HW, g + k,
+                                          m + k, depth + i0 + k);
     }
   };
   if constexpr (PX == 1) {
@@ -116,14 +133,20 @@ struct HeadGradPlain {
 // trip, plain float atomics into dbias.
 // PX = 4: four consecutive pixels per thread (HW % 4 == 0): 16-byte loads of every plane, 16-byte stores; `draw` may be
 // null - the bf16 path consumes only the pixel-major copy, and three 8 MB planes were written for nobody.
-template <int arch, int CP, int PX, typename DD>   // CP: 0 no pixel-major copy, 2 / 4 that padded channel count, 1 any other
+// LT: the learnable temperature (head_post.h) - the slopes come from the master weights, and the two temperature sums G_pixel,
+// G_image travel exactly as the head-bias sums do (block sum; then the fixed-point slots and tickets, or float atomics) into
+// tau.dw[k] += sigma(w_k) G_k, the factor applied once where the total is converted.  The launch sums them with or without dbias.
+template <int arch, int CP, int PX, typename DD, bool LT = false>   // CP: 0 no pixel-major copy, 2 / 4 that padded channel count, 1 any other
 __global__ __launch_bounds__(256) void head_post_bwd_kernel(const float* __restrict__ gout, const float* __restrict__ noise_pixel,
                                      const float* __restrict__ noise_image, const float* __restrict__ mask,
-                                     DD ddepth, float inv_tau, float drop_const, int B, long HW,
+                                     DD ddepth, const HeadTau<LT> tau, float drop_const, int B, long HW,
                                      float s_depth, float s_conf, float* __restrict__ draw, float* __restrict__ dbias,
                                      bf16* __restrict__ draw_pm, int cp, float* __restrict__ bias_ws) {
   __shared__ float red[16];
   float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+  float at1 = 0.f, at2 = 0.f;   // (LT) this thread's part of G_pixel, G_image
+  float inv_tau, inv_i;
+  head_slopes<arch, LT>(tau, inv_tau, inv_i);
   const int b = blockIdx.y;
   constexpr int nch = 1 + arch;
   const float* g = gout + (long)b * nch * HW;
@@ -137,10 +160,19 @@ __global__ __launch_bounds__(256) void head_post_bwd_kernel(const float* __restr
     if (arch >= 1) { ld_px<PX>(g + HW + p, g1); ld_px<PX>(noise_pixel + idx, np); ld_px<PX>(mk + p, mp); }
     if (arch == 2) { ld_px<PX>(mk + HW + p, mi); ld_px<PX>(g + 2 * HW + p, g2); }
     float d0[PX], d1[PX], d2[PX];   // unscaled gradients w.r.t. the head outputs (= the head bias gradients)
+    if constexpr (LT) {
+      float e1[PX], e2[PX];
 #pragma unroll
-    for (int q = 0; q < PX; ++q)
-      head_px_bwd<arch>(t[q], go[q], arch >= 1 ? g1[q] + np[q] : 0.f, arch == 2 ? g2[q] + ni : 0.f, arch >= 1 ? mp[q] : 1.f,
-                        arch == 2 ? mi[q] : 1.f, inv_tau, drop_const, d0[q], d1[q], d2[q]);
+      for (int q = 0; q < PX; ++q)
+        head_px_bwd_lt<arch>(t[q], go[q], arch >= 1 ? g1[q] + np[q] : 0.f, arch == 2 ? g2[q] + ni : 0.f, arch >= 1 ? mp[q] : 1.f,
+                             arch == 2 ? mi[q] : 1.f, inv_tau, inv_i, drop_const, d0[q], d1[q], d2[q], e1[q], e2[q]);
+      at1 += px_sum<PX>(e1); at2 += px_sum<PX>(e2);
+    } else {
+#pragma unroll
+      for (int q = 0; q < PX; ++q)
+        head_px_bwd<arch>(t[q], go[q], arch >= 1 ? g1[q] + np[q] : 0.f, arch == 2 ? g2[q] + ni : 0.f, arch >= 1 ? mp[q] : 1.f,
+                          arch == 2 ? mi[q] : 1.f, inv_tau, drop_const, d0[q], d1[q], d2[q]);
+    }
     if (PX == 1 || draw) {
       float* d = draw + (long)b * nch * HW + p;
       float v[PX];
@@ -173,7 +205,7 @@ __global__ __launch_bounds__(256) void head_post_bwd_kernel(const float* __restr
   } else {
     for (long p = p_first; p < HW; p += p_step) pixels(p);
   }
-  if (dbias) {  // head biases are outside EqualLR's input scaling: their gradient is the unscaled sum
+  if (LT || dbias) {  // head biases are outside EqualLR's input scaling: their gradient is the unscaled sum
     // Atomics on ONE address retire at ~10 ns each (they execute memory-side): a thousand blocks adding straight into
     // dbias[n] cost 10 us per head - more than the pass over the data.  With `bias_ws` (PX = 4; 4 KB per sample, zero on entry
     // and left zero) the blocks of a sample add into that sample's slot - B independent addresses - and the last one to
@@ -181,6 +213,13 @@ __global__ __launch_bounds__(256) void head_post_bwd_kernel(const float* __restr
     const float s0 = dg_block_sum(a0, red);
     const float s1 = arch >= 1 ? dg_block_sum(a1, red) : 0.f;
     const float s2 = arch >= 2 ? dg_block_sum(a2, red) : 0.f;
+    const float st1 = (LT && arch >= 1) ? dg_block_sum(at1, red) : 0.f;
+    const float st2 = (LT && arch >= 2) ? dg_block_sum(at2, red) : 0.f;
+    const bool heads = !LT || dbias;   // (LT: the temperature sums do not wait for a dbias)
+    // (LT) adds sigma(w_k) v onto the gradient of temperature weight k
+    auto dtau_add = [&](int k, float v) {
+      if constexpr (LT) atomicAdd(&tau.dw[k], hp_dinv_tau_lt(tau.w[k]) * v);
+    };
     if (threadIdx.x == 0) {
       if (PX == 4 && bias_ws && gridDim.x > 1) {
         // Round 5: the staged sums are 32.32 FIXED POINT (integer adds commute: the total no longer depends on the order in
@@ -191,24 +230,51 @@ __global__ __launch_bounds__(256) void head_post_bwd_kernel(const float* __restr
         unsigned long long* w = (unsigned long long*)(bias_ws + (long)b * DG_BIAS_WS_SAMPLE_FLOATS);
         unsigned long long* gacc = (unsigned long long*)(bias_ws + DG_BIAS_WS_ACC);
         const float sv[3] = {s0, s1, s2};
+        if (heads) {
 #pragma unroll
-        for (int h = 0; h <= arch; ++h) {
-          long long q;
-          if (dg_fix1(sv[h], q)) atomicAdd(&w[h], (unsigned long long)q);
-          else atomicAdd(&dbias[h], sv[h]);
+          for (int h = 0; h <= arch; ++h) {
+            long long q;
+            if (dg_fix1(sv[h], q)) atomicAdd(&w[h], (unsigned long long)q);
+            else atomicAdd(&dbias[h], sv[h]);
+          }
+        }
+        if constexpr (LT) {   // the temperature sums: words DG_BIAS_WS_TAU, + 1 of the same slots, the same two tickets
+          const float tv[2] = {st1, st2};
+#pragma unroll
+          for (int k = 0; k < arch; ++k) {
+            long long q;
+            if (dg_fix1(tv[k], q)) atomicAdd(&w[DG_BIAS_WS_TAU + k], (unsigned long long)q);
+            else dtau_add(k, tv[k]);
+          }
         }
         if (dg_ticket_last(dg_bias_ws_ticket(w), gridDim.x)) {
+          if (heads) {
 #pragma unroll
-          for (int h = 0; h <= arch; ++h) atomicAdd(&gacc[h], atomicExch(&w[h], 0ull));
+            for (int h = 0; h <= arch; ++h) atomicAdd(&gacc[h], atomicExch(&w[h], 0ull));
+          }
+          if constexpr (LT) {
+#pragma unroll
+            for (int k = 0; k < arch; ++k) atomicAdd(&gacc[DG_BIAS_WS_TAU + k], atomicExch(&w[DG_BIAS_WS_TAU + k], 0ull));
+          }
           if (dg_ticket_last(dg_bias_ws_ticket(gacc), gridDim.y)) {
+            if (heads) {
 #pragma unroll
-            for (int h = 0; h <= arch; ++h) atomicAdd(&dbias[h], dg_fix1_value((long long)atomicExch(&gacc[h], 0ull)));
+              for (int h = 0; h <= arch; ++h) atomicAdd(&dbias[h], dg_fix1_value((long long)atomicExch(&gacc[h], 0ull)));
+            }
+            if constexpr (LT) {
+#pragma unroll
+              for (int k = 0; k < arch; ++k) dtau_add(k, dg_fix1_value((long long)atomicExch(&gacc[DG_BIAS_WS_TAU + k], 0ull)));
+            }
           }
         }
       } else {
-        atomicAdd(&dbias[0], s0);
-        if (arch >= 1) atomicAdd(&dbias[1], s1);
-        if (arch >= 2) atomicAdd(&dbias[2], s2);
+        if (heads) {
+          atomicAdd(&dbias[0], s0);
+          if (arch >= 1) atomicAdd(&dbias[1], s1);
+          if (arch >= 2) atomicAdd(&dbias[2], s2);
+        }
+        if (arch >= 1) dtau_add(0, st1);
+        if (arch >= 2) dtau_add(1, st2);
       }
     }
   }
@@ -283,9 +349,10 @@ __global__ void head_post_bwd2_kernel(const float* __restrict__ gout, const floa
 
 // ----------------------------------------------------------------------------------------------------------
 // grid: ~1024 blocks in all, each one atomic per head
-template <int PX, typename DD>
+// LT: `tau` holds the learnable temperature's pointers (arch 1 / 2 only: the callers have checked)
+template <int PX, typename DD, bool LT = false>
 static int head_post_bwd_launch(DD dd, const float* gout, const float* noise_pixel, const float* noise_image,
-                                const float* mask, int arch, float tau, float drop_const, int B, long HW, float s_depth,
+                                const float* mask, int arch, const HeadTau<LT> tau, float drop_const, int B, long HW, float s_depth,
                                 float s_conf, float* draw, float* dbias, void* draw_pm, int cpk, int cp, float* bias_ws,
                                 hipStream_t s) {
   const unsigned per = B >= 1024 ? 1u : (unsigned)(1024 / B);
@@ -293,22 +360,24 @@ static int head_post_bwd_launch(DD dd, const float* gout, const float* noise_pix
   if (hb > per) hb = per;
   const dim3 grid(hb, B);
 #define DG_HPB(A, C)                                                                                                     \
-  head_post_bwd_kernel<A, C, PX, DD><<<grid, 256, 0, s>>>(gout, noise_pixel, noise_image, mask, dd, 1.f / tau, drop_const, \
-                                                          B, HW, s_depth, s_conf, draw, dbias, (bf16*)draw_pm, cp, bias_ws)
+  head_post_bwd_kernel<A, C, PX, DD, LT><<<grid, 256, 0, s>>>(gout, noise_pixel, noise_image, mask, dd, tau, drop_const, \
+                                                              B, HW, s_depth, s_conf, draw, dbias, (bf16*)draw_pm, cp, bias_ws)
 #define DG_HPB_A(A)                                                                            \
   do {                                                                                         \
     if (cpk == 0) DG_HPB(A, 0); else if (cpk == 2) DG_HPB(A, 2); else if (cpk == 4) DG_HPB(A, 4); \
     else if constexpr (PX == 1) DG_HPB(A, 1);   /* (any other `cp`: the callers send it to the scalar form only) */ \
   } while (0)
-  if (arch == 0) DG_HPB_A(0); else if (arch == 1) DG_HPB_A(1); else DG_HPB_A(2);
+  if (arch == 0) { if constexpr (!LT) DG_HPB_A(0); } else if (arch == 1) DG_HPB_A(1); else DG_HPB_A(2);
 #undef DG_HPB_A
 #undef DG_HPB
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }
 
+template <bool LT = false>
 static int head_post_fwd_impl(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
-                              float tau, float drop_const, int B, long HW, float* mask, float* depth, float* dsum, void* s_) {
+                              const HeadTau<LT> tau, float drop_const, int B, long HW, float* mask, float* depth, float* dsum,
+                              void* s_) {
   hipStream_t s = (hipStream_t)s_;
   if (arch < 0 || arch > 2) return DG_EINVAL;
   if (dsum && HW % 256 != 0) return DG_EUNSUPPORTED;
@@ -318,45 +387,79 @@ static int head_post_fwd_impl(float* gout, const float* noise_pixel, const float
   const bool quad = dsum && chunk % 1024 == 0 && ((size_t)gout & 15) == 0 && ((size_t)depth & 15) == 0 && ((size_t)mask & 15) == 0 &&
                     ((size_t)noise_pixel & 15) == 0;
 #define DG_HPF(A, PX)                                                                                                      \
-  head_post_fwd_kernel<A, PX><<<nb, 256, 0, s>>>(gout, noise_pixel, noise_image, training, 1.f / tau, drop_const, B, HW, mask, \
-                                                 depth, dsum, chunk, det)
+  head_post_fwd_kernel<A, PX, LT><<<nb, 256, 0, s>>>(gout, noise_pixel, noise_image, training, tau, drop_const, B, HW, mask, \
+                                                     depth, dsum, chunk, det)
 #define DG_HPF_A(A) do { if (quad) DG_HPF(A, 4); else DG_HPF(A, 1); } while (0)
-  if (arch == 0) DG_HPF_A(0); else if (arch == 1) DG_HPF_A(1); else DG_HPF_A(2);
+  if (arch == 0) { if constexpr (!LT) DG_HPF_A(0); } else if (arch == 1) DG_HPF_A(1); else DG_HPF_A(2);
 #undef DG_HPF_A
 #undef DG_HPF
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }
 
-extern "C" {
-
-int dg_head_post_fwd(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
-                     float tau, float drop_const, int B, long HW, float* mask, float* depth, void* s_) {
-  return head_post_fwd_impl(gout, noise_pixel, noise_image, arch, training, tau, drop_const, B, HW, mask, depth, nullptr, s_);
-}
-// ... + dsum[b] += sum of depth[b] (dsum zeroed by the caller; HW % 256 == 0 or DG_EUNSUPPORTED): the per-sample sums
-// that dg_diffaug_fwd_pre takes instead of making its own pass over the image
-int dg_head_post_fwd_sum(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
-                         float tau, float drop_const, int B, long HW, float* mask, float* depth, float* dsum, void* s_) {
-  if (!dsum) return DG_EINVAL;
-  return head_post_fwd_impl(gout, noise_pixel, noise_image, arch, training, tau, drop_const, B, HW, mask, depth, dsum, s_);
-}
-
-int dg_head_post_bwd(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
-                     const float* ddepth, int arch, float tau, float drop_const, int B, long HW, float s_depth,
-                     float s_conf, float* draw, float* dbias, void* draw_pm, int cp, float* bias_ws,
-                     void* s_) {
+// the two backward entry points' bodies, shared by the fixed-tau and the learnable-temperature forms
+template <bool LT>
+static int head_post_bwd_impl(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
+                              const float* ddepth, int arch, const HeadTau<LT> tau, float drop_const, int B, long HW,
+                              float s_depth, float s_conf, float* draw, float* dbias, void* draw_pm, int cp, float* bias_ws,
+                              void* s_) {
   hipStream_t s = (hipStream_t)s_;
   if (arch < 0 || arch > 2) return DG_EINVAL;
   const int cpk = !draw_pm ? 0 : (cp == 2 ? 2 : (cp == 4 ? 4 : 1));
   if (!draw && !draw_pm) return DG_EINVAL;
   auto al = [](const void* q) { return ((size_t)q & 15) == 0; };
   if (HW % 4 == 0 && cpk != 1 && al(gout) && al(ddepth) && al(draw) && al(draw_pm) && al(noise_pixel) && al(mask))
-    return head_post_bwd_launch<4>(HeadGradPlain{ddepth}, gout, noise_pixel, noise_image, mask, arch, tau, drop_const, B, HW,
-                                   s_depth, s_conf, draw, dbias, draw_pm, cpk, cp, bias_ws, s);
+    return head_post_bwd_launch<4, HeadGradPlain, LT>(HeadGradPlain{ddepth}, gout, noise_pixel, noise_image, mask, arch, tau,
+                                                      drop_const, B, HW, s_depth, s_conf, draw, dbias, draw_pm, cpk, cp, bias_ws, s);
   if (!draw) return DG_EUNSUPPORTED;   // (the scalar form always writes the planar copy)
-  return head_post_bwd_launch<1>(HeadGradPlain{ddepth}, gout, noise_pixel, noise_image, mask, arch, tau, drop_const, B, HW,
-                                 s_depth, s_conf, draw, dbias, draw_pm, cpk, cp, bias_ws, s);
+  return head_post_bwd_launch<1, HeadGradPlain, LT>(HeadGradPlain{ddepth}, gout, noise_pixel, noise_image, mask, arch, tau,
+                                                    drop_const, B, HW, s_depth, s_conf, draw, dbias, draw_pm, cpk, cp, bias_ws, s);
+}
+
+template <bool LT>
+static int head_post_bwd_aug_impl(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
+                                  const float* gy, const float* u_b, const float* u_c, const int* t_h, const int* t_w,
+                                  const int* o_x, const int* o_y, int policy, const float* gsum, int arch, const HeadTau<LT> tau,
+                                  float drop_const, int B, int H, int W, float s_depth, float s_conf, float* draw, float* dbias,
+                                  void* draw_pm, int cp, float* bias_ws, void* s_) {
+  if (arch < 0 || arch > 2 || !gy || B <= 0 || H <= 0 || W <= 1) return DG_EINVAL;
+  if (!draw && !draw_pm) return DG_EINVAL;
+  if ((policy & 4) && !gsum) return DG_EINVAL;
+  const int cpk = !draw_pm ? 0 : (cp == 2 ? 2 : (cp == 4 ? 4 : 1));
+  auto al = [](const void* q) { return ((size_t)q & 15) == 0; };
+  if (!(W % 4 == 0 && cpk != 1 && al(gout) && al(draw) && al(draw_pm) && al(noise_pixel) && al(mask))) return DG_EUNSUPPORTED;
+  HeadGradAug dd{make_aug(u_b, u_c, t_h, t_w, o_x, o_y, policy, B, H, W), gy, gsum};
+  return head_post_bwd_launch<4, HeadGradAug, LT>(dd, gout, noise_pixel, noise_image, mask, arch, tau, drop_const, B, (long)H * W,
+                                                  s_depth, s_conf, draw, dbias, draw_pm, cpk, cp, bias_ws, (hipStream_t)s_);
+}
+
+// the learnable-temperature entry points' own argument checks: a dusty arch, the weights, a positive 1 / tau_max
+static bool head_lt_ok(int arch, const float* tau_w, float inv_tau_min) {
+  return (arch == 1 || arch == 2) && tau_w != nullptr && inv_tau_min > 0.f;
+}
+
+extern "C" {
+
+int dg_head_post_fwd(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
+                     float tau, float drop_const, int B, long HW, float* mask, float* depth, void* s_) {
+  return head_post_fwd_impl(gout, noise_pixel, noise_image, arch, training, HeadTau<false>{1.f / tau}, drop_const, B, HW, mask,
+                            depth, nullptr, s_);
+}
+// ... + dsum[b] += sum of depth[b] (dsum zeroed by the caller; HW % 256 == 0 or DG_EUNSUPPORTED): the per-sample sums
+// that dg_diffaug_fwd_pre takes instead of making its own pass over the image
+int dg_head_post_fwd_sum(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
+                         float tau, float drop_const, int B, long HW, float* mask, float* depth, float* dsum, void* s_) {
+  if (!dsum) return DG_EINVAL;
+  return head_post_fwd_impl(gout, noise_pixel, noise_image, arch, training, HeadTau<false>{1.f / tau}, drop_const, B, HW, mask,
+                            depth, dsum, s_);
+}
+
+int dg_head_post_bwd(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
+                     const float* ddepth, int arch, float tau, float drop_const, int B, long HW, float s_depth,
+                     float s_conf, float* draw, float* dbias, void* draw_pm, int cp, float* bias_ws,
+                     void* s_) {
+  return head_post_bwd_impl<false>(gout, noise_pixel, noise_image, mask, ddepth, arch, HeadTau<false>{1.f / tau}, drop_const, B, HW,
+                                   s_depth, s_conf, draw, dbias, draw_pm, cp, bias_ws, s_);
 }
 
 // dg_diffaug_bwd_pre + dg_head_post_bwd in one launch: d loss / d depth is DiffAugment's adjoint gather of gy (the BlurVH
@@ -368,15 +471,45 @@ int dg_head_post_bwd_aug(const float* gout, const float* noise_pixel, const floa
                          const int* o_x, const int* o_y, int policy, const float* gsum, int arch, float tau,
                          float drop_const, int B, int H, int W, float s_depth, float s_conf, float* draw, float* dbias,
                          void* draw_pm, int cp, float* bias_ws, void* s_) {
-  if (arch < 0 || arch > 2 || !gy || B <= 0 || H <= 0 || W <= 1) return DG_EINVAL;
-  if (!draw && !draw_pm) return DG_EINVAL;
-  if ((policy & 4) && !gsum) return DG_EINVAL;
-  const int cpk = !draw_pm ? 0 : (cp == 2 ? 2 : (cp == 4 ? 4 : 1));
-  auto al = [](const void* q) { return ((size_t)q & 15) == 0; };
-  if (!(W % 4 == 0 && cpk != 1 && al(gout) && al(draw) && al(draw_pm) && al(noise_pixel) && al(mask))) return DG_EUNSUPPORTED;
-  HeadGradAug dd{make_aug(u_b, u_c, t_h, t_w, o_x, o_y, policy, B, H, W), gy, gsum};
-  return head_post_bwd_launch<4>(dd, gout, noise_pixel, noise_image, mask, arch, tau, drop_const, B, (long)H * W, s_depth,
-                                 s_conf, draw, dbias, draw_pm, cpk, cp, bias_ws, (hipStream_t)s_);
+  return head_post_bwd_aug_impl<false>(gout, noise_pixel, noise_image, mask, gy, u_b, u_c, t_h, t_w, o_x, o_y, policy, gsum, arch,
+                                       HeadTau<false>{1.f / tau}, drop_const, B, H, W, s_depth, s_conf, draw, dbias, draw_pm, cp,
+                                       bias_ws, s_);
+}
+
+// ---- the learnable temperature (tau = None): the four entry points above with `float tau` replaced by tau_w (device pointer to
+// the `arch` fp32 MASTER weights, pixel then image - never a bf16 shadow) and inv_tau_min = 1 / tau_max; the backward forms also
+// take dtau_w (`arch` accumulators, added to like dbias).  arch 1 / 2; a null tau_w / dtau_w or inv_tau_min <= 0: DG_EINVAL.
+int dg_head_post_fwd_lt(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
+                        const float* tau_w, float inv_tau_min, float drop_const, int B, long HW, float* mask, float* depth,
+                        void* s_) {
+  if (!head_lt_ok(arch, tau_w, inv_tau_min)) return DG_EINVAL;
+  return head_post_fwd_impl<true>(gout, noise_pixel, noise_image, arch, training, HeadTau<true>{tau_w, inv_tau_min, nullptr},
+                                  drop_const, B, HW, mask, depth, nullptr, s_);
+}
+int dg_head_post_fwd_sum_lt(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
+                            const float* tau_w, float inv_tau_min, float drop_const, int B, long HW, float* mask, float* depth,
+                            float* dsum, void* s_) {
+  if (!dsum || !head_lt_ok(arch, tau_w, inv_tau_min)) return DG_EINVAL;
+  return head_post_fwd_impl<true>(gout, noise_pixel, noise_image, arch, training, HeadTau<true>{tau_w, inv_tau_min, nullptr},
+                                  drop_const, B, HW, mask, depth, dsum, s_);
+}
+int dg_head_post_bwd_lt(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
+                        const float* ddepth, int arch, const float* tau_w, float inv_tau_min, float* dtau_w, float drop_const,
+                        int B, long HW, float s_depth, float s_conf, float* draw, float* dbias, void* draw_pm, int cp,
+                        float* bias_ws, void* s_) {
+  if (!head_lt_ok(arch, tau_w, inv_tau_min) || !dtau_w) return DG_EINVAL;
+  return head_post_bwd_impl<true>(gout, noise_pixel, noise_image, mask, ddepth, arch, HeadTau<true>{tau_w, inv_tau_min, dtau_w},
+                                  drop_const, B, HW, s_depth, s_conf, draw, dbias, draw_pm, cp, bias_ws, s_);
+}
+int dg_head_post_bwd_aug_lt(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
+                            const float* gy, const float* u_b, const float* u_c, const int* t_h, const int* t_w,
+                            const int* o_x, const int* o_y, int policy, const float* gsum, int arch, const float* tau_w,
+                            float inv_tau_min, float* dtau_w, float drop_const, int B, int H, int W, float s_depth, float s_conf,
+                            float* draw, float* dbias, void* draw_pm, int cp, float* bias_ws, void* s_) {
+  if (!head_lt_ok(arch, tau_w, inv_tau_min) || !dtau_w) return DG_EINVAL;
+  return head_post_bwd_aug_impl<true>(gout, noise_pixel, noise_image, mask, gy, u_b, u_c, t_h, t_w, o_x, o_y, policy, gsum, arch,
+                                      HeadTau<true>{tau_w, inv_tau_min, dtau_w}, drop_const, B, H, W, s_depth, s_conf, draw, dbias,
+                                      draw_pm, cp, bias_ws, s_);
 }
 
 int dg_head_post_bwd2(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,

@@ -70,6 +70,22 @@ class ParamStore:
         self.x2_cico, self.x2_coci = {}, {}
         self._x2_key = None  # the fp32 shadows' pointers the twins were built for
 
+    def extend(self, segments):
+        """append trailing segments (zero-filled) to a store that has no training state, shadow or device table yet: a module
+        that wraps the network adds parameters of its own (the DUSty wrappers' learnable temperature, `tau_w`).  Earlier
+        segments keep their offsets and values."""
+        assert self.grad is None and self.shadow is None and self._tdesc is None, "extend a store at construction only"
+        off = self.n
+        for name, shape, kind in segments:
+            assert name not in self.seg, name
+            s = Segment(name, off, shape, kind)
+            self.seg[name] = s
+            off = _align(off + s.numel)
+        flat = torch.zeros(off, dtype=torch.float32, device=self.flat.device)
+        flat[:self.n] = self.flat
+        self.n, self.flat = off, flat
+        self._seen_version = -1
+
     # -- views
     def view(self, name, buf=None):
         s = self.seg[name]
@@ -274,12 +290,19 @@ def d_segments(in_ch, ch, shape):
 
 
 class NetCfg:
-    def __init__(self, shape, nz, ch, arch="none", ring=True, tau=1.0, drop_const=-1.0, dis_in_ch=1):
+    def __init__(self, shape, nz, ch, arch="none", ring=True, tau=1.0, drop_const=-1.0, dis_in_ch=1, tau_learn=False,
+                 inv_tau_min=1.0):
+        """tau_learn: the Gumbel temperature is a DEVICE scalar per sigmoid - segment `tau_w` of the generator's store, slope
+        softplus(w) + inv_tau_min (models/dusty.py) - which the head kernels read from the fp32 master (dg_head_post_*_lt);
+        `tau` is then only what the inference paths that take it by value were last given (_DUSty._sync)."""
         self.H, self.W = int(shape[0]), int(shape[1])
         if self.H % 16 or self.W % 16 or self.H < 32:
             raise ValueError(f"shape {shape}: H and W must be multiples of 16 and H >= 32 (SURVEY.md §0.2)")
         self.nz, self.ch = int(nz), [int(c) for c in ch]
         self.arch, self.ring, self.tau, self.drop_const = arch, bool(ring), float(tau), float(drop_const)
+        self.tau_learn, self.inv_tau_min = bool(tau_learn), float(inv_tau_min)
+        if self.tau_learn and ARCH_ID[arch] == 0:
+            raise ValueError("a learnable Gumbel temperature needs a dusty arch")
         self.nheads = 1 + ARCH_ID[arch]
         self.h0, self.w0 = self.H >> 4, self.W >> 4
         self.proj_rows = self.h0 * self.w0 * self.ch[3]   # Proj.weight is [proj_rows][nz], rows in (y, x, c) order
@@ -1011,14 +1034,16 @@ class GEngine:
             if arch == 2 and training and self.noise_image is None:
                 raise ValueError("dusty2 in training mode needs image-level noise")
         sums = L.AccArena.take(B, self.depth.device) if (self.HW % 256 == 0 and want_sums) else None
+        fwd, fwd_sum = ((lib.dg_head_post_fwd_lt, lib.dg_head_post_fwd_sum_lt) if c.tau_learn
+                        else (lib.dg_head_post_fwd, lib.dg_head_post_fwd_sum))
         hp_args = (L.ptr(self.gout), L.ptr(self.noise_pixel) if arch else None,
-                   L.ptr(self.noise_image) if arch == 2 and training else None, arch, int(training), c.tau, c.drop_const, B,
-                   self.HW, L.ptr(self.mask), L.ptr(self.depth))
+                   L.ptr(self.noise_image) if arch == 2 and training else None, arch, int(training), *self._tau_args(st),
+                   c.drop_const, B, self.HW, L.ptr(self.mask), L.ptr(self.depth))
         if sums is not None:  # per-sample sums of the depth image in the same pass (DiffAugment's contrast reads them)
-            L.check(lib.dg_head_post_fwd_sum(*hp_args, L.ptr(sums), sp), "dg_head_post_fwd_sum")
+            L.check(fwd_sum(*hp_args, L.ptr(sums), sp), "dg_head_post_fwd_sum")
             L.tag_sums(self.depth, sums)
         else:
-            L.check(lib.dg_head_post_fwd(*hp_args, sp), "dg_head_post_fwd")
+            L.check(fwd(*hp_args, sp), "dg_head_post_fwd")
         out = OrderedDict()
         out["depth"] = self.depth
         if arch:
@@ -1087,6 +1112,14 @@ class GEngine:
         self.ops.conv(L.MODE_S2, 1, self.cfg.ring, B, hc, wc, co, ci, g, sg, chain[2][i - 1], sa, st.sptr(name + "_w"), s,
                       L.EPI_MASK, aux=self.a[i - 1], dbias=dbias, bias_mod=ci, in_dt=gdt, defer_db=True)
 
+    def _tau_args(self, st, grad=False):
+        """the temperature arguments of a head post-processing launch: tau by value, or - learnable - the master weights'
+        device pointer and 1 / tau_max for the `_lt` entry points (+ grad: the weights' slice of the flat gradient)"""
+        c = self.cfg
+        if not c.tau_learn:
+            return (c.tau,)
+        return (st.fptr("tau_w"), c.inv_tau_min) + ((st.fptr("tau_w", st.grad),) if grad else ())
+
     def _head_saved(self):
         """what the head post-processing's backward kernels read of the forward pass: (gout, pixel noise, image noise, mask)"""
         arch = ARCH_ID[self.cfg.arch]
@@ -1126,15 +1159,17 @@ class GEngine:
                 L.ptr(self.draw_pm), self.cp, L.ptr(self.hp_ws), L.stream_ptr())
         if isinstance(ddepth, AugGrad):  # DiffAugment's adjoint gather inside this launch: the upstream gradient is never written
             g = ddepth
-            rc = lib.dg_head_post_bwd_aug(*head, L.ptr(g.gy), *g.args, g.A.mask, L.ptr(g.gsum), arch, c.tau, c.drop_const, B,
-                                          c.H, c.W, *tail)
+            bwd_aug = lib.dg_head_post_bwd_aug_lt if c.tau_learn else lib.dg_head_post_bwd_aug
+            rc = bwd_aug(*head, L.ptr(g.gy), *g.args, g.A.mask, L.ptr(g.gsum), arch, *self._tau_args(st, True), c.drop_const, B,
+                         c.H, c.W, *tail)
             if rc == L.DG_EUNSUPPORTED:
                 ddepth = g.materialize()
             else:
                 L.check(rc, "dg_head_post_bwd_aug")
                 ddepth = None
         if ddepth is not None:
-            L.check(lib.dg_head_post_bwd(*head, L.ptr(ddepth), arch, c.tau, c.drop_const, B, self.HW, *tail), "dg_head_post_bwd")
+            bwd = lib.dg_head_post_bwd_lt if c.tau_learn else lib.dg_head_post_bwd
+            L.check(bwd(*head, L.ptr(ddepth), arch, *self._tau_args(st, True), c.drop_const, B, self.HW, *tail), "dg_head_post_bwd")
         chain = (self.draw, self.draw_pm, self.dp)
         # The weight gradients of Up1-3 only read finished buffers (a[i-1], dp[i]: nothing below overwrites them), so they are
         # collected while the backward-data chain is issued and leave as ONE launch behind it (dg_wgrad_group, round 5: the ring
@@ -1181,6 +1216,9 @@ class GEngine:
         s_depth, s_conf = self.head_scales
         full = acts is not None
         assert not (full and head_ready)
+        if c.tau_learn and not head_ready:
+            raise NotImplementedError("the path-length walks through the head post-processing (data-only chain, second-order "
+                                      "pass) take tau by value: not implemented for a learnable Gumbel temperature")
         if full:
             L.check(lib.dg_head_post_bwd2(*self._head_saved(), L.ptr(ddepth), L.ptr(thead), arch, c.tau, c.drop_const, B, self.HW,
                                           s_depth, s_conf, L.ptr(draw), st.fptr("head_b", st.grad), L.ptr(draw_pm), self.cp,

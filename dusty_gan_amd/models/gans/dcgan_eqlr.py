@@ -126,6 +126,7 @@ class Generator(_EngineNet):
         self.in_ch, self.ring, self.shape = in_ch, ring, (int(shape[0]), int(shape[1]))
         self.chs = [ch(0), ch(1), ch(2), ch(3)]
         self.tau, self.drop_const = 1.0, -1.0
+        self.tau_learn, self.inv_tau_min = False, 1.0   # (set by a DUSty wrapper built with tau=None: models/dusty.py)
         self.compute_dtype = torch.float32
         self._eng = None
         self.store = E.ParamStore(E.g_segments(in_ch, self.chs, self.shape, 1 + k))
@@ -155,7 +156,8 @@ class Generator(_EngineNet):
         x2 = bool(getattr(self, "fp32_pairs", False))   # (... with split-bf16 storage of the fat feature maps: DG_BF16X2)
         if (self._eng is None or self._eng.dtype != self.compute_dtype
                 or self._eng.ops.x3 != (x3 and self.compute_dtype == torch.float32) or self._eng.x2_asked != x2):
-            cfg = E.NetCfg(self.shape, self.in_ch, self.chs, self.masker, self.ring, self.tau, self.drop_const)
+            cfg = E.NetCfg(self.shape, self.in_ch, self.chs, self.masker, self.ring, self.tau, self.drop_const,
+                           tau_learn=self.tau_learn, inv_tau_min=self.inv_tau_min)
             self._eng = E.GEngine(cfg, self.compute_dtype, x3=x3, x2=x2)
         self._eng.cfg.tau, self._eng.cfg.drop_const = float(self.tau), float(self.drop_const)
         return self._eng

@@ -164,7 +164,7 @@ class FlatAdam:
     def _param_views(self, buf):
         """views of `buf` (grad/m/v) shaped like the module's parameters, in named_parameters() order"""
         st = self.store
-        pairs = _backbone(self.net)._bind_pairs()
+        pairs = self.net._bind_pairs()   # (a DUSty wrapper's: the backbone's, then its temperature weights')
         by_param = {id(p): mk for p, mk in pairs}
         views = []
         saved = st.flat
@@ -460,6 +460,10 @@ class Trainer:
         if self.loss_weight.get("gp", 0) > 0.0:
             self.criterion["gp"] = True
         if self.loss_weight.get("pl", 0) > 0.0:
+            if _backbone(self.G).tau_learn:
+                raise NotImplementedError("solver.loss.pl > 0 with model.gen.tau: null - the path-length penalty's second-order "
+                                          "head pass (dg_head_post_bwd2) has no derivative in the learnable temperature; train "
+                                          "with pl: 0 (the reference's configs do) or a numeric tau")
             self.criterion["pl"] = True  # path-length regularisation (reference :109-111, :268-306)
         self.pl_ema = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._geng_pl = None
@@ -808,7 +812,8 @@ class Trainer:
             # offsets: that is only sound for this segment order (engine.g_segments / d_segments)
             dn, gn = list(self.D.store.seg), list(_backbone(self.G).store.seg)
             assert dn[dn.index("d4_w"):] == ["d4_w", "d4_b", "final_w", "final_b"], dn
-            assert gn == ["proj_w", "proj_b", "up1_w", "up1_b", "up2_w", "up2_b", "up3_w", "up3_b", "head_w", "head_b"], gn
+            assert gn[:10] == ["proj_w", "proj_b", "up1_w", "up1_b", "up2_w", "up2_b", "up3_w", "up3_b", "head_w", "head_b"], gn
+            assert gn[10:] in ([], ["tau_w"]), gn   # (the learnable temperature rides at the end of the tail bucket)
             self._buckets_checked = True
         return on
 

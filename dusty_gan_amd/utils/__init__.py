@@ -50,6 +50,8 @@ def setup(model_path, config_path, ema=True, fix_noise=True, cuda=True):
     G.eval()
     G.load_state_dict(G_state_dict)
     G.to(device)
+    if hasattr(G, "_sync"):
+        G._sync()   # (a learnable temperature: the by-value tau of the inference paths, one host read of the loaded weight)
     if fix_noise:
         for m in G.modules():
             if isinstance(m, GumbelSigmoid):

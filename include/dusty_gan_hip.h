@@ -286,6 +286,23 @@ int dg_head_post_bwd(const float* gout, const float* noise_pixel, const float* n
                      const float* ddepth, int arch, float tau, float drop_const, int B, long HW, float s_depth,
                      float s_conf, float* draw, float* dbias, void* draw_pm /* optional bf16 [B,H,W,cp] copy */, int cp,
                      float* bias_ws, void* stream);
+/* The learnable Gumbel temperature (GumbelSigmoid(tau=None), models/dusty.py:25-26,38-43): the entry points above with `tau`
+ * replaced by tau_w - a DEVICE pointer to the `arch` fp32 master weights, pixel then image (never a bf16 shadow: the kernel
+ * forms the slope inv_k = softplus(w_k) + inv_tau_min itself, so a replayed step graph follows the training) - and
+ * inv_tau_min = 1 / tau_max.  The backward also takes dtau_w, `arch` accumulators added to like dbias:
+ * dtau_w[k] += sigmoid(w_k) * sum over pixels of pre_k s_k (1 - s_k) l_k (l the noisy logit, s its sigmoid, pre the factor in
+ * front of the sigmoid's derivative in d1 / d2); the sums take the path the bias sums take (bias_ws: bit-reproducible).
+ * arch 1 or 2; DG_EINVAL for a NULL tau_w or dtau_w or inv_tau_min <= 0.  dbias may be NULL. */
+int dg_head_post_fwd_lt(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
+                        const float* tau_w, float inv_tau_min, float drop_const, int B, long HW, float* mask, float* depth,
+                        void* stream);
+int dg_head_post_fwd_sum_lt(float* gout, const float* noise_pixel, const float* noise_image, int arch, int training,
+                            const float* tau_w, float inv_tau_min, float drop_const, int B, long HW, float* mask, float* depth,
+                            float* dsum, void* stream);
+int dg_head_post_bwd_lt(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
+                        const float* ddepth, int arch, const float* tau_w, float inv_tau_min, float* dtau_w, float drop_const,
+                        int B, long HW, float s_depth, float s_conf, float* draw, float* dbias, void* draw_pm, int cp,
+                        float* bias_ws, void* stream);
 /* GumbelSigmoid.logistic_noise  models/dusty.py:30-36 */
 int dg_logistic_noise(const float* u1, const float* u2, float eps, long n, float* out, void* stream);
 
@@ -335,6 +352,12 @@ int dg_head_post_bwd_aug(const float* gout, const float* noise_pixel, const floa
                          const int* o_x, const int* o_y, int policy, const float* gsum, int arch, float tau,
                          float drop_const, int B, int H, int W, float s_depth, float s_conf, float* draw, float* dbias,
                          void* draw_pm, int cp, float* bias_ws, void* stream);
+/* ... with the learnable temperature (dg_head_post_bwd_lt's arguments in place of tau) */
+int dg_head_post_bwd_aug_lt(const float* gout, const float* noise_pixel, const float* noise_image, const float* mask,
+                            const float* gy, const float* u_b, const float* u_c, const int* t_h, const int* t_w,
+                            const int* o_x, const int* o_y, int policy, const float* gsum, int arch, const float* tau_w,
+                            float inv_tau_min, float* dtau_w, float drop_const, int B, int H, int W, float s_depth, float s_conf,
+                            float* draw, float* dbias, void* draw_pm, int cp, float* bias_ws, void* stream);
 
 /* ---- GANLoss, all metrics  models/loss.py:39-61 (loss_D), :66-85 (loss_G) ------------------------------------
  * metric: DG_GAN_* below (the reference's `solver.gan_mode` strings in models/loss.py order).  The loss with the step's
