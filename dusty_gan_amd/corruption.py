@@ -16,7 +16,7 @@ from . import _lib as L
 
 CORRUPTIONS = ("additive noise", "low resolution", "dropout", "closing")   # the demo's option names (demo.py:241)
 ALIASES = {"additive_noise": "additive noise", "low_resolution": "low resolution"}   # the command line's spellings
-STREAM_CORRUPT = 14    # Philox stream id (inversion.py lists the others)
+STREAM_CORRUPT = 14    # Philox stream id (inversion.py lists the others: 0-16)
 HOLE_THRESH = 1e-8     # closing: `inv > 1e-8` is valid (demo.py:120)
 MAX_PIXELS = 1 << 18   # dg_hole_fill
 

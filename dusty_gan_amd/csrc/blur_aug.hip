@@ -330,8 +330,8 @@ __global__ __launch_bounds__(256) void sample_sum_kernel(const float* __restrict
 }
 
 // ----------------------------------------------------------------------------------------------------------
-// DiffAugment (utils/diff_augment.py:114-132, p = 1) on [B,1,H,W] fp32, one fused gather pass; its geometry and arithmetic are
-// diffaug.h's.  xsum[b] = sum of x[b] (needed by contrast: mean of x + brightness).
+// DiffAugment (utils/diff_augment.py:114-132, any p: the per-sample gates arrive as DG_AUG_OFF in t_h / o_x) on [B,1,H,W] fp32, one
+// fused gather pass; its geometry and arithmetic are diffaug.h's.  xsum[b] = sum of x[b] (needed by contrast: mean of x + brightness).
 
 // One block per image row (blockIdx.x = row, blockIdx.y = sample): everything that depends on the sample or the row is
 // block-uniform, the per-pixel work is 32-bit (the first version decoded a flat 64-bit index per pixel: three 64-bit

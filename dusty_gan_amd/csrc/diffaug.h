@@ -1,10 +1,15 @@
-// DiffAugment's geometry and arithmetic, written ONCE (utils/diff_augment.py:114-132, p = 1) for every kernel that evaluates it:
+// DiffAugment's geometry and arithmetic, written ONCE (utils/diff_augment.py:114-132, any p) for every kernel that evaluates it:
 // the forward gathers and the adjoint's sum and gather (blur_aug.hip), the BlurVH adjoint's window sum (blur_aug.hip) and the
 // head post-processing's backward, which applies the adjoint gather on the fly (head_post.hip, HeadGradAug).  Every one of the
 // reference's quirks lives here and nowhere else: the applied factor is u * u, the translation wraps columns
 // modulo W - 1, so that output columns 0 and W - 1 read the same source column, and shifted-out rows read zero.
 // policy bits: 1 brightness, 2 saturation (identity for one channel), 4 contrast, 8 translation, 16 cutout.
 // Per-sample parameters: u_b, u_c (the uniform(-1,1) draws), t_h, t_w, o_x, o_y ints.
+// The gate of p < 1 (rand_translation / rand_cutout restore y[~mask] = x[~mask], :53-102) is per SAMPLE and travels in those
+// arrays: t_h[b] == DG_AUG_OFF switches the translation off for sample b, o_x[b] == DG_AUG_OFF the cutout - the stage is then
+// what it is outside the policy, the exact identity (a shift by 0 would not be: the wrap modulo W - 1 folds column W - 1 onto
+// column 0).  So whatever chooses between "the stage runs" and "it does not" below chooses on AugSample::tr / ::cut, never on the
+// policy bit.  The colour stages have no gate: the reference overwrites their Bernoulli draw.
 #pragma once
 #include "common.h"
 
@@ -24,24 +29,34 @@ static AugP make_aug(const float* u_b, const float* u_c, const int* t_h, const i
 }
 
 // ---- the per-sample part.  A stage that is not in the policy leaves its identity: no shift, br = 0, cc = 1 (r0 / cl are
-//      read under the policy bit only: aug_row).
+//      read under AugSample::cut only: aug_row).
 struct AugSample {
   int th, tw, wm;  // row shift; column shift t_w mod wm, non-negative; the column modulus: W - 1 under translation (the
                    // reference's wrap), W without it (never reached: no wrap)
   int r0, cl;      // the cut-out box [r0, r0 + cut_h) x [cl, cl + cut_w), in the augmented image's coordinates
+  bool tr, cut;    // the stage runs for THIS sample: in the policy and not gated off (block- or wave-uniform in every caller:
+                   // the sample index is, so the compares below stay on the scalar side)
   float br, cc;    // brightness 0.5 u^2, contrast 1 + 0.5 u^2
 };
 // which pixels of the augmented image come from the source image at all: the row shift and the box (t_h, o_x, o_y only - the
-// BlurVH adjoint's window sum has no other parameter)
+// BlurVH adjoint's window sum has no other parameter; both sentinels arrive in these)
 __device__ __forceinline__ AugSample aug_window(const AugP& a, int b) {
-  AugSample s = {0, 0, a.W, 0, 0, 0.f, 1.f};
-  if (a.policy & 8) s.th = a.t_h[b];
-  if (a.policy & 16) { s.r0 = a.o_x[b] - a.cut_h / 2; s.cl = a.o_y[b] - a.cut_w / 2; }
+  AugSample s = {0, 0, a.W, 0, 0, false, false, 0.f, 1.f};
+  if (a.policy & 8) {
+    const int th = a.t_h[b];
+    s.tr = th != DG_AUG_OFF;
+    s.th = s.tr ? th : 0;
+  }
+  if (a.policy & 16) {
+    const int ox = a.o_x[b];
+    s.cut = ox != DG_AUG_OFF;
+    if (s.cut) { s.r0 = ox - a.cut_h / 2; s.cl = a.o_y[b] - a.cut_w / 2; }
+  }
   return s;
 }
 __device__ __forceinline__ AugSample aug_sample(const AugP& a, int b) {
   AugSample s = aug_window(a, b);
-  if (a.policy & 8) {
+  if (s.tr) {
     const int Wm1 = a.W - 1;
     s.wm = Wm1;
     s.tw = a.t_w[b] % Wm1;
@@ -70,7 +85,7 @@ __device__ __forceinline__ AugRow aug_row(const AugP& a, const AugSample& s, int
   r.y = kAdjoint ? y - s.th : y + s.th;
   r.ok = r.y >= 0 && r.y < a.H;
   const int ya = kAdjoint ? r.y : y;
-  const bool cut = (a.policy & 16) && ya >= s.r0 && ya < s.r0 + a.cut_h;
+  const bool cut = s.cut && ya >= s.r0 && ya < s.r0 + a.cut_h;
   r.c0 = cut ? s.cl : 0;
   r.c1 = cut ? s.cl + a.cut_w : 0;
   return r;
@@ -99,7 +114,7 @@ __device__ __forceinline__ float aug_adj_px(const AugP& a, const AugSample& s, c
                                             float gb, float gm, int c) {
   const int W = a.W;
   float g2 = 0.f;  // gradient w.r.t. the pre-translation image at column c
-  if (a.policy & 8) {
+  if (s.tr) {
     int w1 = c - s.tw;                                               // (c - t_w) mod (W - 1)
     if (w1 < 0) w1 += W - 1;
     const float ga = grow[w1];

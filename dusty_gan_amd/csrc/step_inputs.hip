@@ -90,9 +90,27 @@ __device__ __forceinline__ void aug_draw_body(uint64_t seed, uint64_t stream, ui
   qi[2 * B + b] = (int)(r1[2] % (uint32_t)nx);
   qi[3 * B + b] = (int)(r1[3] % (uint32_t)ny);
 }
+// The gates of DiffAugment(policy, p < 1) (rand_translation / rand_cutout, utils/diff_augment.py:59,86: mask = bernoulli_(p)), AFTER
+// the sample's seven numbers, which stay what they are: one more Philox block at the sample's FIRST counter under a stream of
+// its own, DG_STREAM_AUG_GATE | the caller's stream id << 32 (two augmenters of one seed on different streams gate apart) - word 0 gates the translation, word 1 the cutout, ON iff u < p with u a 24-bit uniform in [0, 1), so p = 1 never
+// gates a stage off and p = 0 always does.  A sample's gates depend on (seed, stream, its counter) alone.  Off: DG_AUG_OFF in t_h / o_x.
+struct AugGate { int on; float p; const float* p_dev; };   // p_dev: p read when the draw runs (a captured step follows the memory)
+__device__ __forceinline__ void aug_gate_body(uint64_t seed, uint64_t stream, uint64_t offset, int B, const AugGate& gt, int* __restrict__ qi, int b) {
+  if (!gt.on || b >= B) return;
+  const float p = gt.p_dev ? *gt.p_dev : gt.p;
+  uint32_t r[4];
+  philox4x32_10(seed, offset + 2 * (uint64_t)b, (uint64_t)DG_STREAM_AUG_GATE | (stream << 32), r);
+  const float s24 = 1.f / 16777216.f;
+  if (!((float)(r[0] >> 8) * s24 < p)) qi[0 * B + b] = DG_AUG_OFF;
+  if (!((float)(r[1] >> 8) * s24 < p)) qi[2 * B + b] = DG_AUG_OFF;
+}
+__host__ __device__ __forceinline__ AugGate aug_gate(float p, const float* p_dev) { return {p_dev != nullptr || p != 1.f, p, p_dev}; }
 __global__ void aug_draw_dev_kernel(uint64_t seed, uint64_t stream, const unsigned long long* __restrict__ offp, uint64_t base,
-                                    int B, AugGeom g, float* __restrict__ uf, int* __restrict__ qi) {
-  aug_draw_body(seed, stream, draw_offset(offp, base), B, g.sh, g.sw, g.nx, g.ny, uf, qi, blockIdx.x * blockDim.x + threadIdx.x);
+                                    int B, AugGeom g, AugGate gt, float* __restrict__ uf, int* __restrict__ qi) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t offset = draw_offset(offp, base);
+  aug_draw_body(seed, stream, offset, B, g.sh, g.sw, g.nx, g.ny, uf, qi, b);
+  aug_gate_body(seed, stream, offset, B, gt, qi, b);
 }
 
 // (dg_counter_add* advance a counter after its consumers, in stream order)
@@ -245,6 +263,7 @@ __global__ __launch_bounds__(256) void step_prologue_kernel(PrologueZero z, Prol
   } else {
     const AugGeom g = aug_geom(d.H, d.W);
     aug_draw_body(d.seed, d.stream_id, offset, d.B, g.sh, g.sw, g.nx, g.ny, d.uf, d.qi, (int)i);
+    aug_gate_body(d.seed, d.stream_id, offset, d.B, aug_gate(d.p, d.p_dev), d.qi, (int)i);
   }
 }
 
@@ -293,18 +312,29 @@ int dg_logistic_noise(const float* u1, const float* u2, float eps, long n, float
   return DG_OK;
 }
 
+static bool aug_p_ok(float p) { return p >= 0.f && p <= 1.f; }   // (false for a NaN)
 static int aug_draw(uint64_t seed, uint64_t stream, const unsigned long long* offset_dev, uint64_t base, int B, int H, int W,
-                    float* uf, int* qi, void* s_) {
-  aug_draw_dev_kernel<<<nblk(B), 256, 0, (hipStream_t)s_>>>(seed, stream, offset_dev, base, B, aug_geom(H, W), uf, qi);
+                    float p, const float* p_dev, float* uf, int* qi, void* s_) {
+  if (!uf || !qi || B <= 0 || H <= 0 || W <= 0 || !aug_p_ok(p)) return DG_EINVAL;
+  aug_draw_dev_kernel<<<nblk(B), 256, 0, (hipStream_t)s_>>>(seed, stream, offset_dev, base, B, aug_geom(H, W), aug_gate(p, p_dev),
+                                                            uf, qi);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }
 int dg_aug_draw(uint64_t seed, uint64_t stream, uint64_t offset, int B, int H, int W, float* uf, int* qi, void* s_) {
-  return aug_draw(seed, stream, nullptr, offset, B, H, W, uf, qi, s_);
+  return aug_draw(seed, stream, nullptr, offset, B, H, W, 1.f, nullptr, uf, qi, s_);
 }
 int dg_aug_draw_dev(uint64_t seed, uint64_t stream, const unsigned long long* offset_dev, int B, int H, int W,
                     float* uf, int* qi, void* s_) {
-  return aug_draw(seed, stream, offset_dev, 0, B, H, W, uf, qi, s_);
+  return aug_draw(seed, stream, offset_dev, 0, B, H, W, 1.f, nullptr, uf, qi, s_);
+}
+int dg_aug_draw_p(uint64_t seed, uint64_t stream, uint64_t offset, int B, int H, int W, float p, float* uf, int* qi, void* s_) {
+  return aug_draw(seed, stream, nullptr, offset, B, H, W, p, nullptr, uf, qi, s_);
+}
+int dg_aug_draw_p_dev(uint64_t seed, uint64_t stream, const unsigned long long* offset_dev, int B, int H, int W,
+                      const float* p_dev, float* uf, int* qi, void* s_) {
+  if (!offset_dev || !p_dev) return DG_EINVAL;
+  return aug_draw(seed, stream, offset_dev, 0, B, H, W, 1.f, p_dev, uf, qi, s_);
 }
 
 // k <= 8 DISTINCT counters advanced by one launch (one graph node instead of one per counter)
@@ -421,7 +451,7 @@ static int step_prologue_impl(float* const* ptrs, const long* counts, int k, con
       if (!d.out || d.n <= 0) return DG_EINVAL;
       threads = (d.n + 3) / 4;
     } else if (d.kind == 2) {
-      if (!d.uf || !d.qi || d.B <= 0 || d.H <= 0 || d.W <= 0) return DG_EINVAL;
+      if (!d.uf || !d.qi || d.B <= 0 || d.H <= 0 || d.W <= 0 || !aug_p_ok(d.p)) return DG_EINVAL;
       threads = d.B;
     } else {
       return DG_EINVAL;

@@ -22,7 +22,8 @@ from . import _lib as L
 from . import engine as E
 
 # Philox stream ids of the inversion's own draws (the model's and the trainer's generators use 0-9); 14 is the target
-# corruptions' (corruption.STREAM_CORRUPT), 15 the ray-drop transfer's (raydrop.STREAM_RAYDROP)
+# corruptions' (corruption.STREAM_CORRUPT), 15 the ray-drop transfer's (raydrop.STREAM_RAYDROP), 16 the gates of DiffAugment with
+# p < 1 (DG_STREAM_AUG_GATE, include/dusty_gan_hip.h: the low word of the gate block's stream, the augmenter's own id the high one)
 STREAM_LATENT, STREAM_PERTURB, STREAM_GUMBEL = 11, 12, 13
 
 

@@ -402,7 +402,29 @@ class Trainer:
         # reference's (train.py:159-166) - records
         self.world = _world()
         self._job_seed = D_.broadcast_int(torch.initial_seed() & (2**62 - 1), self.device, src=0)
+        # DiffAugment's probability: `solver.augment_p` (absent: 1, the reference trainer's), fixed - or, with
+        # `solver.ada.target` set, the start of the adaptive controller (csrc/ada.hip), whose p lives in device memory where
+        # the step's draw reads it.  Both keys are read with defaults: the shipped YAML files do not carry them.
+        augment_p = float(self.cfg.solver.get("augment_p", 1.0))
+        ada = self.cfg.solver.get("ada", None)
+        self.ada = None
+        if ada is not None and ada.get("target", None) is not None:
+            self.ada = {"target": float(ada.target), "interval": int(ada.get("interval", 4)), "kimg": float(ada.get("kimg", 500))}
+            if not 0.0 <= augment_p <= 1.0:
+                raise ValueError(f"solver.augment_p = {augment_p}: outside [0, 1]")
+            if not -1.0 <= self.ada["target"] <= 1.0:
+                raise ValueError(f"solver.ada.target = {self.ada['target']}: a mean sign lies in [-1, 1]")
+            if self.ada["interval"] < 1:
+                raise ValueError(f"solver.ada.interval = {self.ada['interval']}: at least 1 iteration")
+            if not self.ada["kimg"] > 0.0:
+                raise ValueError(f"solver.ada.kimg = {self.ada['kimg']}: must be positive")
+            # DgAdaState {float p; int64 sign_sum, count; int32 steps} as eight 32-bit words, and the iteration's pending sums
+            self._ada_state = torch.zeros(8, dtype=torch.int32, device=self.device)
+            self._ada_pend = torch.zeros(2, dtype=torch.int64, device=self.device)
+            self._ada_p = self._ada_state[:1].view(torch.float32)
+            self._ada_p.fill_(augment_p)
         self.A = DiffAugment(policy=list(self.cfg.solver.augment) if self.cfg.solver.augment is not None else None,
+                             p=self._ada_p if self.ada is not None else augment_p,
                              seed=self._job_seed + 101 + 7919 * _rank())   # (fixed at construction: the lazy default reads
                                                                             #  torch's GLOBAL seed at the first draw)
         H, W = self.cfg.dataset.shape
@@ -509,6 +531,8 @@ class Trainer:
         self.fixed_noise = self.sample_latents(self.local_batch)
         if resume_extra is not None:
             self._restore_position(resume_extra)
+            if self.ada is not None and resume_extra.get("ada") is not None:   # (absent: the run starts at solver.augment_p)
+                self._ada_restore(resume_extra["ada"])
         self._geng = None
         self._dev_scal = None
         self._mb = []               # the D phase's micro-batches, kept for the G phase: x_real, m_real, rand, synth, geng
@@ -609,7 +633,7 @@ class Trainer:
         n_sets = 4
         uf = torch.empty(3, n_sets * B, **f32)
         qi = torch.empty(4, n_sets * B, dtype=torch.int32, device=dev)
-        jobs.append(ra.job(2, 0, B=n_sets * B, H=self.H, W=self.W, uf=L.ptr(uf), qi=L.ptr(qi)))
+        jobs.append(ra.job(2, 0, **self.A.draw_job(n_sets * B, self.H, self.W, uf, qi)))
         self._predrawn = {"z": z, "noise": noise, "aug": self.A.sets_of(uf, qi, n_sets, B), "z_ready": z_ready, "B": B}
 
         def advance(total=base):
@@ -860,9 +884,17 @@ class Trainer:
             self._grads_zeroed.discard("D")
         else:
             self.optim_D.zero_grad()
-        scal = L.AccArena.take(16, self.device)[:7]
+        scal16 = L.AccArena.take(16, self.device)
+        scal = scal16[:7]
+        self._ada_scal = scal16[7:9] if self.ada is not None else None   # augment/rt, augment/p (slots 7 and 8 of the slice)
         for j in gradient_accumulation(self.n_acc, True, (self.G, self.D)):
             extra_D = self._d_micro_batch(j, deng, gp, scal, reals, rands)
+        if self.ada is not None and self.world > 1:
+            # every rank applies the same adjustment: the iteration's integer sign sum and count are summed over the ranks
+            # (a host-side collective between two graph segments, as the gradient exchange's), then the window takes them
+            pend = self._ada_pend
+            self._coll(lambda: D_.allreduce_sum(pend), name="all-reduce ADA signs")
+            self._ada_update(None, 0, True)
         if self._bucketed():
             self._allreduce_async("D.lo", Dst.grad[:Dst.seg["d4_w"].off])
             self._comm_wait("D.hi", "D.lo")
@@ -886,6 +918,8 @@ class Trainer:
                              z_ready=bool(rand.get("z_ready")) and j == 0)
         # :199-204  A(real) | A(fake) -> D, one pass; DiffAugment fused into BlurVH's pass where the sums exist
         y = deng.forward_aug(Dst, self.A, [(x_real, rand["aug"][0]), (synth["depth"], rand["aug"][1])], 0)
+        if self.ada is not None:   # :203's y_real steers p; every micro-batch counts, the last one ends the iteration
+            self._ada_update(y, B, self.world == 1 and j == self.n_acc - 1)
         # loss + dLoss/dy + the R1 schedule's per-sample vectors + scalar sums + final-bias gradient: one launch
         # chain upstream `up`: 1 for the real half (that IS d sum(y_real)/dx, :218-223), dLoss/dy for the fake half;
         # `rs`: the real half's ordinary backward is the same chain weighted per sample by dLoss/dy_real
@@ -910,6 +944,30 @@ class Trainer:
         extra_D = self._d_weight_grads(deng, Dst, B, gp, rs, dy, fused)
         self._mb.append({"x_real": x_real, "m_real": m_real, "rand": rand, "synth": synth, "geng": geng})
         return extra_D
+
+    def _ada_update(self, y, B, advance):
+        """one dg_ada_update launch: the signs of y[:B] (None: none) into the iteration's pending sums; advance: the iteration
+        ends - the window takes them and, every `interval` iterations, p moves.  The step's scalars augment/rt (the mean sign,
+        averaged over the micro-batches) and augment/p are written beside the others."""
+        a = self.ada
+        L.check(L.lib().dg_ada_update(L.ptr(y), B, L.ptr(self._ada_state), L.ptr(self._ada_pend), int(advance), a["target"],
+                                      a["interval"], int(self.cfg.solver.batch_size), a["kimg"], 1.0 / self.n_acc,
+                                      L.ptr(self._ada_scal), L.ptr(self._ada_scal) + 4, L.stream_ptr()), "dg_ada_update")
+
+    def _ada_record(self):
+        """{p, sign_sum, count, steps} of the controller (checkpoints); p as the float32 it is"""
+        w = self._ada_state.cpu()
+        q = w.view(torch.int64)
+        return {"p": float(w[:1].view(torch.float32)[0]), "sign_sum": int(q[1]), "count": int(q[2]), "steps": int(w[6])}
+
+    def _ada_restore(self, st):
+        w = torch.zeros(8, dtype=torch.int32)
+        w[:1].view(torch.float32)[0] = float(st["p"])
+        q = w.view(torch.int64)
+        q[1], q[2] = int(st["sign_sum"]), int(st["count"])
+        w[6] = int(st["steps"])
+        self._ada_state.copy_(w)   # (in place: DiffAugment's p is a view of this storage)
+        self._ada_pend.zero_()
 
     def _r1_rowscale(self, B):
         """per-sample weights of the weight-gradient sums over the 3B input slots real | fake | tangent: the loss step's
@@ -1209,9 +1267,17 @@ class Trainer:
         if "pl" in self.criterion:
             keys += ["loss/G/path_length/baseline", "loss/G/path_length"]
             idx += [5, 6]
+        if self.ada is not None:
+            keys += ["augment/rt", "augment/p"]
+            idx += [7, 8]
         return keys, idx
 
     SCALAR_RING = 64
+
+    def _snap_n(self):
+        """floats of the step's arena slice a ring slot holds: the seven loss scalars' eight, or - with the controller - nine
+        (augment/rt and augment/p are slots 7 and 8)"""
+        return 9 if self.ada is not None else 8
 
     def _use_ring(self):
         return self.world == 1 and self.n_acc == 1 and os.environ.get("DUSTY_GAN_SCALAR_RING", "1") != "0"
@@ -1233,10 +1299,10 @@ class Trainer:
             # every pending counter advance and the scalar snapshot (the scalars live in `scal`, the step's arena slice,
             # for both phases); whatever is still pending afterwards goes out with the flush below
             if self._snap_ring is None:
-                self._snap_ring = torch.zeros(self.SCALAR_RING, 8, dtype=torch.float32).pin_memory()
+                self._snap_ring = torch.zeros(self.SCALAR_RING, self._snap_n(), dtype=torch.float32).pin_memory()
                 self._snap_ctr = torch.full((1,), self._snap_pos, dtype=torch.int64, device=self.device)
             L.Counters.add(self._snap_ctr, 1)
-            L.Counters.snapshot(self._snap_ctr, scal.data_ptr(), 8, self._snap_ring.data_ptr(), self.SCALAR_RING)
+            L.Counters.snapshot(self._snap_ctr, scal.data_ptr(), self._snap_n(), self._snap_ring.data_ptr(), self.SCALAR_RING)
             L.Counters.ride = True
             try:
                 self.optimize_G()
@@ -1257,7 +1323,9 @@ class Trainer:
         # (while capturing: the replay loop copies the arena slice after every replay - no copy node inside the graph)
         # (slices, not a Python index list: that would be a host-to-device copy, illegal during graph capture)
         end = 7 if "pl" in self.criterion else 5
-        return scal[:end] if "gp" in self.criterion else torch.cat((scal[:3], scal[4:end]))
+        out = scal[:end] if "gp" in self.criterion else torch.cat((scal[:3], scal[4:end]))
+        # (the controller's two: already the iteration's - the kernel weights each micro-batch's mean sign by 1 / n_acc)
+        return out if self.ada is None else torch.cat((out, self._ada_scal))
 
     def _graph_eligible(self, reals, rands):
         # world > 1: the step is replayed as hipGraph segments with the collectives issued between them (eager launches
@@ -1523,8 +1591,11 @@ class Trainer:
         the number of batches drawn from the loader, per rank"""
         def ph(r):
             return None if r is None else {"seed": r.seed, "stream_id": r.stream_id, "offset": r.offset}
-        return {"rank": _rank(), "world": self.world, "rng": ph(self.rng), "augment_rng": ph(self.A._rng),
-                "fixed_noise": self.fixed_noise.detach().cpu(), "batches_drawn": self.batches_drawn}
+        st = {"rank": _rank(), "world": self.world, "rng": ph(self.rng), "augment_rng": ph(self.A._rng),
+              "fixed_noise": self.fixed_noise.detach().cpu(), "batches_drawn": self.batches_drawn}
+        if self.ada is not None:
+            st["ada"] = self._ada_record()   # (the same on every rank: the window is summed over the ranks)
+        return st
 
     def _restore_position(self, st):
         """Continue from a checkpoint's position record.  The record is the WRITING rank's (rank 0 saves, as in the

@@ -1,10 +1,15 @@
-"""DiffAugment on [B,1,H,W] range images -- reference: utils/diff_augment.py:114-132 (p = 1.0).
+"""DiffAugment on [B,1,H,W] range images -- reference: utils/diff_augment.py:114-132, any probability 0 <= p <= 1.
 
 One fused gather kernel per call (csrc/blur_aug.hip, csrc/diffaug.h) instead of the reference's ~40 small ops, plus the hand-derived
 backward (the G phase differentiates through A(fake), trainers/dcgan_amp.py:256).  Every random draw of one call is
 an explicit parameter set `rp` so parity tests can inject the reference's draws:
     u_b,u_s,u_c float [B] (the uniform_(-1,1) draws; the applied factor is u*u),
     t_h,t_w,o_x,o_y int [B].
+The gate of p < 1 is per sample and per stage, and only translation and cutout have one (the reference restores
+y[~mask] = x[~mask] there, :77-78,99-100; its colour stages overwrite their Bernoulli draw, so p never reaches them).  There is
+no g_t / g_c array: a parameter set marks a gated-off stage by the sentinel itself - t_h[b] == AUG_OFF switches the translation
+off for sample b (t_w[b] is ignored), o_x[b] == AUG_OFF the cutout (o_y[b] ignored) - and every kernel then leaves that stage
+the exact identity for that sample (csrc/diffaug.h).  Golden parameter sets are injected in the same form.
 """
 import torch
 from torch import nn
@@ -12,6 +17,7 @@ from torch import nn
 from .. import _lib as L
 from .rng import Philox
 
+AUG_OFF = L.DG_AUG_OFF    # INT32_MIN: no draw produces it
 DEFAULT_POLICY = ["brightness", "saturation", "contrast", "translation", "cutout"]
 
 
@@ -28,8 +34,15 @@ class DiffAugment(nn.Module):
         order = [k for k in DEFAULT_POLICY if k in self.policy]
         if [k for k in self.policy if k in DEFAULT_POLICY] != order or len(set(self.policy)) != len(self.policy):
             raise NotImplementedError(f"DiffAugment policy order {self.policy}: the kernel applies {order}")
-        if p != 1.0:
-            raise NotImplementedError("DiffAugment probability p != 1 (the reference trainer always uses p=1)")
+        # p: a float in [0, 1], or a device scalar (float32 [1]) read when a draw runs - the adaptive controller's p, which a
+        # captured step follows (trainers/dcgan_amp.py)
+        if isinstance(p, torch.Tensor):
+            if p.dtype != torch.float32 or p.numel() != 1 or not p.is_cuda:
+                raise ValueError("DiffAugment p as a tensor: one float32 on the GPU")
+        else:
+            p = float(p)
+            if not 0.0 <= p <= 1.0:      # (a NaN fails both compares)
+                raise ValueError(f"DiffAugment probability p = {p}: outside [0, 1]")
         self.p = p
         self.mask = L.policy_mask(self.policy)
         self._seed = seed
@@ -53,10 +66,27 @@ class DiffAugment(nn.Module):
         uf = torch.empty(3, n * B, dtype=torch.float32, device=device)
         qi = torch.empty(4, n * B, dtype=torch.int32, device=device)
         r.sync()
-        L.check(L.lib().dg_aug_draw_dev(r.seed, r.stream_id, L.ptr(r.ctr), n * B, H, W, L.ptr(uf), L.ptr(qi),
-                                        L.stream_ptr()), "dg_aug_draw_dev")
+        if isinstance(self.p, torch.Tensor):
+            L.check(L.lib().dg_aug_draw_p_dev(r.seed, r.stream_id, L.ptr(r.ctr), n * B, H, W, L.ptr(self.p), L.ptr(uf), L.ptr(qi),
+                                              L.stream_ptr()), "dg_aug_draw_p_dev")
+        elif self.p != 1.0:
+            # (the prologue's draw job: the device counter, with p a plain argument)
+            d = r.job(2, 0, **self.draw_job(n * B, H, W, uf, qi))
+            L.step_prologue([], [d])
+        else:
+            L.check(L.lib().dg_aug_draw_dev(r.seed, r.stream_id, L.ptr(r.ctr), n * B, H, W, L.ptr(uf), L.ptr(qi),
+                                            L.stream_ptr()), "dg_aug_draw_dev")
         r.advance(2 * n * B)
         return self.sets_of(uf, qi, n, B)
+
+    def draw_job(self, nB, H, W, uf, qi):
+        """the fields of a kind-2 DgDraw for nB samples with this module's p source (Philox.job adds the generator's)"""
+        kw = dict(B=nB, H=H, W=W, uf=L.ptr(uf), qi=L.ptr(qi))
+        if isinstance(self.p, torch.Tensor):
+            kw["p_dev"] = L.ptr(self.p)
+        else:
+            kw["p"] = self.p
+        return kw
 
     @staticmethod
     def sets_of(uf, qi, n, B):
@@ -70,7 +100,8 @@ class DiffAugment(nn.Module):
 
     @staticmethod
     def params_to_device(rp, device):
-        """Accept CPU / int64 parameter sets (golden vectors) and put them in the kernel's dtypes."""
+        """Accept CPU / int64 parameter sets (golden vectors) and put them in the kernel's dtypes.  AUG_OFF passes through: it
+        is an int32 number."""
         out = {}
         for k, v in rp.items():
             v = torch.as_tensor(v)

@@ -118,6 +118,14 @@ def allreduce_grads(flat_grad, async_op=False):
     return (work if async_op else None), 1.0 / w
 
 
+def allreduce_sum(t):
+    """SUM all-reduce of a small integer tensor in place (the adaptive augmentation controller's sign sum and count): every
+    rank then holds the job's totals.  Nothing to do in a single process."""
+    if through_backend():
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t
+
+
 def mean_scalars(t):
     """one packed collective for the logged scalars (the reference does one all_reduce + .item() per key,
     trainers/dcgan_amp.py:319-323), issued asynchronously: returns (tensor, finish) where `finish()` waits for the

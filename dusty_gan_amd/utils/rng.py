@@ -47,6 +47,7 @@ class Philox:
         same launch take); the caller syncs before the launch and advances afterwards, as the single draws do"""
         d = L.DgDraw()
         d.kind, d.seed, d.stream_id, d.offset_dev, d.base = kind, self.seed, self.stream_id, L.ptr(self.ctr), int(base)
+        d.p = 1.0   # (kind 2: DiffAugment's probability; 1 and no p_dev draws no gates)
         for k, v in kw.items():
             setattr(d, k, v)
         return d

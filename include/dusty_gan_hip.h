@@ -306,8 +306,14 @@ int dg_head_post_bwd_lt(const float* gout, const float* noise_pixel, const float
 /* GumbelSigmoid.logistic_noise  models/dusty.py:30-36 */
 int dg_logistic_noise(const float* u1, const float* u2, float eps, long n, float* out, void* stream);
 
-/* ---- DiffAugment.forward  utils/diff_augment.py:114-132 (p = 1) and its backward ------------------------- */
+/* ---- DiffAugment.forward  utils/diff_augment.py:114-132 and its backward ---------------------------------- */
 /* policy bits: 1 brightness, 2 saturation, 4 contrast, 8 translation, 16 cutout; per-sample draws are arguments */
+/* The per-sample gate of DiffAugment(policy, p < 1) (rand_translation / rand_cutout restore y[~mask] = x[~mask],
+ * utils/diff_augment.py:53-102) travels in the parameter arrays every entry point below already takes: t_h[b] == DG_AUG_OFF
+ * switches the translation off for sample b (t_w[b] is then ignored), o_x[b] == DG_AUG_OFF the cutout (o_y[b] ignored) - the
+ * stage is then the exact identity for that sample, as if it were not in the policy.  INT32_MIN: no draw produces it.  The
+ * colour stages have no gate (the reference overwrites their Bernoulli draw). */
+#define DG_AUG_OFF (-2147483647 - 1)
 int dg_diffaug_fwd(const float* x, const float* u_b, const float* u_c, const int* t_h, const int* t_w, const int* o_x,
                    const int* o_y, int policy, int B, int H, int W, float* xsum_ws, float* y, void* stream);
 int dg_diffaug_fwd_acc(const float* x, const float* u_b, const float* u_c, const int* t_h, const int* t_w, const int* o_x,
@@ -633,6 +639,14 @@ int dg_philox_fill(uint64_t seed, uint64_t stream_id, uint64_t offset, int kind,
  * (ranges of utils/diff_augment.py:58-60,85-87); consumes 2*B Philox counters starting at `offset` */
 int dg_aug_draw(uint64_t seed, uint64_t stream_id, uint64_t offset, int B, int H, int W, float* uf, int* qi,
                 void* stream);
+/* ... for DiffAugment(policy, p): the same seven numbers, then the two gates of sample b from ONE more Philox block at the
+ * sample's first counter, offset + 2 b, under the stream DG_STREAM_AUG_GATE | stream_id << 32 (the caller's stream id in the high
+ * word: augmenters of one seed on different streams draw different gates; the counter advance stays 2 per sample): word 0
+ * gates the translation, word 1 the cutout, a stage is ON iff u < p with u = (word >> 8) 2^-24; a stage that is off gets
+ * DG_AUG_OFF in t_h[b] / o_x[b].  p == 1 draws no gates: dg_aug_draw itself.  DG_EINVAL unless 0 <= p <= 1. */
+#define DG_STREAM_AUG_GATE 16
+int dg_aug_draw_p(uint64_t seed, uint64_t stream_id, uint64_t offset, int B, int H, int W, float p, float* uf, int* qi,
+                  void* stream);
 
 /* ---- device-resident counters (hipGraph-friendly variants): Philox offset / Adam step count read from device memory;
  *      dg_counter_add advances a counter after its consumers.  A step captured once replays with fresh draws. */
@@ -670,6 +684,9 @@ typedef struct DgDraw {
   int B, H, W;               /* kind 2 */
   float* uf;                 /* kind 2: [3][B] */
   int* qi;                   /* kind 2: [4][B] */
+  float p;                   /* kind 2: DiffAugment's probability (dg_aug_draw_p); 1 and no p_dev: no gates are drawn.  NOT neutral
+                              * at zero: a zero-initialised DgDraw has p = 0, which gates every sample off - set 1 for today's draw */
+  const float* p_dev;        /* kind 2, optional: p read from device memory when the draw runs (dg_aug_draw_p_dev) */
 } DgDraw;
 int dg_step_prologue(float* const* zero_ptrs, const long* zero_counts, int k, const DgDraw* draws, int ndraw, void* stream);
 /* ... and fetch_reals of the step's batch as more workgroups of the SAME launch (round 6; trainers/dcgan_amp.py:154-160 with
@@ -708,6 +725,27 @@ int dg_resident_gather(const float* store, long nslab, int B, long HW, long slab
                        float* mask, void* stream);
 int dg_aug_draw_dev(uint64_t seed, uint64_t stream_id, const unsigned long long* offset_dev, int B, int H, int W,
                     float* uf, int* qi, void* stream);
+/* dg_aug_draw_p from the device-resident counter, with p itself read from device memory WHEN THE DRAW RUNS (a captured step
+ * follows the adaptive controller's p, dg_ada_update); a p outside [0, 1] or not finite acts as its clamp (NaN: 0) */
+int dg_aug_draw_p_dev(uint64_t seed, uint64_t stream_id, const unsigned long long* offset_dev, int B, int H, int W,
+                      const float* p_dev, float* uf, int* qi, void* stream);
+/* ---- the adaptive controller of DiffAugment's p (StyleGAN2-ADA's rule; the reference's p is a constant,
+ *      utils/diff_augment.py:114-122): one single-workgroup launch per D phase, only when the controller is on.
+ * state (device memory, the layout below; `p` is what dg_aug_draw_p_dev / DgDraw.p_dev read) and pend (device, two integers:
+ * the sign sum and count of the iteration under way).
+ * y_real != NULL (the D phase's real logits [B], trainers/dcgan_amp.py:203): pend += {sum_b sign(y_real[b]), B} - sign as
+ * torch.sign, a logit that is not finite counts 0 - and rt_slot[0] += rt_scale * (this call's sum / B) (optional).
+ * advance != 0 (the iteration's last call; with several ranks the caller sums pend over the ranks first, then calls with
+ * y_real == NULL): window += pend, pend = 0, steps += 1, and at steps % interval == 0:  r_t = sign_sum / count,
+ * p = clamp(p + sign(r_t - target) * (batch_size * interval) / (kimg * 1000), 0, 1) in float32 in this order, window = 0.
+ * p_slot[0] = p behind this call (optional).  Integer sums: two runs give the same bits. */
+typedef struct DgAdaState {
+  float p;
+  long long sign_sum, count; /* the window since the last adjustment */
+  int steps;                 /* iterations seen */
+} DgAdaState;
+int dg_ada_update(const float* y_real, int B, void* state, long long* pend, int advance, float target, int interval,
+                  int batch_size, float kimg, float rt_scale, float* rt_slot, float* p_slot, void* stream);
 /* Adam with the (0-based, already-completed) step count in device memory: this call is step *step_dev + 1 */
 int dg_adam_ema_step_dev(float* p, const float* grad, float* m, float* v, float* ema, void* shadow, int shadow_dtype,
                          long n, float gscale, float lr, float beta1, float beta2, float eps,
