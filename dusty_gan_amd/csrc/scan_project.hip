@@ -19,22 +19,13 @@
 //     fixed point, common.h) and the valid count: integer sums, so the grid depends neither on the chunk size nor on scheduling.
 // All HBM-bound: 16 bytes per point in, 8 bytes of key + 16 bytes out per cell.
 #include "common.h"
+#include "scan_cell.h"   // the column, the z-buffer key, key fill and gather: shared with beam_project.hip
 
 namespace {
 
 #define SCAN_THREADS 1024
 #define SCAN_SPLIT 8      // workgroups per scan
 #define PROJ_H 64         // the reference hard-codes line_idx = 63
-#define KEY_EMPTY 0xFFFFFFFFFFFFFFFFull
-
-inline int nblk(long n) { return (int)((n + 255) / 256); }
-
-__global__ __launch_bounds__(256) void key_fill_kernel(unsigned long long* __restrict__ keys, long n, int* __restrict__ status,
-                                                       int S) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) keys[i] = KEY_EMPTY;
-  if (i < S) status[i] = 0;
-}
 
 // quadrant as process_kitti.py:90-94 (a NaN coordinate matches no line there: 0)
 __device__ __forceinline__ int quadrant(float x, float y) {
@@ -116,36 +107,16 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_scatter_kernel(const float*
     } else {
       if (row < 0) row += PROJ_H;
       const float4 v = p[i];
-      const float yaw = -atan2f(v.y, v.x);
-      float g = (yaw / 3.14159274101257324f + 1.f) / 2.f;   // np.pi as float32
-      g = fmodf(g, 1.f);                                    // np.remainder(g, 1): g >= 0, so the C remainder is numpy's
-      if (g < 0.f) g += 1.f;
-      const float colf = floorf(g * (float)W);
+      const float colf = sc_column(v.x, v.y, W);
       const float depth = sqrtf((v.x * v.x + v.y * v.y) + v.z * v.z);   // np.linalg.norm(xyz, ord=2, axis=1) in float32
       // (a non-finite coordinate has no column, and the reference's scatter would index out of range: the point is dropped)
       if (colf >= 0.f && colf < (float)W && depth >= 0.f) {
         cell = row * W + (int)colf;
-        atomicMin(&kimg[cell], ((unsigned long long)__float_as_uint(depth) << 32) | (unsigned)i);
+        atomicMin(&kimg[cell], sc_key(depth, (unsigned)i));
       }
     }
     if (cell_out) cell_out[o0 + i] = cell;
   }
-}
-
-__global__ __launch_bounds__(256) void scan_gather_kernel(const float* __restrict__ points, const long* __restrict__ offsets,
-                                                          const unsigned long long* __restrict__ keys,
-                                                          const int* __restrict__ status, long cells_per_scan, long n,
-                                                          float* __restrict__ out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int s = (int)(i / cells_per_scan);
-  const unsigned long long k = keys[i];
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (k != KEY_EMPTY && status[s] == 0) {
-    const long o0 = offsets[s], idx = (long)(unsigned)(k & 0xFFFFFFFFull);
-    if (idx < offsets[s + 1] - o0) v = reinterpret_cast<const float4*>(points)[o0 + idx];
-  }
-  reinterpret_cast<float4*>(out)[i] = v;
 }
 
 // compute_avg_angles' loop body (process_kitti.py:150-166) on KITTIOdometry.preprocess's unit-space xyz (datasets/kitti.py:54-67,
@@ -259,9 +230,9 @@ int dg_scan_project(const float* points, const long* offsets, int S, int H, int 
   if ((long)H * W > 0x7FFFFFFFl) return DG_EINVAL;
   hipStream_t st = (hipStream_t)s_;
   const long cells = (long)H * W, n = (long)S * cells;
-  key_fill_kernel<<<nblk(n), 256, 0, st>>>(keys, n, status, S);
+  key_fill_kernel<<<sc_nblk(n), 256, 0, st>>>(keys, n, status, S);
   scan_scatter_kernel<<<dim3(S, SCAN_SPLIT), SCAN_THREADS, 0, st>>>(points, offsets, W, keys, status, cell);
-  scan_gather_kernel<<<nblk(n), 256, 0, st>>>(points, offsets, keys, status, cells, n, out);
+  scan_gather_kernel<<<sc_nblk(n), 256, 0, st>>>(points, offsets, keys, status, cells, n, out);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }
@@ -270,7 +241,7 @@ int dg_angle_accum(const float* scans, int S, int H, int W, int C, double min_de
                    int* count, void* s_) {
   if (!scans || !sums || !count || S <= 0 || H <= 0 || W <= 0 || C < 3 || !(max_depth > min_depth)) return DG_EINVAL;
   const long hw = (long)H * W;
-  angle_accum_kernel<<<nblk(hw), 256, 0, (hipStream_t)s_>>>(scans, S, hw, C, (float)min_depth, (float)max_depth, sums, count);
+  angle_accum_kernel<<<sc_nblk(hw), 256, 0, (hipStream_t)s_>>>(scans, S, hw, C, (float)min_depth, (float)max_depth, sums, count);
   HIP_CHECK_RET(hipGetLastError());
   return DG_OK;
 }

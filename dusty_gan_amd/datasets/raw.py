@@ -5,6 +5,10 @@ Reference: process_kitti.py:76-118 (process_point_clouds: one `.bin` -> one 64 x
 (compute_avg_angles -> angles.pt).  There, joblib workers argsort and scatter every scan in Python; here the host threads
 only move bytes - ScanLoader's pipeline in reverse - and the arithmetic is three launches per chunk of scans
 (`dg_scan_project`, csrc/scan_project.hip) plus one per chunk for the angle sums (`dg_angle_accum`).
+
+The second half of the file does the same for clouds of ANY spinning sensor, whose records come in no order:
+`cloud_chunks` reads `.bin` / `.npy` clouds into pinned slots, `project_clouds_beams` / `project_files_beams` give every
+point the row of its nearest beam (`dg_beam_project`, csrc/beam_project.hip; the table comes from datasets/beams.py).
 """
 import os
 import os.path as osp
@@ -400,4 +404,185 @@ def project_files(pairs, W=2048, chunk=16, num_workers=4, device=None, progress=
         pool.shutdown(wait=True)
     if bad:
         raise RawScanError(bad)
+    return written
+
+
+# ------------------------------------------------------------------------------------------------ any sensor: clouds -> .npy
+def _read_cloud_into(path, dst, cols):
+    """one cloud file (see _cloud_rows) into its [n,4] slice of a pinned slot, metres as stored; column 3 of an N x 3 file is 0"""
+    if not path.endswith(".npy"):
+        _read_bin_into(path, dst)
+    elif cols == 4:
+        _read_npy_into(path, dst)
+    else:
+        xyz = np.empty((dst.shape[0], 3), dtype=np.float32)
+        _read_npy_into(path, xyz)
+        dst[:, :3] = xyz
+        dst[:, 3] = 0.0
+
+
+class _CloudSlot:
+    """one chunk of clouds on its way to the device: pinned records / offsets and their device twins"""
+
+    def __init__(self, chunk, device):
+        self.device, self.cap = device, 0
+        self.pts_pin = self.pts_host = self.pts_dev = None
+        self.off_pin = torch.empty(chunk + 1, dtype=torch.int64).pin_memory()
+        self.off_dev = torch.empty(chunk + 1, dtype=torch.int64, device=device)
+        self.copied = torch.cuda.Event()   # H2D of this slot finished -> the pinned buffers may be refilled
+        self.futs, self.batch, self.npts = [], [], 0
+
+    def reserve(self, n_points):
+        if n_points > self.cap or self.pts_dev is None:   # (the first chunk allocates even when it holds no point)
+            self.cap = int(n_points * 1.25) + 1024
+            self.pts_pin = torch.empty(self.cap, 4, dtype=torch.float32).pin_memory()
+            self.pts_host = self.pts_pin.numpy()
+            self.pts_dev = torch.empty(self.cap, 4, dtype=torch.float32, device=self.device)
+
+
+def cloud_chunks(items, chunk=16, num_workers=4, device=None, path_of=None):
+    """generator over `items` (cloud files: `.bin` N x 4 or `.npy` N x 3 / N x 4, or anything path_of maps to one), `chunk`
+    at a time: yields (points [N,4] fp32, offsets [S+1] int64, the items of the chunk) - device tensors as dg_scan_project
+    takes them, valid until the generator is advanced.  Host threads read the next chunk into a pinned slot while the caller
+    works on this one; the H2D copies ride the caller's stream.  A file read_clouds would refuse raises RawScanError."""
+    items = list(items)
+    path_of = os.fspath if path_of is None else path_of
+    chunk, dev = max(1, int(chunk)), _device(device)
+    batches = [items[i:i + chunk] for i in range(0, len(items), chunk)]
+    slots = [_CloudSlot(chunk, dev) for _ in range(min(2, len(batches)))]
+    pool = ThreadPoolExecutor(max(1, int(num_workers)))
+
+    def start(s, batch):
+        s.copied.synchronize()   # (no-op for a never-recorded event)
+        paths = [path_of(it) for it in batch]
+        shapes = [_cloud_rows(p) for p in paths]
+        o = np.concatenate([[0], np.cumsum([n for n, _ in shapes])]).astype(np.int64)
+        s.reserve(int(o[-1]))
+        s.off_pin[:len(o)] = torch.from_numpy(o)
+        s.batch, s.npts = batch, int(o[-1])
+        s.futs = [pool.submit(_read_cloud_into, p, s.pts_host[o[j]:o[j + 1]], cols)
+                  for j, (p, (_, cols)) in enumerate(zip(paths, shapes))]
+
+    try:
+        if batches:
+            start(slots[0], batches[0])
+        for k in range(len(batches)):
+            s = slots[k % 2]
+            if k + 1 < len(batches):
+                start(slots[(k + 1) % 2], batches[k + 1])
+            for f in s.futs:
+                f.result()
+            n = len(s.batch)
+            s.pts_dev[:s.npts].copy_(s.pts_pin[:s.npts], non_blocking=True)
+            s.off_dev[:n + 1].copy_(s.off_pin[:n + 1], non_blocking=True)
+            s.copied.record(torch.cuda.current_stream(dev))
+            yield s.pts_dev[:s.npts], s.off_dev[:n + 1], s.batch
+    finally:
+        pool.shutdown(wait=True)
+
+
+def _beam_table(beams):
+    """the table as dg_beam_project reads it: float64 on the host, radians, strictly descending"""
+    b = np.ascontiguousarray(np.asarray(beams, dtype=np.float64).reshape(-1))
+    if b.size < 1 or not np.all(np.isfinite(b)) or np.any(np.diff(b) >= 0):
+        raise ValueError(f"the beam table must hold strictly descending elevations (radians); got {b.tolist()[:8]}...")
+    return b
+
+
+def _launch_beam_project(points, offsets, S, table, W, keys, cells, out):
+    L.check(L.lib().dg_beam_project(L.ptr(points), L.ptr(offsets), S, table.ctypes.data, table.size, W, L.ptr(keys),
+                                    L.ptr(cells), L.ptr(out), L.stream_ptr()), "dg_beam_project")
+
+
+def project_clouds_beams(points, offsets, beams, W=2048, return_cells=False, device=None):
+    """project_scans for clouds whose records come in ANY order, from a sensor with the beam table `beams` ([H] elevations in
+    radians, strictly descending: estimate_beams' result).  -> device tensor [S,H,W,4]: a point's row is its nearest beam
+    (in double; a tie goes to the lower row), its column project_scans' own; every cell holds its nearest point (float32
+    range; on a tie the lower point index), zeros where none fell.  A point with a non-finite coordinate takes no part, nor
+    does the origin.  return_cells: also every point's row * W + column [N] int32, -1 where it took no part."""
+    points = torch.as_tensor(points)
+    if not points.is_cuda:
+        if not torch.cuda.is_available():
+            raise RuntimeError("project_clouds_beams runs on the GPU only (no CPU fallback)")
+        points = points.to(_device(device))
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 4, (points.dtype, points.shape)
+    points = points.contiguous()
+    o = _check_offsets(offsets, points.shape[0])
+    table = _beam_table(beams)
+    S, H, W, dev = o.size - 1, table.size, int(W), points.device
+    with torch.cuda.device(dev):
+        offs = torch.from_numpy(o).to(dev)
+        keys = torch.empty(S * H * W, dtype=torch.int64, device=dev)
+        cells = torch.empty(max(points.shape[0], 1), dtype=torch.int32, device=dev) if return_cells else None
+        out = torch.empty(S, H, W, 4, dtype=torch.float32, device=dev)
+        if points.shape[0] == 0:   # nothing to scatter (and no pointer to hand over)
+            out.zero_()
+            return (out, cells[:0]) if return_cells else out
+        _launch_beam_project(points, offs, S, table, W, keys, cells, out)
+    return (out, cells[:points.shape[0]]) if return_cells else out
+
+
+def project_files_beams(pairs, beams, W=2048, chunk=16, num_workers=4, device=None, progress=None, on_chunk=None):
+    """project_files for any sensor: [(cloud file, destination `.npy`)] -> the files, (H, W, 4) float32 each, `chunk` clouds
+    per dg_beam_project.  Host threads read the clouds (cloud_chunks) and write the `.npy` files; on_chunk(pairs of the
+    chunk, their projections [S,H,W,4] on the device) runs before the projections leave the device (the angle grid's
+    sums).  Returns the number of files written."""
+    pairs = [(os.fspath(a), os.fspath(b)) for a, b in pairs]
+    if not pairs:
+        return 0
+    table = _beam_table(beams)
+    chunk, H, W, dev = max(1, int(chunk)), table.size, int(W), _device(device)
+    pool = ThreadPoolExecutor(max(1, int(num_workers)))
+    copy_stream = torch.cuda.Stream(dev)
+    keys = torch.empty(chunk * H * W, dtype=torch.int64, device=dev)
+    outs = [{"dev": torch.empty(chunk, H, W, 4, dtype=torch.float32, device=dev),
+             "pin": torch.empty(chunk, H, W, 4, dtype=torch.float32).pin_memory(), "done": torch.cuda.Event(),
+             "read": None, "wfuts": [], "batch": []} for _ in range(2)]
+    made_dirs, written = set(), 0
+
+    def start_write(o):
+        nonlocal written
+        o["done"].synchronize()
+        host = o["pin"].numpy()
+        for j, (_, dst) in enumerate(o["batch"]):
+            d = osp.dirname(dst)
+            if d not in made_dirs:
+                os.makedirs(d, exist_ok=True)
+                made_dirs.add(d)
+            o["wfuts"].append(pool.submit(write_npy, dst, host[j]))
+            written += 1
+        if progress is not None:
+            progress(len(o["batch"]))
+
+    try:
+        prev = None
+        with torch.cuda.device(dev):
+            for k, (pts, offs, batch) in enumerate(cloud_chunks(pairs, chunk, num_workers, dev, path_of=lambda p: p[0])):
+                o, n = outs[k % 2], len(batch)
+                for f in o["wfuts"]:   # the slot's previous files are on disk (re-raises a writer's error)
+                    f.result()
+                o["wfuts"], o["batch"] = [], batch
+                cur = torch.cuda.current_stream(dev)
+                if o["read"] is not None:
+                    cur.wait_event(o["read"])   # the slot's previous D2H copy has read `dev`
+                _launch_beam_project(pts, offs, n, table, W, keys, None, o["dev"])
+                if on_chunk is not None:
+                    on_chunk(batch, o["dev"][:n])
+                ran = torch.cuda.Event()
+                ran.record(cur)
+                with torch.cuda.stream(copy_stream):
+                    copy_stream.wait_event(ran)
+                    o["pin"][:n].copy_(o["dev"][:n], non_blocking=True)
+                    o["done"].record(copy_stream)
+                o["read"] = o["done"]
+                if prev is not None:
+                    start_write(prev)
+                prev = o
+            if prev is not None:
+                start_write(prev)
+        for o in outs:
+            for f in o["wfuts"]:
+                f.result()
+    finally:
+        pool.shutdown(wait=True)
     return written

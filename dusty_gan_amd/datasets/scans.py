@@ -127,6 +127,27 @@ class SparseMPO(ScanDataset):
         self.datalist = datalist
 
 
+class ScanFolder(ScanDataset):
+    """projected scans of ANY sensor, as `python -m dusty_gan_amd.process_clouds` writes them: the split table comes from the
+    config (`dataset.split`: recording directory names per phase; a phase it does not name is empty) and the file list is
+    root/sequences/<name>/velodyne/*.npy, sorted, in the table's order.  A name is taken as written: quote one that YAML
+    would read as a number ("08")."""
+
+    def __init__(self, root, split, config=None, **kwargs):
+        table = dict((config or {}).get("split") or {})
+        table.setdefault(split, [])
+        super().__init__(root, split, config={"split": {k: [str(n) for n in (v or [])] for k, v in table.items()}}, **kwargs)
+
+    def _root(self, root):
+        return osp.join(root, "sequences")
+
+    def load_datalist(self):
+        datalist = []
+        for name in self.subsets:
+            datalist += sorted(glob(osp.join(self.root, str(name), "velodyne", "*.npy")))
+        self.datalist = datalist
+
+
 def sampler_indices(n, world, rank, seed=0, epoch=0, shuffle=True):
     """DistributedSampler(dataset) as built at trainers/dcgan_amp.py:88: shuffle with seed 0, pad to a multiple of the
     world size by repeating the head, take rank::world.  The reference never calls set_epoch, so every epoch replays

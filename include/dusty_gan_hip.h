@@ -475,6 +475,33 @@ int dg_angle_accum(const float* scans, int S, int H, int W, int C, double min_de
                    int* count, void* stream);
 int dg_angle_finish(const long long* sums, const int* count, int H, int W, float* angles, void* stream);
 
+/* ---- unordered clouds of any spinning LiDAR -> the dataset's files (dusty_gan_amd/datasets/beams.py;
+ * csrc/beam_project.hip).  The reference holds no code for it.  points / offsets as dg_scan_project takes
+ * them (both on the device).  Per point, in DOUBLE on the float32 coordinates (csrc/points_body.h): the elevation
+ * u = atan2(z, sqrt(x^2 + y^2)) and the range d = |xyz| in metres.  A point with a non-finite coordinate takes no part in
+ * either call, nor does the origin.  Neither call uses float atomics.
+ * dg_elev_hist: for every point with min_depth < d < max_depth (both strict) and lo <= u < hi,
+ *   hist[min(floor((u - lo) * (NB / (hi - lo))), NB - 1)] += 1.  hist [NB] u64 is zeroed by the CALLER and ADDED to, so a
+ *   dataset goes through in chunks; integer counts, so the result depends neither on the chunking nor on scheduling.  One
+ *   launch: a workgroup counts into NB u32 words of LDS and adds its non-zero bins with one global integer atomic each.
+ *   DG_EINVAL: a NULL pointer, S < 1, lo >= hi (or either not finite), NB outside 64..16384.
+ * dg_beam_project: out [S,H,W,4] fp32.  beams: H doubles ON THE HOST (read before the call returns), radians, strictly
+ *   descending - row 0 is the highest beam, as in the KITTI files.
+ *     row     the beam nearest to u in double; on an exact tie the LOWER row
+ *     column  dg_scan_project's float32 expression floor(((-atan2f(y, x) / pi + 1) / 2 mod 1) * W) (csrc/scan_cell.h)
+ *     cell    keeps its NEAREST point: 64-bit atomicMin of (bits of (float)d << 32 | point index within the scan), so of two
+ *             points with the same float32 range the LOWER index wins - dg_scan_project's key and tie rule
+ *   The winner's four floats are copied bit for bit; a cell without a point is zero.  cell [N] int32 (nullable): every
+ *   point's row * W + column, -1 for a point that took no part - also a finite point whose float32 column coordinate
+ *   rounds up to W itself (an azimuth a hair above -pi), which has no column here as in dg_scan_project.  keys [S*H*W]
+ *   u64: caller-owned workspace, no initial contents required.  Three launches (key fill, scatter, gather).  Bit-identical from run to run, whatever S is, and for
+ *   any permutation of a scan's points up to the tie rule.  DG_EINVAL: a NULL pointer but cell, S < 1, H outside 1..256,
+ *   W outside 1..8192, a table that is not strictly descending or holds an entry outside [-4, 4]. */
+int dg_elev_hist(const float* points, const long* offsets, int S, double min_depth, double max_depth, double lo, double hi,
+                 int NB, unsigned long long* hist, void* stream);
+int dg_beam_project(const float* points, const long* offsets, int S, const double* beams, int H, int W,
+                    unsigned long long* keys, int* cell, float* out, void* stream);
+
 /* ---- the picture log of a training run (utils/render.py:18-127, train.py:28-34; csrc/render.hip) ---------------
  * acc: caller-owned u64 words [B,H,W,C] (24.40 fixed point, dg_fix40 of csrc/common.h), ZERO AT REST: all zeros before the
  * first accumulate, zeroed again by dg_splat_finish.  Integer atomics: the image is bit-identical whatever the order of the
