@@ -30,7 +30,7 @@ class DgError(RuntimeError):
 # to a struct of the header: POINTER(that struct)
 _SCALARS = {"int": C.c_int, "long": C.c_long, "long long": C.c_longlong, "unsigned": C.c_uint,
             "unsigned long long": C.c_ulonglong, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "float": C.c_float,
-            "double": C.c_double, "unsigned char": C.c_ubyte}
+            "double": C.c_double, "unsigned char": C.c_ubyte, "unsigned short": C.c_ushort}
 _C_WORDS = frozenset("const void char short int long unsigned signed float double struct enum".split())
 
 

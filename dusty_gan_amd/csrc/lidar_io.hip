@@ -10,18 +10,11 @@
 // Both are HBM-bound: one 16-byte cell read per output pixel / one image-sized stream in, three out.
 #include "common.h"
 #include "inv_point.h"
+#include "nearest.h"   // nearest_src: shared with dg_label_resize (object_removal.hip)
 
 namespace {
 
 inline int nblk(long n) { return (int)((n + 255) / 256); }
-
-// torch's legacy "nearest" (what torchvision 0.9 TF.resize(tensor, size, NEAREST) calls: F.interpolate(mode="nearest")):
-// src = min(floor(dst * float(in) / out), in - 1)
-__device__ __forceinline__ int nearest_src(int dst, int in_size, int out_size) {
-  const float scale = (float)in_size / (float)out_size;
-  const int s = (int)floorf((float)dst * scale);
-  return s < in_size - 1 ? s : in_size - 1;
-}
 
 __global__ __launch_bounds__(256) void scan_to_polar_kernel(
     const float* __restrict__ scan, int B, int Hs, int Ws, int C, int H, int W, const unsigned char* __restrict__ flip,

@@ -47,11 +47,19 @@ def _launch_project(points, offsets, S, W, keys, status, cells, out):
                                     L.ptr(cells), L.ptr(out), L.stream_ptr()), "dg_scan_project")
 
 
-def project_scans(points, offsets, W=2048, return_cells=False, names=None, device=None):
+def _results(out, cells, keys):
+    """out alone, or the tuple (out[, cells][, keys])"""
+    extra = tuple(t for t in (cells, keys) if t is not None)
+    return (out,) + extra if extra else out
+
+
+def project_scans(points, offsets, W=2048, return_cells=False, names=None, device=None, return_keys=False):
     """process_point_clouds (process_kitti.py:76-118) for a batch of raw scans, on the GPU.
     points [N,4] fp32 (tensor or array: the scans' records back to back), offsets [S+1] ints on the host (scan s =
     points[offsets[s]:offsets[s+1]]) -> device tensor [S,64,W,4]: every cell holds its nearest point (float32 depth; on a
     tie the lower point index), zeros where none fell.  return_cells: also every point's row * W + column [N] int32.
+    return_keys: also (last) the z-buffer words [S*64*W] int64 as the call left them - every cell's (range bits << 32 | the
+    winner's index within its scan) or -1 for an empty cell: what datasets.labels.project_labels reads.
     Raises RawScanError (naming names[s], or the index s) for a scan with a ring row below -64."""
     points = torch.as_tensor(points)
     if not points.is_cuda:
@@ -70,12 +78,12 @@ def project_scans(points, offsets, W=2048, return_cells=False, names=None, devic
         out = torch.empty(S, H_RINGS, W, 4, dtype=torch.float32, device=dev)
         if points.shape[0] == 0:   # nothing to scatter (and no pointer to hand over)
             out.zero_()
-            return (out, cells[:0]) if return_cells else out
+            return _results(out, cells[:0] if return_cells else None, keys.fill_(-1) if return_keys else None)
         _launch_project(points, offs, S, W, keys, status, cells, out)
         bad = torch.nonzero(status).flatten().tolist()
     if bad:
         raise RawScanError([names[s] if names is not None else f"scan {s}" for s in bad])
-    return (out, cells[:points.shape[0]]) if return_cells else out
+    return _results(out, cells[:points.shape[0]] if return_cells else None, keys if return_keys else None)
 
 
 # ------------------------------------------------------------------------------------------------ angle grid
@@ -293,6 +301,10 @@ class _ProjSlot:
         self.out_host = self.out_pin.numpy()
         self.done = torch.cuda.Event()
         self.rfuts, self.wfuts, self.pairs, self.n = [], [], [], 0
+        # the label images (project_files(label_pairs=...)): allocated with the first chunk that carries labels
+        self.lab_cap, self.lab_pin, self.lab_host, self.lab_dev = 0, None, None, None
+        self.sem_dev = self.sem_pin = self.sem_host = self.lst_dev = self.lst_pin = None
+        self.label_pairs, self.has_labels = [], False
 
     def reserve(self, n_points):
         if n_points > self.cap:
@@ -301,24 +313,55 @@ class _ProjSlot:
             self.pts_host = self.pts_pin.numpy()
             self.pts_dev = torch.empty(self.cap, 4, dtype=torch.float32, device=self.device)
 
+    def reserve_labels(self, n_points):
+        if self.sem_dev is None:
+            self.sem_dev = torch.empty(self.chunk, H_RINGS, self.W, dtype=torch.uint8, device=self.device)
+            self.sem_pin = torch.empty(self.chunk, H_RINGS, self.W, dtype=torch.uint8).pin_memory()
+            self.sem_host = self.sem_pin.numpy()
+            self.lst_dev = torch.empty(self.chunk, dtype=torch.int32, device=self.device)
+            self.lst_pin = torch.empty(self.chunk, dtype=torch.int32).pin_memory()
+        if n_points > self.lab_cap:
+            self.lab_cap = int(n_points * 1.25) + 1024
+            self.lab_pin = torch.empty(self.lab_cap, dtype=torch.int32).pin_memory()
+            self.lab_host = self.lab_pin.numpy()
+            self.lab_dev = torch.empty(self.lab_cap, dtype=torch.int32, device=self.device)
 
-def project_files(pairs, W=2048, chunk=16, num_workers=4, device=None, progress=None):
+
+def project_files(pairs, W=2048, chunk=16, num_workers=4, device=None, progress=None, label_pairs=None):
     """[(raw `.bin`, destination `.npy`)] -> the files, `chunk` scans per launch.  ScanLoader's pipeline in reverse: host
     threads read the `.bin` records into a pinned slot, one H2D copy per chunk on a side stream, dg_scan_project, one D2H copy
     into a pinned slot, host threads write v1.0 / C-order / float32 `.npy` files of shape (64, W, 4).  A scan the reference
-    would have raised on (RawScanError) is not written; the rest of its chunk is.  Returns the number of files written."""
-    pairs = [(os.fspath(a), os.fspath(b)) for a, b in pairs]
+    would have raised on (RawScanError) is not written; the rest of its chunk is.  Returns the number of files written.
+    A destination of None is not written (its label image may still be).
+    label_pairs: one entry per pair, None or (SemanticKITTI `.label` of the scan, destination `.png`): the scan's label image
+    (datasets.labels; process_kitti.py:120-131) out of the same chunk and the same z-buffer words as its `.npy`, the label
+    reads and PNG writes on the same host threads.  A label file of another length than its scan, or an id outside the
+    table among the winners, raises RawScanError after the rest is written.  The PNGs are not counted in the result."""
+    pairs = [(os.fspath(a), None if b is None else os.fspath(b)) for a, b in pairs]
     if not pairs:
         return 0
+    if label_pairs is None:
+        label_pairs = [None] * len(pairs)
+    label_pairs = [None if lp is None else (os.fspath(lp[0]), os.fspath(lp[1])) for lp in label_pairs]
+    if len(label_pairs) != len(pairs):
+        raise ValueError(f"{len(label_pairs)} label pairs for {len(pairs)} scans")
+    if any(lp is not None for lp in label_pairs):
+        from . import labels as LB
     chunk, W, dev = max(1, int(chunk)), int(W), _device(device)
     pool = ThreadPoolExecutor(max(1, int(num_workers)))
     copy_stream = torch.cuda.Stream(dev)
-    batches = [pairs[i:i + chunk] for i in range(0, len(pairs), chunk)]
+    batches = [(pairs[i:i + chunk], label_pairs[i:i + chunk]) for i in range(0, len(pairs), chunk)]
     free = deque(_ProjSlot(chunk, W, dev) for _ in range(min(3, len(batches))))
     reading, on_gpu, slots = deque(), deque(), list(free)
-    made_dirs, written, bad = set(), 0, []
+    made_dirs, written, bad, bad_labels = set(), 0, [], []
 
-    def start_read(s, batch):
+    def read_labels_into(path, dst):
+        if osp.getsize(path) != dst.nbytes:
+            raise RawScanError([path], f"not one uint32 label for each of the scan's {dst.size} points")
+        _read_bin_into(path, dst)
+
+    def start_read(s, batch_and_labels):
+        batch, lpairs = batch_and_labels
         for f in s.wfuts:   # the slot's previous files are on disk (re-raises a writer's error)
             f.result()
         s.wfuts = []
@@ -332,6 +375,14 @@ def project_files(pairs, W=2048, chunk=16, num_workers=4, device=None, progress=
         s.pairs, s.n, s.npts = batch, len(batch), int(o[-1])
         s.rfuts = [pool.submit(_read_bin_into, src, s.pts_host[o[j]:o[j + 1]]) for j, (src, _) in enumerate(batch)
                    if o[j + 1] > o[j]]
+        s.label_pairs, s.has_labels = lpairs, any(lp is not None for lp in lpairs)
+        if s.has_labels:
+            s.reserve_labels(int(o[-1]))
+            for j, lp in enumerate(lpairs):
+                if lp is None:
+                    s.lab_host[o[j]:o[j + 1]] = 0   # ("unlabeled": in the table; the image is not written)
+                elif o[j + 1] > o[j] or osp.getsize(lp[0]):
+                    s.rfuts.append(pool.submit(read_labels_into, lp[0], s.lab_host[o[j]:o[j + 1]]))
 
     def launch(s):
         for f in s.rfuts:
@@ -341,38 +392,60 @@ def project_files(pairs, W=2048, chunk=16, num_workers=4, device=None, progress=
         if s.npts == 0:
             s.out_pin[:n].zero_()
             s.st_pin[:n].zero_()
+            if s.has_labels:
+                s.sem_pin[:n].zero_()
+                s.lst_pin[:n].zero_()
             s.done.record(cur)
             return
         with torch.cuda.stream(copy_stream):
             s.pts_dev[:s.npts].copy_(s.pts_pin[:s.npts], non_blocking=True)
             s.off_dev[:n + 1].copy_(s.off_pin[:n + 1], non_blocking=True)
+            if s.has_labels:
+                s.lab_dev[:s.npts].copy_(s.lab_pin[:s.npts], non_blocking=True)
             up = torch.cuda.Event()
             up.record(copy_stream)
         cur.wait_event(up)
         with torch.cuda.device(dev):
             _launch_project(s.pts_dev, s.off_dev, n, W, s.keys, s.st_dev, None, s.out_dev)
+            if s.has_labels:   # the same chunk, the same keys
+                LB.launch_scan_labels(s.keys, s.off_dev, s.lab_dev, LB.device_lut(dev), n, H_RINGS, W, s.sem_dev, None, s.lst_dev[:n])
         ran = torch.cuda.Event()
         ran.record(cur)
         with torch.cuda.stream(copy_stream):
             copy_stream.wait_event(ran)
             s.out_pin[:n].copy_(s.out_dev[:n], non_blocking=True)
             s.st_pin[:n].copy_(s.st_dev[:n], non_blocking=True)
+            if s.has_labels:
+                s.sem_pin[:n].copy_(s.sem_dev[:n], non_blocking=True)
+                s.lst_pin[:n].copy_(s.lst_dev[:n], non_blocking=True)
             s.done.record(copy_stream)
+
+    def submit_write(s, fn, path, arr):
+        d = osp.dirname(path)
+        if d not in made_dirs:
+            os.makedirs(d, exist_ok=True)
+            made_dirs.add(d)
+        s.wfuts.append(pool.submit(fn, path, arr))
 
     def start_write(s):
         nonlocal written
         s.done.synchronize()
         status = s.st_pin[:s.n].tolist()
+        lstatus = s.lst_pin[:s.n].tolist() if s.has_labels else [0] * s.n
         for j, (src, dst) in enumerate(s.pairs):
             if status[j]:
                 bad.append(src)
                 continue
-            d = osp.dirname(dst)
-            if d not in made_dirs:
-                os.makedirs(d, exist_ok=True)
-                made_dirs.add(d)
-            s.wfuts.append(pool.submit(write_npy, dst, s.out_host[j]))
-            written += 1
+            lp = s.label_pairs[j]
+            if lp is not None and lstatus[j]:
+                ids = LB.read_label_file(lp[0]) & 0xFFFF
+                bad_labels.append(f"{lp[0]} (ids {sorted(int(i) for i in np.unique(ids[LB.SEMANTIC_KITTI_LUT[ids] == LB.UNKNOWN]))})")
+                lp = None
+            if dst is not None:
+                submit_write(s, write_npy, dst, s.out_host[j])
+                written += 1
+            if lp is not None:
+                submit_write(s, LB.write_label_png, lp[1], s.sem_host[j])
         if progress is not None:
             progress(s.n)
 
@@ -404,6 +477,8 @@ def project_files(pairs, W=2048, chunk=16, num_workers=4, device=None, progress=
         pool.shutdown(wait=True)
     if bad:
         raise RawScanError(bad)
+    if bad_labels:
+        raise RawScanError(bad_labels, "a label id outside the SemanticKITTI table")
     return written
 
 
@@ -494,12 +569,13 @@ def _launch_beam_project(points, offsets, S, table, W, keys, cells, out):
                                     L.ptr(cells), L.ptr(out), L.stream_ptr()), "dg_beam_project")
 
 
-def project_clouds_beams(points, offsets, beams, W=2048, return_cells=False, device=None):
+def project_clouds_beams(points, offsets, beams, W=2048, return_cells=False, device=None, return_keys=False):
     """project_scans for clouds whose records come in ANY order, from a sensor with the beam table `beams` ([H] elevations in
     radians, strictly descending: estimate_beams' result).  -> device tensor [S,H,W,4]: a point's row is its nearest beam
     (in double; a tie goes to the lower row), its column project_scans' own; every cell holds its nearest point (float32
     range; on a tie the lower point index), zeros where none fell.  A point with a non-finite coordinate takes no part, nor
-    does the origin.  return_cells: also every point's row * W + column [N] int32, -1 where it took no part."""
+    does the origin.  return_cells: also every point's row * W + column [N] int32, -1 where it took no part.  return_keys:
+    also (last) the z-buffer words [S*H*W] int64 as the call left them, as project_scans returns them."""
     points = torch.as_tensor(points)
     if not points.is_cuda:
         if not torch.cuda.is_available():
@@ -517,9 +593,9 @@ def project_clouds_beams(points, offsets, beams, W=2048, return_cells=False, dev
         out = torch.empty(S, H, W, 4, dtype=torch.float32, device=dev)
         if points.shape[0] == 0:   # nothing to scatter (and no pointer to hand over)
             out.zero_()
-            return (out, cells[:0]) if return_cells else out
+            return _results(out, cells[:0] if return_cells else None, keys.fill_(-1) if return_keys else None)
         _launch_beam_project(points, offs, S, table, W, keys, cells, out)
-    return (out, cells[:points.shape[0]]) if return_cells else out
+    return _results(out, cells[:points.shape[0]] if return_cells else None, keys if return_keys else None)
 
 
 def project_files_beams(pairs, beams, W=2048, chunk=16, num_workers=4, device=None, progress=None, on_chunk=None):

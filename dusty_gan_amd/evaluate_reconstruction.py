@@ -110,13 +110,23 @@ def flatten(t):
     return t.flatten(2).permute(0, 2, 1).contiguous()
 
 
+def invert_target(G, lidar, tgt_ref, tgt_mask, args, **keyed):
+    """inversion.invert against (tgt_ref, tgt_mask) under a command's inversion flags (add_inversion_arguments): the one call
+    evaluate_batch and remove_objects share; keyed: further arguments of invert (remove_objects keys the draws by first_index)"""
+    from .inversion import invert
+    names = split_distance(args.distance)
+    multi = dict(num_code=args.num_code, composition_layer=args.composition_layer) if args.num_code > 1 else {}
+    return invert(G, tgt_ref, tgt_mask, num_step=args.num_step, distance=names[0] if len(names) == 1 else names,
+                  lidar=lidar if ("chamfer" in names or "emd" in names) else None,
+                  **({"emd_points": args.emd_points} if "emd" in names else {}), **multi, **keyed)
+
+
 def evaluate_batch(G, lidar, arch, item, args, first_index=0, outputs=None):
     """one batch of the reference's loop body (:80-152) -> {column: list}.  With args.corruption the latent is optimised
     against the corrupted (depth, mask) - the Chamfer term's reference points included - and every column is scored against
     the full scan (demo.py:385-397); first_index: the dataset index of the batch's first scan (keys the corruption's draws);
     outputs: a dict that receives the postprocessed generator outputs ("depth", "points", "normals", ...), the optimised
     inverse depth "inv_gen" and the inversion's target "target_inv" / "target_mask" (dusty_gan_amd.reconstruct)"""
-    from .inversion import invert
     from .utils.lidar import postprocess
     from .utils.metrics.depth import depth_metrics
     from .utils.metrics.distance import compute_cd
@@ -130,11 +140,7 @@ def evaluate_batch(G, lidar, arch, item, args, first_index=0, outputs=None):
         dep_c, tgt_mask = apply_corruption(depth, mask, corruption, seed=getattr(args, "corruption_seed", 0), first_index=first_index)
         inv_c = lidar.invert_depth(dep_c)
         tgt_ref = tgt_mask * inv_c + (1 - tgt_mask) * 0.0   # demo.py:396-397
-    names = split_distance(args.distance)
-    multi = dict(num_code=args.num_code, composition_layer=args.composition_layer) if args.num_code > 1 else {}
-    res = invert(G, tgt_ref, tgt_mask, num_step=args.num_step, distance=names[0] if len(names) == 1 else names,
-                 lidar=lidar if ("chamfer" in names or "emd" in names) else None,
-                 **({"emd_points": args.emd_points} if "emd" in names else {}), **multi)
+    res = invert_target(G, lidar, tgt_ref, tgt_mask, args)
     out = postprocess(res["out"], lidar, tol=args.tol)
     if outputs is not None:
         outputs.update(out, inv_gen=res["inv_gen"], target_inv=tgt_ref, target_mask=tgt_mask)

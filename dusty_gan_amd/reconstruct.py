@@ -82,15 +82,15 @@ def project_clouds(lidar, paths, tau, device):
     return {"depth": depth, "mask": mask, "xyz": lidar.inv_to_xyz(inv_ref)}
 
 
-def _side_by_side(pics_target, pics_recon, b):
-    """file b's picture: per row of PICTURES, target beside reconstruction (make_grid of the two), rows stacked and
+def _side_by_side(pics_target, pics_recon, b, names=PICTURES):
+    """file b's picture: per row of `names`, target beside reconstruction (make_grid of the two), rows stacked and
     padded on the right to the widest -> uint8 [H,W,3]"""
     import numpy as np
     import torch
 
     from .utils.render import image_grid
     rows = []
-    for name in PICTURES:
+    for name in names:
         (xt, color, scale), (xr, _, _) = pics_target[name], pics_recon[name]
         rows.append(image_grid(torch.cat([xt[b:b + 1], xr[b:b + 1]], dim=0), color=color, scale=scale).cpu().numpy())
     width = max(r.shape[1] for r in rows)

@@ -461,7 +461,8 @@ int dg_normals(const float* points, int B, int H, int W, int d, float* out, void
  * depth; on a depth tie the LOWER point index), zeros where none did.  status[s] = 1: scan s has a ring row below -64, where
  * numpy's negative index raises - out[s] is all zeros and the caller reports the scan; rows in [-64,-1] wrap to row + 64 as
  * numpy's do.  cell [N] int32 (nullable): every point's row * W + column (-1: not scattered).  Bit-identical from run to
- * run and whatever S is.
+ * run and whatever S is.  ON RETURN every word of keys is (range bits << 32 | the winner's index within its scan) or the
+ * empty word ~0 (csrc/scan_cell.h): the gather does not clear them, and dg_scan_labels reads them.
  * dg_angle_accum / dg_angle_finish: compute_avg_angles  process_kitti.py:143-183.  scans [S,H,W,C] fp32 projected scans
  * (C >= 3) at their own size; per pixel the 32.32 fixed-point sums of pitch = atan2(z, |xy|) and yaw = atan2(y, x) of
  * KITTIOdometry.preprocess's unit-space, range-masked xyz, and the count of pixels with depth > 1e-8, are ADDED to sums
@@ -494,7 +495,9 @@ int dg_angle_finish(const long long* sums, const int* count, int H, int W, float
  *   The winner's four floats are copied bit for bit; a cell without a point is zero.  cell [N] int32 (nullable): every
  *   point's row * W + column, -1 for a point that took no part - also a finite point whose float32 column coordinate
  *   rounds up to W itself (an azimuth a hair above -pi), which has no column here as in dg_scan_project.  keys [S*H*W]
- *   u64: caller-owned workspace, no initial contents required.  Three launches (key fill, scatter, gather).  Bit-identical from run to run, whatever S is, and for
+ *   u64: caller-owned workspace, no initial contents required; ON RETURN every word is (range bits << 32 | the winner's
+ *   index within its scan) or the empty word ~0, as dg_scan_project leaves them (the gather does not clear them;
+ *   dg_scan_labels reads them).  Three launches (key fill, scatter, gather).  Bit-identical from run to run, whatever S is, and for
  *   any permutation of a scan's points up to the tie rule.  DG_EINVAL: a NULL pointer but cell, S < 1, H outside 1..256,
  *   W outside 1..8192, a table that is not strictly descending or holds an entry outside [-4, 4]. */
 int dg_elev_hist(const float* points, const long* offsets, int S, double min_depth, double max_depth, double lo, double hi,
@@ -1027,6 +1030,49 @@ int dg_raydrop_keep(const float* conf, int arch, const int* win, const float* no
 int dg_raydrop_gather(const float* rec, long rec_sb, int stride, int N, const int* win, const unsigned char* keep,
                       const unsigned* labels, int B, int K, int H, int W, int* chunk_counts, float* out_records,
                       unsigned* out_labels, int* out_index, int* out_counts, void* stream);
+
+/* ---- semantic labels on the range image, and label-driven object removal (dusty_gan_amd/datasets/labels.py,
+ * dusty_gan_amd/removal.py; csrc/label_image.hip, csrc/object_removal.hip).  Integer work and bit-for-bit
+ * copies only; no float atomics anywhere.
+ * dg_scan_labels: the SemanticKITTI branch of process_point_clouds  process_kitti.py:120-131.  keys [S*H*W] u64 as
+ *   dg_scan_project or dg_beam_project (same S, H, W, offsets) LEFT them; labels [N] uint32 = the raw `.label` words in the
+ *   points' order; lut: 65536 bytes on the device, entry i = the class of raw id i, 255 = no such id.  sem [S,H,W] uint8 =
+ *   lut[labels[offsets[s] + winner] & 0xFFFF], 0 for an empty cell; inst [S,H,W] uint16 (nullable) = labels >> 16 of the
+ *   winner, 0 for an empty cell: the label of the very record the projection's `out` holds, under its tie rule.  status [S]
+ *   int32, zeroed by the CALLER: status[s] |= 1 (integer atomic OR) when a winner of scan s has an id whose lut entry is 255
+ *   (sem is 255 there).  One launch.  DG_EINVAL: a NULL pointer other than inst, S < 1, H or W < 1.
+ * dg_label_resize: sem [B,Hs,Ws] uint8 -> out [B,H,W] uint8 with dg_scan_to_polar's NEAREST rule (csrc/nearest.h: src =
+ *   min(floor(dst * float(in) / out), in - 1)), no flip.
+ * dg_remove_mask: sem [B,H,W] uint8, valid [B,H,W] fp32 (non-zero = a measured pixel: the target's mask), table: 256 bytes on
+ *   the device (non-zero = remove this class), r in 0..8.  remove [B,H,W] uint8 = 1 where any pixel q with |dh| <= r and
+ *   |dw| <= r has valid[q] && table[sem[q]], else 0; columns wrap around (the azimuth is a ring), rows outside the image take
+ *   no part.  class_pixels [B,256] uint32, zeroed by the CALLER and ADDED to: the valid pixels of every class before
+ *   dilation (counted in LDS, one integer global atomic per non-zero bin per workgroup).  One launch.  B, H <= 65535.
+ * dg_compose_removed: per pixel of [B,H,W]: tgt_inv / valid = the target's inverse depth and mask, gen_inv = the generated
+ *   inverse depth, keep = the generated keep map (keep_is_depth 0: kept where keep != 0; 1: kept where keep > tol -
+ *   evaluate_batch's two rules).  inv_out = tgt_inv's bits where !remove && valid, gen_inv's bits where remove && kept, +0
+ *   elsewhere; source uint8 = 1 (measured), 2 (generated), 0 (empty) respectively; sem_out uint8 = sem, fill_label, 0.
+ *   counts [B,3] int32, zeroed by the CALLER: removed = pixels with remove && valid, filled = pixels with source 2, in_front =
+ *   filled pixels that were valid and whose gen_inv > tgt_inv (a background nearer than the object measured there).  One
+ *   launch; integer atomics only.  fill_label 0..255, B <= 65535.
+ * dg_cloud_remove: for every cloud b, over the records n < counts[b] (nullable = N; clamped to [0, N]) in input order, the
+ *   records with idx[b,n] < 0, idx[b,n] >= H W (took no part in the image) or remove[b, idx[b,n]] == 0: out_records[b,j] =
+ *   the `stride` 32-bit words of record n of rec, bit for bit, column 3 = 0 for stride 3; out_labels[b,j] = labels[b,n]
+ *   (labels [B,N] uint32 and out_labels both, or neither); out_index[b,j] = n; j ascending from 0; out_counts[b] = their
+ *   number.  idx [B,N] as dg_points_to_depth returned it, remove [B,H W].  Outputs are [B,N(,4)]; rows at and beyond the count
+ *   are not written.  chunk_counts: workspace of B ceil(N / DG_EXPORT_CHUNK) int32 (need not be initialised).  Two launches,
+ *   no atomics (csrc/compact.h over records): two calls give the same bytes.  out_records 16-byte aligned. */
+int dg_scan_labels(const unsigned long long* keys, const long* offsets, const unsigned* labels, const unsigned char* lut, int S,
+                   int H, int W, unsigned char* sem, unsigned short* inst, int* status, void* stream);
+int dg_label_resize(const unsigned char* sem, int B, int Hs, int Ws, int H, int W, unsigned char* out, void* stream);
+int dg_remove_mask(const unsigned char* sem, const float* valid, const unsigned char* table, int B, int H, int W, int r,
+                   unsigned char* remove, unsigned* class_pixels, void* stream);
+int dg_compose_removed(const float* tgt_inv, const float* valid, const float* gen_inv, const float* keep, int keep_is_depth,
+                       float tol, const unsigned char* remove, const unsigned char* sem, int fill_label, int B, int H, int W,
+                       float* inv_out, unsigned char* source, unsigned char* sem_out, int* counts, void* stream);
+int dg_cloud_remove(const float* rec, long rec_sb, int stride, const int* counts, const int* idx, const unsigned char* remove,
+                    const unsigned* labels, int B, int N, int H, int W, int* chunk_counts, float* out_records,
+                    unsigned* out_labels, int* out_index, int* out_counts, void* stream);
 
 const char* dg_version(void);
 
