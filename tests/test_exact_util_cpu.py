@@ -329,3 +329,209 @@ def test_folded_bias_slack_admits_the_folded_epilogue_and_no_product_error():
     off = folded(lay.q_fwd + 1)
     lo2, hi2 = X.neighbours(ref - slack, BF)[0], X.neighbours(ref + slack, BF)[1]
     assert bool(((off.double() < lo2) | (off.double() > hi2)).all())
+
+
+# ---- the fp32x3 mode: wide operands, the pair, the split-storage comparators ------------------------------------------------------
+def test_x2_split_is_round_to_nearest_even_twice_and_the_generators_do_what_they_are_for():
+    v = torch.tensor([257.0, 259.0, -257.0, 511.0, 2049.0, 4095.0, 1.0 + 2.0 ** -9, 3.0, 0.0], dtype=torch.float64)
+    hi, lo = X.x2_split(v)
+    assert hi.tolist() == [256.0, 260.0, -256.0, 512.0, 2048.0, 4096.0, 1.0, 3.0, 0.0]      # ties to even, both ways
+    assert lo.tolist() == [1.0, -1.0, -1.0, -1.0, 1.0, -1.0, 2.0 ** -9, 0.0, 0.0]
+    t = torch.tensor([1.0 + 2.0 ** -9 + 2.0 ** -17 + 2.0 ** -23], dtype=torch.float64)    # v - hi needs rounding: lo is bf16 of it
+    hi, lo = X.x2_split(t)
+    assert float(hi) == 1.0 and float(lo) == 2.0 ** -9 + 2.0 ** -16    # (cut toward zero: 2^-9)
+    g = X.gen(3)
+    a = X.wide12((200000,), 0.5, g)
+    nz, opp, _ = X.wide_stats(a)
+    print(f"12-bit class: lo != 0 on {nz:.1%}, opposite signs on {opp:.1%}, max |lo| {float(X.x2_split(a)[1].abs().max()):g}")
+    assert nz >= 0.90 and opp >= 0.40 and float(X.x2_split(a)[1].abs().max()) <= 8
+    assert 0.45 < float((a != 0).double().mean()) < 0.55 and float(a.abs()[a != 0].min()) >= 2048 and float(a.abs().max()) < 4096
+    c = X.wide9((200000,), 1.0, g)
+    nz, _, ties = X.wide_stats(c)
+    assert nz == 1.0 and ties == 1.0 and float(c.abs().min()) >= 257 and float(c.abs().max()) <= 511
+    assert bool((X.x2_split(c)[1].abs() == 1).all())
+    for t in (a, c):
+        hi, lo = X.x2_split(t)
+        assert torch.equal(hi + lo, t)
+    # the planes of a DG_BF16X2 buffer: hi at 2 i - i % 64, lo 64 further
+    raw = torch.arange(512).float()
+    hi, lo = X.x2_planes(raw, 256)
+    assert hi[:3].tolist() == [0.0, 1.0, 2.0] and float(hi[64]) == 128.0 and float(lo[0]) == 64.0 and float(lo[65]) == 193.0
+    aux = X.wide_mask_source((4, 64, 8, 8), g)
+    assert 0.15 < float((aux == 0).double().mean()) < 0.25
+
+
+def _layer_conditions(lay):
+    cls = lay.cls
+    wide = {"A": (lay.x, lay.e, lay.prev), "B": (lay.w, lay.prev), "C": (lay.x, lay.w, lay.e)}[cls]
+    X.assert_wide_conditions(cls, wide, (lay.mass_fwd, lay.mass_bwd, lay.dw_mass()), (lay.fwd_lrelu(), lay.fwd_linear()),
+                             lay.lolo_fwd if cls == "C" else None)
+    nz, opp, _ = X.wide_stats(lay.prev)
+    assert nz >= 0.90 and opp >= 0.40 and 0.1 < float((lay.prev == 0).double().mean()) < 0.3
+    if cls == "B":
+        X.assert_wide_conditions("B", (lay.eg,), ())
+    # every result the comparators take bit for bit is an fp32 number, every operand 16 bits of hi + lo
+    for t in (lay.fwd_linear(), lay.q_bwd * X.BWD_SCALE, lay.dw(0.25, lay.rs), lay.fwd_linear(full=True)):
+        assert torch.equal(t.float().double(), t)
+    for t in (lay.x, lay.w, lay.e, lay.prev, lay.xg, lay.eg):
+        hi, lo = X.x2_split(t)
+        assert torch.equal(hi + lo, t)
+    if cls == "C":
+        assert not torch.equal(lay.q_fwd, lay.q_fwd_full) and not torch.equal(lay.q_bwd, lay.q_bwd_full)
+        assert not torch.equal(lay.dw(1.0), lay.dw(1.0, full=True)) or float(lay.dw(1.0).abs().max()) == 0
+    else:
+        assert torch.equal(lay.q_fwd, lay.q_fwd_full) and torch.equal(lay.q_bwd, lay.q_bwd_full)
+    return float(max(lay.mass_fwd.max(), lay.mass_bwd.max())), float(lay.dw_mass().max())
+
+
+WIDE_LAYER_CASES = ([(w,) + s for w in ("down", "up") for s in X.MFMA_SHAPES] + X.x2_layer_cases())
+
+
+@pytest.mark.parametrize("cls", X.CLASSES)
+@pytest.mark.parametrize("case", WIDE_LAYER_CASES, ids=lambda c: "-".join(str(v) for v in c))
+def test_wide_layer_references_stay_exact_and_carry_low_halves(case, cls):
+    """conditions (b), (c), (d) for every layer tests/test_gpu_x2_exact.py launches, on the reference alone"""
+    m, mw = _layer_conditions(X.Layer(*case, True, cls=cls))
+    print(f"class {cls} {case}: sum |terms| <= 2^{math.log2(m):.1f} (conv passes), 2^{math.log2(max(mw, 1)):.1f} (dW) units")
+
+
+@pytest.mark.parametrize("cls", ["A", "B"])
+@pytest.mark.parametrize("Hc,Wc,B", X.DOWN1_SHAPES)
+def test_wide_down1_references(Hc, Wc, B, cls):
+    _layer_conditions(X.Layer("down", 2, 64, Hc, Wc, B, True, cls=cls))
+
+
+@pytest.mark.parametrize("cls", ["A", "B"])
+@pytest.mark.parametrize("nh", [1, 2, 3])
+@pytest.mark.parametrize("Hc,Wc", X.HEAD_SHAPES)
+def test_wide_head_references(nh, Hc, Wc, cls):
+    h = X.Head(nh, Hc, Wc, cls=cls)
+    X.assert_wide_conditions(cls, {"A": (h.x, h.e, h.prev), "B": (h.w, h.prev, h.eg)}[cls], h.masses(), (h.fwd(),))
+    for t in (h.fwd(), h.q_bwd * X.BWD_SCALE, h.dw(X.pow2_rowscale(h.B, 1)) * 0.5):
+        assert torch.equal(t.float().double(), t)
+
+
+@pytest.mark.parametrize("cls", X.CLASSES)
+@pytest.mark.parametrize("B,N", X.PROJ_SHAPES)
+def test_wide_proj_references(B, N, cls):
+    p = X.Proj(B, N, cls=cls)
+    wide = {"A": (p.z, p.e), "B": (p.w, p.eg), "C": (p.z, p.w, p.e)}[cls]
+    X.assert_wide_conditions(cls, wide, (p.mass, p.dw_mass), (p.fwd(X.EPI_LRELU), p.fwd(X.EPI_LINEAR)), p.lolo if cls == "C" else None)
+    assert torch.equal(p.dw(0.5).float().double(), p.dw(0.5))
+
+
+def _epi(lay, epi):
+    if epi == X.EPI_LINEAR:
+        return lambda q: X.epilogue64(q, X.LIN_SCALE, X.EPI_LINEAR, lay.b)
+    return lambda q: X.epilogue64(q, X.FWD_SCALE, X.EPI_LRELU, lay.b)
+
+
+@pytest.mark.parametrize("cls", X.CLASSES)
+def test_emulated_fp32x3_kernel_passes_every_new_comparator(cls):
+    """float64 emulation of the three-term contraction with x2_split outputs, on the wide integer data"""
+    lay = X.layer("down", *SHAPE, True, cls)
+    fn = lambda a, b: X.down_q(a, b, True)
+    q = X.x3_contract(fn, lay.x, lay.w)
+    assert torch.equal(q, lay.q_fwd)
+    hi, lo = X.x2_store(_epi(lay, X.EPI_LINEAR)(q))
+    X.assert_x2_exact(hi, lo, lay.fwd_linear())
+    hi, lo = X.x2_store(_epi(lay, X.EPI_LRELU)(q))
+    X.assert_x2_close(hi, lo, lay.fwd_lrelu())
+    assert X.x2_rel_error(hi, lo, lay.fwd_lrelu()) <= X.X2_REL
+    # each order of the two constants in fp32, then the pair
+    for f in X.epilogue_f32_foldings(lay.q_fwd, X.FWD_SCALE, X.EPI_LRELU, lay.b):
+        X.assert_x2_close(*X.x2_split(f.double()), lay.fwd_lrelu())
+    # backward-data with the wide mask source, and the weight gradient (fp32 output: the existing comparators)
+    qb = X.x3_contract(lambda e, w: X.adjoint_q(X.down_q, lay.x_shape, w, True, e), lay.e, lay.w)
+    assert torch.equal(qb, lay.q_bwd)
+    hi, lo = X.x2_store(X.epilogue64(qb, X.BWD_SCALE, X.EPI_MASK, None, lay.prev))
+    X.assert_x2_close(hi, lo, lay.bwd_mask())
+    # the slope follows the hi half alone: same decision as the value itself
+    assert torch.equal(X.x2_split(lay.prev)[0] > 0, lay.prev > 0)
+    fold = X.epilogue_f32_foldings(lay.q_fwd, X.FWD_SCALE, X.EPI_LRELU, lay.b)
+    X.assert_faithful(fold[0], lay.fwd_lrelu(), F32, fold)
+    X.assert_exact(lay.dw(0.5, lay.rs).float(), lay.dw(0.5, lay.rs))
+    # a non-canonical pair and a non-zero pair for a zero fail
+    ref = lay.fwd_lrelu()
+    hi, lo = X.x2_split(ref.float().double())
+    step = X.ulp_of(hi, BF) * (ref != 0)
+    with pytest.raises(AssertionError, match="hi plane is not bf16"):
+        X.assert_x2_close(hi + step, lo - step, ref)
+    z = torch.zeros(1, 64, 1, 1, dtype=torch.float64)
+    with pytest.raises(AssertionError, match="planes of a zero"):
+        X.assert_x2_close(z + 1, z - 1, z)
+
+
+FAULT_CLASS = {"seam_xlo_whi_dropped": "A", "last_pixel_hi_hi_only": "A", "output_lo_truncated": "A", "lo_lo_added": "C",
+               "xhi_wlo_missing_one_k_group": "B", "planes_exchanged_one_group": "A"}
+FAULT_BAR = {"seam_xlo_whi_dropped": r"by x % 64: 0:\d+\n", "last_pixel_hi_hi_only": r"by y: 3:\d+\n  by x % 64: 63:\d+\n",
+             "planes_exchanged_one_group": r"by c // 64: 1:\d+$"}
+
+
+@pytest.mark.parametrize("name", [n for n in X.X3_FAULTS if n != "input_lo_truncated"])
+def test_fp32x3_faults_fail_the_new_comparators(name):
+    """each fault the rel-L2 bound of tests/test_gpu_x2.py lets through, on the class of wide data that isolates its term"""
+    cls = FAULT_CLASS[name]
+    lay = X.layer("down", *SHAPE, True, cls)
+    hi, lo = X.x3_fault_down(name, lay.x, lay.w, _epi(lay, X.EPI_LINEAR))
+    with pytest.raises(AssertionError, match="elements wrong") as ei:
+        X.assert_x2_exact(hi, lo, lay.fwd_linear())
+    if name in FAULT_BAR:
+        import re
+        assert re.search(FAULT_BAR[name], str(ei.value)), str(ei.value)
+    if name == "output_lo_truncated":
+        assert "[lo plane]" in str(ei.value)
+        return                                       # (a cut lo is within 2^-16 |v|: the bit-for-bit linear pass is what holds it)
+    hi, lo = X.x3_fault_down(name, lay.x, lay.w, _epi(lay, X.EPI_LRELU))
+    with pytest.raises(AssertionError, match="elements wrong"):
+        X.assert_x2_close(hi, lo, lay.fwd_lrelu())
+    if name != "planes_exchanged_one_group":         # the fp32-output comparators (register split) see the accumulator faults too
+        v = hi + lo
+        q = X.x3_contract(lambda a, b: X.down_q(a, b, True), lay.x, lay.w)
+        assert not torch.equal(v, X.x2_store(_epi(lay, X.EPI_LRELU)(q))[0] + X.x2_store(_epi(lay, X.EPI_LRELU)(q))[1])
+
+
+def test_input_lo_truncation_needs_operands_of_more_than_16_bits():
+    """On the wide integer data hi + lo == x, so x - hi is a bf16 number and cutting it is no fault at all: the contraction
+    cannot see this one.  What holds it is the plane check in front of every launch (packed planes == x2_split) on operands that
+    do need the second rounding - 24-bit integers here, as tests/test_gpu_x2_exact.py casts them."""
+    lay = X.layer("down", *SHAPE, True, "A")
+    hi, lo = X.x3_fault_down("input_lo_truncated", lay.x, lay.w, _epi(lay, X.EPI_LINEAR))
+    X.assert_x2_exact(hi, lo, lay.fwd_linear())
+    v = X.cast_probe((64, 2, 1, 64))
+    whi, wlo = X.x2_split(v)
+    assert bool((whi + wlo != v).any())
+    cut = X.trunc_bf16(v - whi)
+    assert bool((cut != wlo).any())
+    with pytest.raises(AssertionError, match=r"\[lo plane\]"):
+        X.assert_x2_exact(whi, cut, v)
+    X.assert_x2_exact(whi, wlo, v)
+
+
+def test_which_fp32x3_faults_the_rel_l2_bound_accepts():
+    """The written-down justification of tests/test_gpu_x2_exact.py: every fault, under tests/test_gpu_x2.py::test_down_layer's
+    recipe (randn data, its first case, Down 256 -> 128, 8 x 256 input, B = 2) and bound (rel-L2 <= 1e-4 against the full
+    product) - which it accepts, and that each of them fails the per-element comparators (the tests above)."""
+    Ci, Co, H, W, B = SHAPE
+    g = torch.Generator().manual_seed(Ci * 1000 + Co + H)
+    x = torch.randn(B, Ci, 2 * H, 2 * W, generator=g).double()
+    w = torch.randn(Co, Ci, 4, 4, generator=g).double()
+    b = torch.randn(Co, generator=g).double()
+    s = 1.0 / math.sqrt(Ci * 16)
+    epi = lambda q: X.epilogue64(q, s, X.EPI_LRELU, b)
+    full = epi(X.down_q(x, w, True))
+    hi, lo = X.x2_store(epi(X.x3_contract(lambda a, b_: X.down_q(a, b_, True), x, w)))
+    own = rel_l2(hi + lo, full)
+    rows = [("none (the contraction itself)", own, True)]
+    for name in X.X3_FAULTS:
+        hi, lo = X.x3_fault_down(name, x, w, epi)
+        r = rel_l2(hi + lo, full)
+        rows.append((name, r, r < 1e-4))
+    print("\nfault                              rel-L2      test_gpu_x2.py (<= 1e-4)   per-element comparators")
+    for name, r, ok in rows:
+        verdict = "pass" if name.startswith("none") else ("reject (by the plane check on 24-bit operands)" if name == "input_lo_truncated" else "reject")
+        print(f"{name:34s} {r:10.3g}  {'accepts' if ok else 'rejects':26s} {verdict}")
+    got = dict((n, ok) for n, _, ok in rows)
+    assert own < 1e-5
+    for name in ("seam_xlo_whi_dropped", "last_pixel_hi_hi_only", "output_lo_truncated", "input_lo_truncated", "lo_lo_added"):
+        assert got[name], name                       # the bound lets every fault of the issue's table through

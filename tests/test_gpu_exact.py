@@ -133,18 +133,22 @@ def conv(L, trace, monkeypatch, *, mode, adj, ring, x, w_nk, N, scale, epi, dtyp
     return from_nhwc(out.cpu(), B, N, Ho, Wo), None if db is None else db.cpu(), rec
 
 
-def check_layer(L, trace, monkeypatch, which, shape, ring, dtype, force, x3=False, multi=False):
+def check_layer(L, trace, monkeypatch, which, shape, ring, dtype, force, x3=False, multi=False, cls=None):
     """forward EPI_LRELU + bias (faithful, mask_out), forward EPI_LINEAR (exact), backward-data EPI_MASK with zeros in aux,
-    power-of-two per-sample weights and the bias gradient - for bf16 both from the saved mask bits and from aux"""
-    lay = X.layer(which, *shape, ring)
+    power-of-two per-sample weights and the bias gradient - for bf16 both from the saved mask bits and from aux.
+    cls: one of the fp32x3 mode's wide operand classes (X.Layer; fp32 storage only) - condition (c) replaces condition (a)"""
+    lay = X.layer(which, *shape, ring, cls)
     down = which == "down"
     fmode, bmode = (L.MODE_S2, L.MODE_UP) if down else (L.MODE_UP, L.MODE_S2)
     wf, wb = (pack_down if down else pack_up)(lay.w)
     fam = f"{NAMES[force]} {tname(dtype, x3)}"
-    tag = f"{which} {shape} ring={ring}" + (" several tiles per workgroup" if multi else "")
+    tag = f"{which} {shape} ring={ring}" + (" several tiles per workgroup" if multi else "") + (f" class {cls}" if cls else "")
     kw = dict(ring=ring, dtype=dtype, force=force, x3=x3, multi=multi)
-    for p in lay.units():                                   # condition (a), on the reference
-        assert float(p.abs().max()) <= X.Q_MAX
+    if cls is None:
+        for p in lay.units():                               # condition (a), on the reference
+            assert float(p.abs().max()) <= X.Q_MAX
+    else:                                                   # condition (c): every term family an exact fp32 sum
+        assert dtype == F32 and max(float(lay.mass_fwd.max()), float(lay.mass_bwd.max())) < X.EXACT_UNITS
     worst = 0.0
     # forward, leaky-relu + bias
     ref = lay.fwd_lrelu()
@@ -374,15 +378,22 @@ PROJ_KERNELS = [(DG_FORCE_DIRECT, F32, False), (DG_FORCE_MFMA, F32, False), (DG_
 def test_proj_gemm(L, trace, force, dtype, x3, B, N):
     """Proj forward on the direct, MFMA, fp32x3 and weight-streaming kernels (ragged batch 17), both epilogues; its weight
     gradient (wmode 2) on the kernels that have one"""
+    check_proj(L, trace, X.proj(B, N), force, dtype, x3)
+
+
+def check_proj(L, trace, p, force, dtype, x3):
+    """p: X.Proj, small operands or one of the fp32x3 mode's wide classes (fp32 storage)"""
     from dusty_gan_amd.engine import Ops
-    p = X.proj(B, N)
-    fam = f"proj {NAMES[force]} {tname(dtype, x3)}"
+    B, N = p.B, p.N
+    fam = f"proj {NAMES[force]} {tname(dtype, x3)}" + (f" class {p.cls}" if p.cls else "")
+    if p.cls is not None:
+        assert dtype == F32 and max(float(p.mass.max()), float(p.dw_mass.max())) < X.EXACT_UNITS      # condition (c)
     o = Ops(dtype, x3=x3)
     o.force = force
     zd, wd, bd = p.z.to(DEV, dtype).contiguous(), p.w.to(DEV, dtype).contiguous(), p.b.to(DEV, F32)
     worst = 0.0
     for epi, code, scale in ((X.EPI_LRELU, L.EPI_LRELU, X.FWD_SCALE), (X.EPI_LINEAR, L.EPI_LINEAR, X.LIN_SCALE)):
-        assert float(p.units(epi).abs().max()) <= X.Q_MAX
+        assert p.cls is not None or float(p.units(epi).abs().max()) <= X.Q_MAX
         out = torch.full((B, N), float("nan"), device=DEV, dtype=dtype)
         n0 = len(trace)
         o.conv(L.MODE_GEMM, 0, 1, B, 1, 1, p.K, N, zd, (p.K, 0, 1), out, (N, 0, 1), wd.data_ptr(), scale, code,
@@ -399,7 +410,7 @@ def test_proj_gemm(L, trace, force, dtype, x3, B, N):
             X.assert_faithful(out.cpu(), ref, dtype, fold, f"{fam} lrelu {(B, N)}", slack)
             worst = X.max_ulp_error(out.cpu(), ref, dtype)
     if force != DG_FORCE_PROJ_STREAM:
-        ed = p.e.to(DEV, dtype).contiguous()
+        ed, zd = p.eg.to(DEV, dtype).contiguous(), p.zg.to(DEV, dtype).contiguous()
         for acc in (0, 1):
             base = torch.randint(-4, 5, (N, p.K), generator=X.gen(B)).double()
             dw = base.to(DEV, F32) if acc else torch.full((N, p.K), float("nan"), device=DEV)
@@ -421,12 +432,16 @@ def wgrad_args(lay, a, e):
     return 1, (H * W * Ci, Ci, 1), (4 * H * W * Co, Co, 1)
 
 
-def check_wgrad(L, trace, lay, force, dtype, x3, fam, variants, pairs=None):
+def check_wgrad(L, trace, lay, force, dtype, x3, fam, variants, pairs=None, put=None):
     """dW of one layer, torch.equal against float64: workspace and atomics path, accumulate onto an integer-valued dW and
-    overwrite of a NaN-filled one, per-sample weights cycling 0.5 / 1 / 2, the gradient-sample map where the kernel has it"""
+    overwrite of a NaN-filled one, per-sample weights cycling 0.5 / 1 / 2, the gradient-sample map where the kernel has it.
+    put: how an operand (NCHW float64) gets onto the device (default: pixel-major in `dtype`; the split-storage tests pack it)"""
     from dusty_gan_amd.engine import Ops
     variants = variants if isinstance(variants, tuple) else (variants,)
-    xd, ed = nhwc(lay.x).to(DEV, dtype), nhwc(lay.e).to(DEV, dtype)
+    put = put or (lambda t: nhwc(t).to(DEV, dtype))
+    xd, ed = put(lay.xg), put(lay.eg)
+    if lay.cls is not None:                                 # condition (c) for the weight gradient's own contraction
+        assert float(lay.dw_mass().max()) < X.EXACT_UNITS
     wmode, sa, sg = wgrad_args(lay, xd, ed)
     B, H, W, Ci, Co = lay.B, lay.H, lay.W, lay.Ci, lay.Co
     seen = set()
@@ -459,7 +474,7 @@ def check_wgrad(L, trace, lay, force, dtype, x3, fam, variants, pairs=None):
         torch.cuda.synchronize()
         X.assert_exact(dw.cpu(), lay.dw(0.5, rs, g_mod), f"{fam} weight gradient {lay.which} g_mod={g_mod}")
         mapped = True
-    print(f"[exact] {fam} weight gradient {lay.which} {(Ci, Co, H, W, B)}: exact; kernels (variant, workspace) {sorted(seen)}"
+    print(f"[exact] {fam} weight gradient {lay.which} {(Ci, Co, H, W, B)}{f' class {lay.cls}' if lay.cls else ''}: exact; kernels (variant, workspace) {sorted(seen)}"
           f"{' + sample map' if mapped else ''}")
     return seen
 
@@ -495,13 +510,18 @@ def test_weight_gradient(L, trace, which, force, dtype, x3, shape):
 @pytest.mark.parametrize("force", [DG_FORCE_MFMA, DG_FORCE_WG_DMA_PAIRS, DG_FORCE_WG_DMA_NOPAIRS], ids=["auto", "tap-pairs", "single-taps"])
 def test_weight_gradient_group_of_three_layers(L, trace, wmode, force):
     """one `with ops.grouped():` block of three layers: each layer's dW is the float64 result, as the three single launches'"""
-    from dusty_gan_amd import engine as E
     which = "down" if wmode == 0 else "up"
     lays = [X.Layer(which, *s, True) for s in ((64, 128, 4, 128, 2), (128, 64, 2, 64, 1), (64, 64, 3, 64, 3))]
-    data = [(nhwc(l.x).to(DEV, BF), nhwc(l.e).to(DEV, BF)) for l in lays]
+    check_wgrad_group(L, trace, lays, force, BF, lambda t: nhwc(t).to(DEV, BF))
+
+
+def check_wgrad_group(L, trace, lays, force, dtype, put):
+    """put: as in check_wgrad"""
+    from dusty_gan_amd import engine as E
+    data = [(put(l.xg), put(l.eg)) for l in lays]
 
     def run(grouped):
-        o = E.Ops(BF)
+        o = E.Ops(dtype)
         o.force = force
         outs = [l.base.to(DEV, F32) for l in lays]
         prev, E.Ops.group_enabled = E.Ops.group_enabled, grouped

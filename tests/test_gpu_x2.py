@@ -67,10 +67,14 @@ def weights_x2(E, w_nk):
     return wd, tw
 
 
-def run_conv_x2(L, mode, adj, x, w_nk, N, scale, epi, force, bias=None, aux=None, want_db=False, rowscale=None):
+def run_conv_x2(L, mode, adj, x, w_nk, N, scale, epi, force, bias=None, aux=None, want_db=False, rowscale=None,
+                planes=False, wg_cap=0, rec=None, check=None):
+    """planes: return the output's two planes (hi, lo), NCHW float64, instead of their fp32 sum; wg_cap: the persistent conv's
+    workgroup cap (DgConv launch argument); rec: a list that receives the launch's TRACE record; check(x_dev, w_twin, aux_dev):
+    called on the packed operands in front of the launch"""
     from dusty_gan_amd import engine as E
     o = E.Ops(torch.float32)
-    o.force = force
+    o.force, o.wg_cap = force, wg_cap
     B, K, Hin, Win = x.shape
     if mode == L.MODE_S2:
         Hc, Wc, Ho, Wo = Hin // 2, Win // 2, Hin // 2, Win // 2
@@ -78,11 +82,13 @@ def run_conv_x2(L, mode, adj, x, w_nk, N, scale, epi, force, bias=None, aux=None
         Hc, Wc, Ho, Wo = Hin, Win, 2 * Hin, 2 * Win
     xd = to_x2(nhwc(x))
     wd, tw = weights_x2(E, w_nk)
-    out = E.tag_x2(torch.full((B * Ho * Wo * N,), 3.0, device=DEV))
+    out = E.tag_x2(torch.full((B * Ho * Wo * N,), float("nan") if planes else 3.0, device=DEV))
     auxd = None if aux is None else to_x2(nhwc(aux))
     biasd = None if bias is None else bias.to(DEV)
     db = torch.zeros(N, device=DEV) if want_db else None
     rs = None if rowscale is None else rowscale.to(DEV)
+    if check is not None:
+        check(xd, tw, auxd)
     E.TRACE = []
     try:
         if force == L.DG_FORCE_DIRECT:   # the direct kernel reads the split weights through dg_ld like everything else
@@ -93,13 +99,20 @@ def run_conv_x2(L, mode, adj, x, w_nk, N, scale, epi, force, bias=None, aux=None
             o.conv(mode, adj, True, B, Hc, Wc, K, N, xd, (Hin * Win * K, K, 1), out, (Ho * Wo * N, N, 1), wd.data_ptr(), scale, epi,
                    bias=None if biasd is None else biasd.data_ptr(), bias_mod=N, aux=auxd,
                    dbias=None if db is None else db.data_ptr(), rowscale=rs)
-        fam = [t for t in E.TRACE if t[0] == "conv"][0][1]
+        convs = [t for t in E.TRACE if t[0] == "conv"]
+        fam = convs[0][1]
+        if rec is not None:
+            rec.extend(convs)
     finally:
         E.TRACE = None
         E.X2_TWIN.pop(wd.data_ptr(), None)
     torch.cuda.synchronize()
     assert fam == (L.DG_CONV_FAMILY_DIRECT if force == L.DG_FORCE_DIRECT else L.DG_CONV_FAMILY_PINGPONG), fam
-    res = from_nhwc(from_x2(out).cpu(), B, N, Ho, Wo)
+    if planes:
+        from tests.exact_util import x2_planes
+        res = tuple(from_nhwc(h, B, N, Ho, Wo) for h in x2_planes(out.view(torch.bfloat16).cpu().float(), out.numel()))
+    else:
+        res = from_nhwc(from_x2(out).cpu(), B, N, Ho, Wo)
     return (res, db.cpu()) if want_db else res
 
 
